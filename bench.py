@@ -11,7 +11,7 @@ eigenvalues of X*X*' and its trace (src/criteria.jl:5, :35-46), so the timed
 job runs the eigensolve (factored identity: H.Z GEMMs + per-replicate
 Rayleigh-Ritz, Kato-Temple eigenvalue stopping rule) and does NOT form the
 replicate factors F*, loadings L* or the OLS + HC2 regression.  The line's
-`all_fields` extra (timed separately, after the headline region) is the rate
+`all_fields` extra (`--full`; timed separately, after the headline region) is the rate
 with the whole regression record per replicate — F*, L*, all OLS
 coefficients and HC2 t-statistics (src/DynamicFactorModel.jl:28-51).  Replicates shard
 across ranks (strong scaling, as BASELINE.json configs[2] states: the 9999
@@ -19,8 +19,20 @@ replicates of a step are sharded contiguously over the ranks, replicate b on
 rank floor(b N / B); a weak-scaling extra field reruns with 9999 per rank).  Inputs (the fitted base model and every replicate's idx/eta) are
 resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up
+steps, the K timed steps, and the result line (the roofline and per-kernel
+fields of the line come from the library's HIP events over the timed steps
+themselves).  `--full` adds the measurements that take runs of their own after
+the timed region: the `all_fields` rate, the weak-scaling rate (N > 1) and the
+CPU baseline (`--no-all-fields`, `--no-weak`, `--no-cpu-baseline` leave one of
+them out of a `--full` run).  `--dump-outputs DIR` saves what the last timed
+step returned to its caller as `DIR/<name>.npy` (float64): the gathered
+per-replicate statistic rows (`rows.npy`; `windows.npy` for `--workload c5`).
+Every input is drawn from fixed seeds, so two builds run with the same
+arguments can be compared output for output.
 
 A plain `python bench.py --gpus N` with N > 1 (no torchrun environment) is a
 launcher: before anything touches a GPU it starts `torch.distributed.run` with
@@ -232,6 +244,23 @@ def hbm_rooflines(timing, eig, Bn, steps, pz=16):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, **arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64.  The files
+    hold at most 64 MB together: an array over its share is cut down to a
+    fixed, seeded sample of its rows (in order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.atleast_1d(np.asarray(a, dtype=np.float64))
+        keep = share // max(a[0].nbytes, 1) if len(a) else 0
+        if len(a) > keep:
+            a = a[np.sort(np.random.default_rng(20261015).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -285,10 +314,15 @@ def main():
                          "T=2000 N=20000, windows sharded over the ranks (strong scaling)")
     ap.add_argument("--rolling", type=int, default=0,
                     help="c5: rolling windows of this many rows instead of expanding windows")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling extra field (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the extras that take runs of their own: the "
+                         "all_fields rate, the weak-scaling rate (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-weak", action="store_true", help="--full without the weak-scaling extra field (N > 1)")
     ap.add_argument("--no-all-fields", action="store_true",
-                    help="skip the all_fields extra (the job with the whole regression record per replicate: F*, "
+                    help="--full without the all_fields extra (the job with the whole regression record per replicate: F*, "
                          "L*, OLS formed) — for rocprofv3 runs whose trace must hold the headline launches only")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dump-rows", default="",
@@ -361,11 +395,18 @@ def main():
     nloc = b1 - b0
     nsteps = args.warmup + args.steps
     idx_d, eta_d = [], []
-    for s in range(nsteps):
-        idx, eta = D.draw_wild_fast(1_000_003 + s, Bn, T)
-        idx_d.append(torch.from_numpy(np.ascontiguousarray(idx[b0:b1])).to(dev))
-        eta_d.append(torch.from_numpy(np.ascontiguousarray(eta[b0:b1])).to(dev))
-        del idx, eta
+    # a step's draws come from its own seeded generator, so the host draws
+    # several steps at a time on threads (NumPy's generators release the GIL)
+    # without changing a value; a group at a time bounds the host copies
+    from concurrent.futures import ThreadPoolExecutor
+    group = max(1, min(8, cpu_share()[0] // world))
+    with ThreadPoolExecutor(group) as pool:
+        for s0 in range(0, nsteps, group):
+            for idx, eta in pool.map(lambda s: D.draw_wild_fast(1_000_003 + s, Bn, T),
+                                     range(s0, min(s0 + group, nsteps))):
+                idx_d.append(torch.from_numpy(np.ascontiguousarray(idx[b0:b1])).to(dev))
+                eta_d.append(torch.from_numpy(np.ascontiguousarray(eta[b0:b1])).to(dev))
+                del idx, eta
     out = torch.empty((max(nloc, 1), width), dtype=torch.float64, device=dev)
     holder = {}
     torch.cuda.synchronize()
@@ -405,8 +446,10 @@ def main():
     ctx.enable_timing(False)
     timing = ctx.read_timing()
     eig = ctx.eig_stats()
+    # what the last timed step handed its caller, taken before any extra runs
+    res = holder["rows"].cpu().numpy()
     weak = None
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         # weak scaling (extra field): every rank runs a full B-replicate job on
         # its own draws, K steps
         wi, we = [], []
@@ -437,7 +480,7 @@ def main():
     # headline job's launches (its H.Z GEMM average then agrees with the
     # HIP-event roofline of the same run).
     full = None
-    if not args.no_all_fields and world == 1 and nloc:
+    if args.full and not args.no_all_fields and world == 1 and nloc:
         fstats = stats + [D.Stat.coefficient(j) for j in range(1, R + 2)] + [D.Stat.t_stat(j) for j in range(1, R + 2)]
         farr = D.api._stat_array(fstats)
         fwidth = int(ctx.lib.dfm_stats_width(model.handle, farr, len(fstats)))
@@ -453,10 +496,11 @@ def main():
                 "value": round(nloc * fk / fel, 2), "unit": "replicates/s", "ms_per_step": round(fel / fk * 1e3, 3),
                 "steps": fk}
         del fout
-    res = holder["rows"].cpu().numpy()
     ok = bool(np.all(np.isfinite(res))) and res.shape[0] >= Bn if dist is not None else bool(np.all(np.isfinite(res)))
     if args.dump_rows and rank == 0:
         np.save(args.dump_rows, res[:Bn])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows=res[:Bn])
 
     total = Bn * args.steps
     value = total / el
@@ -532,7 +576,7 @@ def main():
         rec["all_fields"] = full
     if weak:
         rec["weak_scaling"] = weak
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     if rank == 0:
         print(json.dumps(rec), flush=True)
@@ -600,6 +644,8 @@ def bench_windows(args, D, ctx, torch, dist, world, rank, dev, comm_dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     allrows = holder["all"].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, windows=allrows[:P5])
     gram_ms, gram_n = timing.get("gram", (0.0, 0))
     roof = None
     if gram_n:   # rank-local prefix Gram of the rows its windows reach: m (m+1) N flop (SYRK count)

@@ -54,19 +54,12 @@ def test_ic_sweep_rejects_bad_args(lib):
 
 
 def test_context_creation_fails_cleanly_without_gpu(dfm):
-    import torch  # noqa: F401  (device count only; no GPU init)
-    if os.environ.get("HIP_VISIBLE_DEVICES") is None and dfm_has_gpu():
-        pytest.skip("a GPU is present")
+    """A context on a device that is not there raises DFMError: device 0 on a
+    host without a GPU, the first index past the visible ones on a host with
+    some (whatever HIP_VISIBLE_DEVICES says, the count is the runtime's)."""
+    import torch
     with pytest.raises(dfm.DFMError):
-        dfm.Context(0)
-
-
-def dfm_has_gpu():
-    try:
-        import torch
-        return torch.cuda.device_count() > 0
-    except Exception:
-        return False
+        dfm.Context(torch.cuda.device_count())
 
 
 def test_product_never_imports_the_oracle():

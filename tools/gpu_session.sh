@@ -5,7 +5,7 @@
 # Usage: tools/gpu_session.sh TAG STEP...   (output under gpurun_out/TAG)
 # Steps (each under its own time limit; the session stops at the first failure):
 #   tests      the -m gpu suite (pytest.txt)
-#   bench      the default bench line (bench.json)
+#   bench      the bench line with its --full extras (bench.json)
 #   prof       rocprofv3 --kernel-trace --stats of the headline workload (prof/)
 #   trace      per-dispatch kernel trace of a 3-step C3 run (TRACE_ARGS: extra bench.py flags)
 #   pmc        FETCH_SIZE and WRITE_SIZE passes of the C3 GEMM + passes -> pmc_traffic.json
@@ -52,7 +52,7 @@ for step in "$@"; do
         || fail tests $? "$OUT/pytest.txt"
       tail -2 "$OUT/pytest.txt" ;;
     bench)
-      timeout -k 10 300 python3 -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || fail bench $? "$OUT/bench.err"
+      timeout -k 10 300 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || fail bench $? "$OUT/bench.err"
       line "$OUT/bench.json" bench ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof" -o run -- python3 bench.py \
