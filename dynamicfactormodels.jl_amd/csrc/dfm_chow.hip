@@ -22,6 +22,7 @@
 //         reference's T x T diagm sandwich (:25-33).
 #include <algorithm>
 
+#include "dfm_internal.h"
 #include "dfm_small.h"
 
 namespace dfm {

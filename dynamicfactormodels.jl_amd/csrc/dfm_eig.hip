@@ -16,7 +16,7 @@
 //   final : sign canonicalisation (largest-|.| entry positive, first index).
 // Converged when ||G u_j - theta_j u_j|| <= tol * |theta_1| for j < k.
 // Deterministic: fixed-order reductions only, no float atomics.
-#include "dfm_common.h"
+#include "dfm_internal.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -873,7 +873,6 @@ size_t eig_workspace_bytes_padded(int m, int nb, int P, int maxit) {
   return eig_workspace_bytes(m, nb, P, maxit) + 16 * 256;
 }
 
-typedef void (*timer_fn)(void *ctx, int cls, int begin);
 // Jacobi sweeps per Rayleigh-Ritz step.  The projected matrix need not be
 // diagonalised exactly at every outer iteration: the next iteration starts
 // from the (nearly) rotated basis, so the inner sweeps accumulate across outer
@@ -1511,13 +1510,6 @@ int eig_run(const double *G, int64_t ldg, int64_t strideG, int m, int nb, int k,
 #endif
 constexpr int BW = DFM_BW;   // dynamic LDS of ap2: 16 T + 4 bytes
 
-struct FactBase {
-  int T, r;
-  int64_t ldH;
-  const double *F, *EL, *S, *H, *cF, *hd;   // T x r, T x r, r x r, T x ldH, T, T
-  const double *FtF = nullptr;   // F'F (16 x 16) when the model holds it (else computed per solve)
-};
-
 // Z, the H.Z GEMM's B operand, replicate-major in 16-row chunks (round 6,
 // gemmh_zrm_kernel): replicate rep's element (s, c) at
 // rep zrs + (s >> 4) 16 pz + 16 c + (s & 15), zrs = round_up(T, 16) pz; the
@@ -1752,16 +1744,6 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
   for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
   if (tid == 0) trace[rep] = red[0];
 }
-
-hipError_t launch_gemm_loadings(const double *Eaug, int64_t lda, const double *ZF, int Kp, int rp, int N, int nrep,
-                                int K, int r, double invT, double *Lout, hipStream_t st);
-hipError_t launch_gemm(bool a_trans, const double *A, int64_t lda, const double *B, int64_t ldb,
-                       double *C, int64_t ldc, int M, int Nc, int K, hipStream_t st,
-                       const int *col_done = nullptr, int col_group = 1, bool b_padded = false,
-                       const int *clist = nullptr, const int *ccount = nullptr);
-hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz, int64_t zrs, double *C,
-                           int64_t ldc, int M, int Nc, int K, hipStream_t st, const int *col_done, const int *clist,
-                           const int *ccount);
 
 // Z (the GEMM's B operand) has round_up(T, 16) rows, the pad rows zero, so
 // the H.Z GEMM streams it with running DMA pointers and no k-tail clamp

@@ -12,7 +12,7 @@
 // those of the Gram kernel (dfm_gram.hip); grid order is XCD-aware: the row
 // blocks of one column block are issued to one XCD so a B tile is fetched
 // from HBM once and re-read from that XCD's L2.
-#include "dfm_common.h"
+#include "dfm_internal.h"
 #include <cstdlib>
 
 namespace dfm {
@@ -768,8 +768,7 @@ hipError_t launch_gram_dma(const double *X, int64_t ld, int m, int K, int S, int
 // the register-staged kernel runs.
 hipError_t launch_gemm(bool a_trans, const double *A, int64_t lda, const double *B, int64_t ldb,
                        double *C, int64_t ldc, int M, int Nc, int K, hipStream_t st,
-                       const int *col_done = nullptr, int col_group = 1, bool b_padded = false,
-                       const int *clist = nullptr, const int *ccount = nullptr) {
+                       const int *col_done, int col_group, bool b_padded, const int *clist, const int *ccount) {
   const int nrb = (M + GT - 1) / GT, ncb = (Nc + GT - 1) / GT;
   const int ncb8 = (ncb + 7) / 8 * 8;
   dim3 grid(nrb * ncb8), block(256);

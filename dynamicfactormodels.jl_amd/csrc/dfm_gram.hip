@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "dfm_common.h"
+#include "dfm_internal.h"
 
 namespace dfm {
 
@@ -222,9 +222,6 @@ int gram_ksplit(int m, int K) {
   return std::max(1, std::min(16, K / 1536));
 }
 
-hipError_t launch_gram_dma(const double *X, int64_t ld, int m, int K, int S, int ksteps, double *G, int64_t ldg,
-                           int64_t strideZ, hipStream_t st, double alpha);
-int gram_dma_slots(int m);
 // K-split of ONE plain-panel Gram (no replicate batch, so no batch
 // invariance to keep): enough (tile, split) workgroups to fill the chip's
 // resident slots (gram_dma_slots) several times over with a last round >= 90 % full, each
@@ -616,10 +613,6 @@ __global__ __launch_bounds__(256) void gram_wk_combine_kernel(const double *__re
     if (m2 < N && n2 < m2) Gr[(int64_t)n2 * N + m2] = tile[b][a];
   }
 }
-
-hipError_t launch_gemm(bool a_trans, const double *A, int64_t lda, const double *B, int64_t ldb,
-                       double *C, int64_t ldc, int M, int Nc, int K, hipStream_t st,
-                       const int *col_done, int col_group, bool b_padded, const int *clist, const int *ccount);
 
 // gram_wk_prep_kernel's dynamic LDS: se (T), sF (T x r), sx (round_up(T, 8) ints), the
 // bucket bounds (round_up(T + 1, 8) ints) and the bucketed t (T ints)

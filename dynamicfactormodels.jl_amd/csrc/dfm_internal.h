@@ -1,0 +1,185 @@
+// dfm_internal.h — the one declaration of every libdfm symbol that one .hip
+// file defines and another uses, grouped by the defining file.  Every .hip
+// includes it; default arguments live here only.
+#pragma once
+#include "dfm_common.h"
+
+struct dfm_ctx;   // dfm_host.h
+
+namespace dfm {
+
+// ---- shared types
+typedef void (*timer_fn)(void *ctx, int cls, int begin);
+struct StatDesc { int kind, arg0, arg1, off; };   // uploaded; indexed by stats_kernel
+struct FactBase {   // passed by value into the factored kernels
+  int T, r;
+  int64_t ldH;
+  const double *F, *EL, *S, *H, *cF, *hd;   // T x r, T x r, r x r, T x ldH, T, T
+  const double *FtF = nullptr;   // F'F (16 x 16) when the model holds it (else computed per solve)
+};
+
+// ---- dfm_ctx.hip
+int ctx_fail(dfm_ctx *ctx, int code, const char *msg);
+hipStream_t ctx_stream(dfm_ctx *ctx);
+int ctx_device(dfm_ctx *ctx);
+
+// ---- dfm_gram.hip
+hipError_t launch_gram(int orient, const PanelSrc &src, int m, int K, int T, double *G, int64_t ldg,
+                       int64_t strideG, int nrep, hipStream_t st);
+hipError_t launch_gram_plain_scaled(const double *X, int64_t ld, int m, int K, double *G, int64_t ldg, double alpha,
+                                    hipStream_t st);
+size_t gram_wk_prep_lds(int T, int r);
+int64_t gram_wk_ldk(int N);
+int gram_wk_tp(int T);
+hipError_t gram_wk_precompute(const double *Ep, int64_t ld, int T, int N, int r, const double *F, const double *L,
+                              double *K, double *A0, hipStream_t st);
+size_t gram_wk_work(int T, int N, int r, int nb);
+double *gram_wk_scratch(double *work, int T, int N, int r, int nb);
+hipError_t launch_gram_wk(const double *Ep, int64_t ld, int T, int N, int r, const double *F, const double *L,
+                          const double *K, const double *A0, const int32_t *idx, const double *eta, int64_t rs,
+                          int nb, double *work, double *G, hipStream_t st);
+
+// ---- dfm_gemm.hip
+hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz, int64_t zrs, double *C,
+                           int64_t ldc, int M, int Nc, int K, hipStream_t st, const int *col_done, const int *clist,
+                           const int *ccount);
+hipError_t launch_gemm_loadings(const double *Eaug, int64_t lda, const double *ZF, int Kp, int rp, int N, int nrep,
+                                int K, int r, double invT, double *Lout, hipStream_t st);
+int gram_dma_slots(int m);
+hipError_t launch_gram_dma(const double *X, int64_t ld, int m, int K, int S, int ksteps, double *G, int64_t ldg,
+                           int64_t strideZ, hipStream_t st, double alpha);
+hipError_t launch_gemm(bool a_trans, const double *A, int64_t lda, const double *B, int64_t ldb,
+                       double *C, int64_t ldc, int M, int Nc, int K, hipStream_t st,
+                       const int *col_done = nullptr, int col_group = 1, bool b_padded = false,
+                       const int *clist = nullptr, const int *ccount = nullptr);
+
+// ---- dfm_eig.hip
+__global__ void eig_trace_kernel(const double *__restrict__ G, int64_t ldg, int64_t strideG, int m,
+                                 double *__restrict__ trace);
+const int *eig_iters_ptr(char *ws, int m, int nb, int P, int maxit);
+size_t eig_workspace_bytes_padded(int m, int nb, int P, int maxit);
+extern thread_local int g_last_iters;   // per host thread: dfm_bootstrap_multi's shards run concurrently
+extern thread_local int64_t g_last_rep_iters;
+extern thread_local int64_t g_last_gemm_products;
+int eig_block_p(int m, int k, int req);
+int fact_block_p(int m, int k, int req);
+int eig_run(const double *G, int64_t ldg, int64_t strideG, int m, int nb, int k, int p,
+            const double *warm, int kw, double tol, int maxit, int poll, char *ws, double *lam,
+            double *Uk, double *trace_out, int *status, int *iters_host, hipStream_t st,
+            timer_fn tf, void *tctx, int64_t rep0, int subspace = 0);
+size_t fact_workspace_bytes(int T, int nb, int P);
+int eig_run_factored(const FactBase &fb, const int32_t *idx, const double *eta, int nb, int k, int p,
+                     const double *warm, int kw, double tol, int maxit, int poll, char *ws, char *fws,
+                     double *lam, double *Uk, double *trace_out, int *status, hipStream_t st,
+                     timer_fn tf, void *tctx, int *off, int *lst, long long *cnt = nullptr, int subspace = 0,
+                     double spread = 0.0, const PollBuf *pb = nullptr);
+int fact_t_max();
+int fact_loadings(const FactBase &fb, const double *Ep, int64_t ld, int N, const double *Lb,
+                  const double *Uk, const double *eta, const int *off, const int *lst, int nb,
+                  double *Fout, double *Lout, char *ws, hipStream_t st);
+size_t fact_loadings_bytes(int T, int N, int r, int nb);
+hipError_t launch_fact_fsf(int T, int r, const double *Fb, const double *S, double *FSF, int64_t ldH, hipStream_t st);
+hipError_t launch_gram_fact(const FactBase &fb, const double *FSF, const int32_t *idx, const double *eta, int nb,
+                            double *G, int64_t ldg, int64_t strideG, hipStream_t st);
+hipError_t launch_fact_ftf(const FactBase &fb, double *FtF, hipStream_t st);
+int fact_precompute(const double *Ep, int64_t ld, int T, int N, int r, const double *Lb, const double *Fb,
+                    const double *H, int64_t ldH, double *EL, double *S, double *cF, double *hd, hipStream_t st);
+int spectrum_max();
+hipError_t launch_spectrum_jacobi(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,
+                                  double *ev, hipStream_t st);
+
+// ---- dfm_model.hip
+__global__ void panel_from_colmajor_kernel(const double *__restrict__ X, int64_t ldx, int T, int N,
+                                           double *__restrict__ P, int64_t ld);
+__global__ void colmajor_from_rows_kernel(const double *__restrict__ P, int64_t ld, int T, int N,
+                                          double *__restrict__ X);
+__global__ void colssr_cols_kernel(const double *__restrict__ G, int64_t ldg, int64_t strideG, int N,
+                                   int k, const double *__restrict__ lam,
+                                   const double *__restrict__ Uk, double *__restrict__ colssr);
+__global__ void common_residual_kernel(const double *__restrict__ X, int64_t ld, int T, int N, int k,
+                                       const double *__restrict__ F, const double *__restrict__ L,
+                                       double *__restrict__ C, double *__restrict__ E);
+__global__ void panel_row_ssq_kernel(const double *__restrict__ E, int64_t ld, int T,
+                                     double *__restrict__ rows);
+__global__ void ordered_sum_kernel(const double *__restrict__ v, int n, double *__restrict__ out);
+hipError_t launch_ols(int nb, hipStream_t st, const double *y, const double *w, int q, const double *F, int Tphys,
+                      int kF, const int *Tn, const int *kr, double *coef, double *tstat, double *cov_out,
+                      double *resid_out, int *status, const int *R0 = nullptr);
+__global__ void tail_sigma2_kernel(const double *__restrict__ ev, int m, int h, int nb, double NT,
+                                   double *__restrict__ sig2);
+__global__ void stats_kernel(int nb, int T, int N, int r, int q, int crit, double sigma2,
+                             const double *__restrict__ sig2v,
+                             const double *__restrict__ lam, const double *__restrict__ trace,
+                             const double *__restrict__ coef, const double *__restrict__ tstat,
+                             const int *__restrict__ iters, const StatDesc *__restrict__ sd, int ns,
+                             double *__restrict__ out, int64_t width, const int *__restrict__ st1,
+                             const int *__restrict__ st2, int *__restrict__ flag);
+int launch_factors(int orient, const PanelSrc &src, int T, int N, int k, int nb,
+                   const double *Uk, double *F, double *L, double *colssr, hipStream_t st,
+                   double Ts = 0, int64_t fstride = 0);
+bool launch_factors_cols_fact(const double *Ep, int64_t ld, int T, int N, int k, const double *Fb, const double *Lb,
+                              int rb, const int32_t *idx, const double *eta, int64_t rs, int nb, const double *Uk,
+                              double *F, double *L, int64_t fstride, double *G, hipStream_t st);
+__global__ void col_ssq_kernel(const double *__restrict__ E, int64_t ld, int T, int N,
+                               double *__restrict__ out);
+__global__ void block_accum_kernel(const double *__restrict__ lam_b, const double *__restrict__ tr_b,
+                                   int nb, int r, double *__restrict__ lam, double *__restrict__ tr,
+                                   int first);
+
+// ---- dfm_chow.hip
+size_t chow_workspace_bytes(int T, int N, int r, int nb);
+hipError_t launch_chow(int orient, const PanelSrc &src, int T, int N, int r, int bp, int nb,
+                       const double *F, const double *Lm, double *LRo, double *LMo, double *WDo,
+                       int64_t out_stride, char *ws, size_t ws_bytes, hipStream_t st, int nblk = 1,
+                       const int *brow = nullptr, int64_t lbs = 0);
+size_t targeted_workspace_bytes(int mode, int T, int N, int q);
+hipError_t launch_targeted(int mode, const double *y, const double *w, int q, const double *Xp,
+                           int64_t ld, int T, int N, double cv, double *tstat, uint8_t *mask, char *ws,
+                           size_t ws_bytes, hipStream_t st, int *bad);
+
+// ---- dfm_spec.hip
+int64_t spectrum_work(int m, int nb);
+int spectrum_any_max();
+hipError_t launch_spectrum_var(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,
+                               double *ev, double *work, hipStream_t st);
+hipError_t launch_spectrum(const double *G, int64_t ldg, int64_t strideG, int m, int nb, double *ev,
+                           double *work, hipStream_t st);
+int dense_eig_max();
+int64_t dense_eig_work(int m, int k);
+hipError_t launch_dense_eig_batched(const double *G, int64_t ldg, int64_t strideG, int m, int mv0, int dmv, int nb,
+                                    int k, double *lam, double *Uk, double *trace, int *status, double *work,
+                                    hipStream_t st);
+hipError_t launch_dense_eig(const double *G, int64_t ldg, int m, int k, double *lam, double *Uk, double *trace,
+                            int *status, double *work, hipStream_t st);
+
+// ---- dfm_wide.hip
+hipError_t gemm_batched(int nb, int M, int Nc, int K, double alpha, const double *A, int64_t sAr, int64_t sAc,
+                        int64_t sAb, const double *B, int64_t sBr, int64_t sBc, int64_t sBb, double beta, double *C,
+                        int64_t sCr, int64_t sCc, int64_t sCb, hipStream_t st);
+hipError_t launch_materialize(const PanelSrc &src, int T, int N, int64_t ld, int nb, double *X, hipStream_t st);
+int launch_factors_wide(int orient, const double *X, int64_t ld, int T, int N, int k, const double *Uk,
+                        double *F, double *L, double *colssr, hipStream_t st, double Ts, int nb = 1, int64_t sX = 0,
+                        int64_t fstride = 0);
+int64_t ols_wide_work(int T, int d);
+hipError_t launch_ols_wide_batched(int nb, const double *y, const double *w, int q, const double *F, int T, int kF,
+                                   int k, const int *Tn, double *coef, double *tstat, double *cov_out,
+                                   double *resid_out, int *status, double *work, hipStream_t st, int hc0 = 0);
+hipError_t launch_ols_wide(const double *y, const double *w, int q, const double *F, int T, int k, double *coef,
+                           double *tstat, double *cov_out, double *resid_out, int *status, double *work,
+                           hipStream_t st);
+hipError_t launch_targeted_joint_wide(const double *y, const double *w, int q, const double *X, int64_t ld, int T,
+                                      int N, double cv, double *tx, uint8_t *mask, int *status, double *work,
+                                      hipStream_t st);
+int64_t targeted_joint_wide_work(int T, int q, int N, int64_t ld);
+int64_t chow_wide_work(int T, int N, int r);
+hipError_t launch_chow_wide(int nb, const double *X, int64_t ld, int64_t sX, const double *E, int T, int N, int r,
+                            int bp, const double *F, int64_t sF, const double *L, int64_t sL, double *LR, double *LM,
+                            double *WD, int64_t ostr, double *scr, double *work, hipStream_t st, int nblk = 1,
+                            const int *brow = nullptr, int64_t lbs = 0);
+
+// ---- dfm_predict.hip
+hipError_t launch_predict(const double *Xp, int64_t ld, int T, int N, const double *L, int r, const double *x_dev,
+                          int64_t ldx, int64_t nn, const double *w_dev, int64_t ldw, int q, const double *beta_dev,
+                          double *work, double *F_out, double *yhat, hipStream_t st);
+
+}  // namespace dfm

@@ -1,7 +1,7 @@
 // dfm_model.hip — K3: the fused, HBM-bound kernels around the eigensolver:
 // factor/loading passes, common-component / factor-residual panels, the
 // OLS + HC2 regression of y on [w F_r], and the per-replicate statistics.
-#include "dfm_common.h"
+#include "dfm_internal.h"
 
 namespace dfm {
 
@@ -569,8 +569,6 @@ DFM_DEV double criterion_dev(int code, double V, int k, int T, int N, double sig
   }
   return NAN;
 }
-
-struct StatDesc { int kind, arg0, arg1, off; };
 
 // PCp's sigma^2 of each replicate's unrestricted fit (src/criteria.jl:18):
 // V(h) = sum_{j >= h} lambda_j / (N T), h = ceil(m/2), from its full spectrum

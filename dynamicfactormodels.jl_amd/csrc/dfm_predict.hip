@@ -14,7 +14,7 @@
 //
 //   F_new[i, j] = sum_n ((x_new[i, n] - mu) / sd) L[n, j] / |L_j|^2
 //   yhat[i]     = sum_k w_new[i, k] beta_k + sum_j F_new[i, j] beta_{q+j}
-#include "dfm_common.h"
+#include "dfm_internal.h"
 
 namespace dfm {
 

@@ -23,7 +23,7 @@
 //                       leader, the O(p |A|) full-pass replays and gradient
 //                       refreshes spread over the helpers)
 //   soft_loss_kernel    hold-out SSE per (fold, lambda)        (HBM-bound)
-#include "dfm_common.h"
+#include "dfm_internal.h"
 #include "../../include/dfm.h"
 #include <algorithm>
 #include <atomic>
@@ -37,11 +37,6 @@
 #include <vector>
 
 namespace dfm {
-hipError_t launch_gram(int orient, const PanelSrc &src, int m, int K, int T, double *G, int64_t ldg,
-                       int64_t strideG, int nrep, hipStream_t st);
-hipError_t launch_gram_plain_scaled(const double *X, int64_t ld, int m, int K, double *G, int64_t ldg, double alpha,
-                                    hipStream_t st);
-__global__ void panel_from_colmajor_kernel(const double *, int64_t, int, int, double *, int64_t);
 
 // y mean / population sd over each problem's training rows (fold != f; f = 0: all).
 __global__ void soft_ystats_kernel(const double *__restrict__ y, const int32_t *__restrict__ fold, int n,
@@ -181,7 +176,6 @@ constexpr int LP_PROF = 32;     // diagnostics slots per problem
 constexpr int LP_U = 32;        // helper change-list chunk (replay snapshots at every chunk boundary)
 constexpr int LP_NCH = LP_LMAX / LP_U + 2;   // chunk snapshots per column
 constexpr int LP_NBL = LP_LMAX / LP_B + 2;   // block snapshots of the leader's full sweep
-constexpr int LP_PF = (LP_B * LP_B + LP_NT - 64 - 1) / (LP_NT - 64);   // next-block loads per thread of waves 1..7
 enum { LP_FULL = 1, LP_REFRESH = 2, LP_EXIT = 3 };
 
 struct alignas(256) LpLine {   // one granule per 256-B line
@@ -1278,13 +1272,6 @@ __global__ __launch_bounds__(256) void soft_loss_kernel(const double *__restrict
 }  // namespace dfm
 
 using namespace dfm;
-
-// Context internals shared with dfm_api.hip (error text, stream, device).
-namespace dfm {
-int ctx_fail(dfm_ctx *ctx, int code, const char *msg);
-hipStream_t ctx_stream(dfm_ctx *ctx);
-int ctx_device(dfm_ctx *ctx);
-}  // namespace dfm
 
 // Process-wide record of the lasso launches (dfm_lasso_stats): every
 // timed-out spin is counted and reported, so a test can assert there were

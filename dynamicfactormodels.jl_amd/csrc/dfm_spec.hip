@@ -11,14 +11,10 @@
 // next symmetric product), then Sturm-count bisection on the tridiagonal,
 // one thread per eigenvalue.  Both are backward stable: eigenvalues to
 // O(eps ||G||), as LAPACK's dsyevr the reference reaches.
-#include "dfm_common.h"
+#include "dfm_internal.h"
 #include <algorithm>
 
 namespace dfm {
-
-hipError_t launch_spectrum_jacobi(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,
-                                  double *ev, hipStream_t st);
-int spectrum_max();
 
 constexpr int TRI_THREADS = 512;
 constexpr int TRI_WAVES = TRI_THREADS / 64;
@@ -357,10 +353,6 @@ hipError_t launch_spectrum(const double *G, int64_t ldg, int64_t strideG, int m,
 //  3. U = H_0 H_1 ... H_{m-3} Z.
 constexpr int SPEC_VEC_MAX = 4096;
 constexpr int OB = 32;   // orthonormalisation block
-
-hipError_t gemm_batched(int nb, int M, int Nc, int K, double alpha, const double *A, int64_t sAr, int64_t sAc,
-                        int64_t sAb, const double *B, int64_t sBr, int64_t sBc, int64_t sBb, double beta, double *C,
-                        int64_t sCr, int64_t sCc, int64_t sCb, hipStream_t st);
 
 // ||T||_inf, and the shifts: sigma_j = lambda_j, pushed down so consecutive
 // shifts differ by >= 10 eps ||T|| (dstein's perturbation of close shifts)

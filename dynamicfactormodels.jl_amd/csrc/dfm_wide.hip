@@ -8,7 +8,7 @@
 //   * factors / loadings of a block (src/DynamicFactorModel.jl:77-92);
 //   * OLS + HC2 on D = [w F_r] (:40-48) with inv(D'D) formed explicitly, as
 //     the reference's `inv` does.
-#include "dfm_common.h"
+#include "dfm_internal.h"
 #include <algorithm>
 
 namespace dfm {
@@ -73,15 +73,6 @@ hipError_t gemm_batched(int nb, int M, int Nc, int K, double alpha, const double
   hipLaunchKernelGGL(gemm_strided_kernel, dim3((Nc + 63) / 64, (M + 63) / 64, nb), dim3(256), 0, st, M, Nc, K, alpha,
                      A, sAr, sAc, B, sBr, sBc, beta, C, sCr, sCc, sAb, sBb, sCb);
   return hipGetLastError();
-}
-hipError_t gemm_strided(int M, int Nc, int K, double alpha, const double *A, int64_t sAr, int64_t sAc,
-                        const double *B, int64_t sBr, int64_t sBc, double beta, double *C, int64_t sCr,
-                        int64_t sCc, hipStream_t st) {
-  return gemm_batched(1, M, Nc, K, alpha, A, sAr, sAc, 0, B, sBr, sBc, 0, beta, C, sCr, sCc, 0, st);
-}
-static void gemm_s(int M, int Nc, int K, double alpha, const double *A, int64_t sAr, int64_t sAc, const double *B,
-                   int64_t sBr, int64_t sBc, double *C, int64_t sCr, int64_t sCc, hipStream_t st) {
-  gemm_strided(M, Nc, K, alpha, A, sAr, sAc, B, sBr, sBc, 0.0, C, sCr, sCc, st);
 }
 
 __global__ void scale_copy_kernel(const double *__restrict__ x, int64_t n, double s, double *__restrict__ y) {

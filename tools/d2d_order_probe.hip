@@ -1,6 +1,6 @@
 // Does hipMemcpyPeer (device-to-device, same device) return before the copy
 // has landed, and is a kernel on a hipStreamNonBlocking stream launched right
-// after it ordered behind it?  dfm_model_clone (dfm_api.hip) made the second
+// after it ordered behind it?  dfm_model_clone (dfm_fit.hip) made the second
 // bootstrap lane's copy of a fit with hipMemcpyPeer on the legacy null stream
 // and the lane then ran on its own non-blocking stream with no event between
 // them (VERDICT r04 Weak #1).  This probe copies a large buffer whose LAST
