@@ -522,11 +522,15 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
       // warm first filter's degree (eig_run_fact2_t)
       const double spread = (M->lam.size() >= (size_t)r && r > 0 && M->lam[r - 1] > 0.0) ? M->lam[0] / M->lam[r - 1]
                                                                                         : 0.0;
+      // ... and its lambda_r, in G*'s scale (both are eigenvalues of X X'), sets the interval end of a warm
+      // solve that starts with the filter: a number of the model alone, the same for every batch, lane and shard
+      // (fact implies nblk == 1, so M->lam[r - 1] is lambda_r of the one full-sample Gram, not a sum over break blocks)
+      const double lamk = spread >= 1.0 ? M->lam[r - 1] : 0.0;
       int rc = eig_run_factored(fb, idx + b0 * T, et, n, r, pf, M->Ub, r, etol,
                                 ctx->maxit, ctx->poll,
                                 w.eig, w.fact, w.lam, need_fl ? w.Uk : nullptr, w.trace, w.status, st, timer_cb,
                                 ctx, w.off, w.lst,
-                                (M->count_ctx ? M->count_ctx : ctx)->cnt_dev, esub, spread, ctx_poll(ctx));
+                                (M->count_ctx ? M->count_ctx : ctx)->cnt_dev, esub, spread, ctx_poll(ctx), lamk);
       if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
       note_iters(ctx);
       if (need_fl) {

@@ -817,17 +817,17 @@ DFM_DEV void eig_final_body(const double *Ur, const double *theta, int done, int
 }
 
 DFM_DEV void count_iters_body(const int *__restrict__ active, int last_gemm, int last_cheb, int nb, long long *cnt,
-                              int cp0, int cp1);
+                              int cp0, int cp1, int skip0);
 template <int P>
 __global__ __launch_bounds__(256) void eig_final_kernel(EigWork w, int m, int k, double *__restrict__ lam,
                                                         double *__restrict__ Uk, int *__restrict__ status,
                                                         double *__restrict__ trace_out, long long *cnt = nullptr,
                                                         int last_gemm = -1, int last_cheb = -1, int cp0 = 0,
-                                                        int cp1 = 0) {
+                                                        int cp1 = 0, int skip0 = 0) {
   const int rep = blockIdx.x;
   if (trace_out && threadIdx.x == 0) trace_out[rep] = w.trace[rep];   // (the caller's copy of trace(G))
   // the factored run's iteration / product counts (count_iters_kernel's work, one launch fewer)
-  if (cnt && rep == 0 && threadIdx.x == 0) count_iters_body(w.active, last_gemm, last_cheb, gridDim.x, cnt, cp0, cp1);
+  if (cnt && rep == 0 && threadIdx.x == 0) count_iters_body(w.active, last_gemm, last_cheb, gridDim.x, cnt, cp0, cp1, skip0);
   eig_final_body<P>(w.U + (int64_t)rep * m * P, w.small + (int64_t)rep * small_stride<P>() + 2 * P * P, w.done[rep],
                     rep, m, k, lam, Uk, status);
 }
@@ -903,19 +903,22 @@ thread_local int64_t g_last_gemm_products = 0;   // replicate-products of the la
 // replicate-iterations (GEMM launches 0..last_gemm, shift 1) and the GEMM
 // replicate-products (those plus the Chebyshev GEMMs 0..last_cheb, shift 0)
 // to cnt[0], cnt[1] — no host synchronisation after the eigen loop.
+// skip0: step 0 was a filter alone (a warm solve without a first
+// Rayleigh-Ritz step; active[0] = nb, q0_guards_kernel): its first product counts as a product
+// but not as a replicate-iteration.
 DFM_DEV void count_iters_body(const int *__restrict__ active, int last_gemm, int last_cheb, int nb, long long *cnt,
-                              int cp0, int cp1) {
+                              int cp0, int cp1, int skip0) {
   long long a = 0, b = 0;
   for (int it = 0; it <= last_gemm; ++it) a += it - 1 < 0 ? nb : active[it - 1];
   // Chebyshev products: cp0 after the first Rayleigh-Ritz step, cp1 after the others
   for (int it = 0; it <= last_cheb; ++it) b += (long long)active[it] * (it == 0 ? cp0 : cp1);
   // device-scope atomics: a model's two bootstrap lanes count into one context
-  atomicAdd(reinterpret_cast<unsigned long long *>(cnt), (unsigned long long)a);
+  atomicAdd(reinterpret_cast<unsigned long long *>(cnt), (unsigned long long)(a - (skip0 && last_gemm >= 0 ? nb : 0)));
   atomicAdd(reinterpret_cast<unsigned long long *>(cnt + 1), (unsigned long long)(a + b));
 }
 __global__ void count_iters_kernel(const int *__restrict__ active, int last_gemm, int last_cheb, int nb,
                                    long long *cnt, int cp0, int cp1) {
-  if (threadIdx.x == 0) count_iters_body(active, last_gemm, last_cheb, nb, cnt, cp0, cp1);
+  if (threadIdx.x == 0) count_iters_body(active, last_gemm, last_cheb, nb, cnt, cp0, cp1, 0);
 }
 static int64_t count_rep_iters(const int *active_dev, int last, int shift, int nb, hipStream_t st) {
   if (last < 0) return 0;
@@ -1532,7 +1535,8 @@ template <int P, bool STG>
 DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid, int wave, int lane,
                            const double *set, const int *so, const int *sl, const double *Qn,
                            double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab,
-                           const dv4 *aacc, double *sred, int ps, double *zst, const double *apre = nullptr);
+                           const dv4 *aacc, double *sred, int ps, double *zst, const double *apre = nullptr,
+                           double *__restrict__ pvr = nullptr);
 // a = F'Q0 of the first product for the whole batch: F and the warm start Q0
 // are shared by every replicate, so boot_prep_kernel's per-workgroup tile
 // loop and fixed-order wave sums are run ONCE, in the same order (one
@@ -1589,7 +1593,8 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
                                                         double *__restrict__ PF, double *__restrict__ E2,
                                                         const double *__restrict__ Q0, int ps,
                                                         double *__restrict__ Zc, int64_t ldz, int pz,
-                                                        double *__restrict__ ab, const double *__restrict__ apre) {
+                                                        double *__restrict__ ab, const double *__restrict__ apre,
+                                                        double *__restrict__ PV, double *__restrict__ FV) {
   static_assert(BW * 64 == 256, "prep runs the factored passes' wave layout");
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
@@ -1716,8 +1721,12 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
       for (int e = tid; e < npad * pz; e += 256) Zc[zrm_ix(rep, T + e / pz, e % pz, pz, zrs)] = 0.0;
     }
     __syncthreads();   // so / set visible
+    // (PV, FV: a warm solve without a first Rayleigh-Ritz step filters V0 = Q0 itself, so the middle Horner
+    // steps' PV = P'D V0 is Z0 row by row and FV = F'V0 is a)
     zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, aacc, sred, ps, zst[wave],
-                           apre);
+                           apre, PV ? PV + (int64_t)rep * T * P : nullptr);
+    if (FV && apre)
+      for (int e = tid; e < 16 * P; e += 256) FV[(int64_t)rep * 16 * P + e] = apre[e];
   }
   double acc = 0.0;
   for (int t = tid; t < T; t += 256) {
@@ -2176,7 +2185,8 @@ template <int P, bool STG>
 DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid, int wave, int lane,
                            const double *set, const int *so, const int *sl, const double *Qn,
                            double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab,
-                           const dv4 *aacc, double *sred, int ps, double *zst, const double *apre) {
+                           const dv4 *aacc, double *sred, int ps, double *zst, const double *apre,
+                           double *__restrict__ pvr) {
   const int64_t zrs = zrm_stride(T, pz);
   constexpr int NT = P / 16;
   const int li = lane & 15, lk = lane >> 4;
@@ -2226,6 +2236,16 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct)
           z[g][ct] = fma(e, 16 * ct + li < ps ? Qn[(int64_t)t * ps + 16 * ct + li] : 0.0, z[g][ct]);
+      }
+    }
+    if (pvr) {   // the same rows as PV = P'D Qn in boot_cheb_mid_kernel's layout (compact rows, ps columns)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int s = s0 + 4 * g + lk;
+        if (s < T)
+#pragma unroll
+          for (int ct = 0; ct < NT; ++ct)
+            if (16 * ct + li < ps) pvr[(int64_t)s * ps + 16 * ct + li] = z[g][ct];
       }
     }
     if constexpr (STG) {
@@ -2496,7 +2516,13 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_kernel(FactBase fb, EigW
                                                         const double *__restrict__ HZ, int64_t ldz, int pz,
                                                         double *__restrict__ ab, double fai, double bbeta, int k,
                                                         double *__restrict__ Qo,
-                                                        double *__restrict__ Zc, int ps) {
+                                                        double *__restrict__ Zc, int ps,
+                                                        const double *__restrict__ V0, int64_t v0s, double bfix) {
+  // V0, v0s: the filtered block and its replicate stride (w.U, T P after a
+  // Rayleigh-Ritz step; the shared warm start Q0, 0, for a filter-only first
+  // step).  bfix > 0: the interval end, the same for every replicate, instead
+  // of filter_end — no Rayleigh-Ritz step has run, so the small record is
+  // not read and no column is deflated.
   constexpr int NT = P / 16;
   const int rep = blockIdx.x;
   if (w.done[rep]) return;
@@ -2529,12 +2555,12 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_kernel(FactBase fb, EigW
   }
   __syncthreads();
   const double *small = w.small + (int64_t)rep * small_stride<P>();
-  const double b = filter_end<P>(small, k, p, bbeta);
+  const double b = bfix > 0.0 ? bfix : filter_end<P>(small, k, p, bbeta);
   // b <= 0 (a degenerate block): plain power steps
   const double cb = b > 0.0 ? 1.0 / b : 1.0, cv0 = b > 0.0 ? fai : 0.0;
   bool dd[NT];
 #pragma unroll
-  for (int ct = 0; ct < NT; ++ct) dd[ct] = small[2 * P * P + P + 16 * ct + li] != 0.0;
+  for (int ct = 0; ct < NT; ++ct) dd[ct] = bfix > 0.0 ? false : small[2 * P * P + P + 16 * ct + li] != 0.0;
   const int KR = (r + 3) >> 2;
   double bA[4][NT], bB[4][NT];
 #pragma unroll
@@ -2544,7 +2570,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_kernel(FactBase fb, EigW
       bA[kk][ct] = sa[(4 * kk + lk) * P + 16 * ct + li];
       bB[kk][ct] = sb[(4 * kk + lk) * P + 16 * ct + li];
     }
-  const double *Xr = w.U + (int64_t)rep * T * P;   // V0 = Q Bm (ap2)
+  const double *Xr = V0 + (int64_t)rep * v0s;   // V0 = Q Bm (ap2), or the warm start
   double *Qr = Qo + (int64_t)rep * T * P;
   dv4 aacc[NT];
 #pragma unroll
@@ -2746,7 +2772,12 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
                                                             const double *__restrict__ PV,
                                                             const double *__restrict__ FV,
                                                             const double *__restrict__ FtF,
-                                                            double *__restrict__ Zc, int ps) {
+                                                            double *__restrict__ Zc, int ps, double bfix,
+                                                            double lead) {
+  // bfix > 0: the interval end of a filter-only first step (boot_cheb_kernel);
+  // lead: the scale of the incoming S_{i+1} not yet applied to its Z, a, cc —
+  // the filter's leading coefficient a_d at the first step of such a filter
+  // (S_d = a_d V0 is never formed: prep left the Z, a, cc of V0), else 1
   constexpr int NT = P / 16;
   const int rep = blockIdx.x;
   if (w.done[rep]) return;
@@ -2760,7 +2791,10 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   // shaped gathers of the same rows, and the tile's Z chunk (16 rows x pz,
   // contiguous in the replicate-major layout) leaves as whole 16-B pieces
   // instead of one 128-B-strided element per lane
-  __shared__ double stg[BW][2][16 * 17];
+  // stage 0 holds the PF rows (16 x (r | 1) <= 16 x 17) and then the Z chunk (16 x pz <= 16 x P)
+  constexpr int MID_STG = 16 * (P > 17 ? P : 17);
+  static_assert(MID_STG >= 16 * P && MID_STG >= 16 * 17, "the stage holds a Z chunk of pz <= P columns and 16 PF rows");
+  __shared__ double stgP[BW][MID_STG], stgE[BW][16 * 17];
   double *abr = ab + (int64_t)rep * 32 * P;
   for (int e = tid; e < 16 * P; e += 64 * BW) sa[e] = abr[e];
   __syncthreads();
@@ -2773,11 +2807,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   }
   __syncthreads();
   const double *small = w.small + (int64_t)rep * small_stride<P>();
-  const double b = filter_end<P>(small, k, p, bbeta);
-  const double cb = b > 0.0 ? 1.0 / b : 1.0, cv0 = b > 0.0 ? fai : 0.0;
+  const double b = bfix > 0.0 ? bfix : filter_end<P>(small, k, p, bbeta);
+  const double cb = b > 0.0 ? lead / b : 1.0, cv0 = b > 0.0 ? fai : 0.0;
   bool dd[NT];
 #pragma unroll
-  for (int ct = 0; ct < NT; ++ct) dd[ct] = small[2 * P * P + P + 16 * ct + li] != 0.0;
+  for (int ct = 0; ct < NT; ++ct) dd[ct] = bfix > 0.0 ? false : small[2 * P * P + P + 16 * ct + li] != 0.0;
   const int KR = (r + 3) >> 2;
   const double *pfr = PF + (int64_t)rep * T * r, *e2r = E2 + (int64_t)rep * T, *pvr = PV + (int64_t)rep * T * P;
   dv4 aacc[NT], cacc[NT];
@@ -2785,7 +2819,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   for (int ct = 0; ct < NT; ++ct) { aacc[ct] = dv4{0.0, 0.0, 0.0, 0.0}; cacc[ct] = aacc[ct]; }
   const int ntile = (T + 15) >> 4;
   const int RS = r | 1;   // staged row stride (odd: the 16-row reads spread over the banks)
-  double *sP = stg[wave][0], *sE = stg[wave][1];
+  double *sP = stgP[wave], *sE = stgE[wave];
   const int64_t zrs = zrm_stride(T, pz);
   for (int tile = wave; tile < ntile; tile += BW) {
     const int t0 = tile * 16;
@@ -2911,7 +2945,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
     const int ct = c >> 4, l = ((j & 3) << 4) | (c & 15), g = j >> 2;
     double a = 0.0;
     if (j < r && c < p) {
-      if (small[2 * P * P + P + c] != 0.0) a = fvr[e];
+      if (!(bfix > 0.0) && small[2 * P * P + P + c] != 0.0) a = fvr[e];
       else {
         double f = 0.0;
         for (int i = 0; i < r; ++i) f = fma(FtF[j * 16 + i], sb[i * P + c], f);
@@ -3007,6 +3041,121 @@ static double warm_beta() {
   static const double v = [] { const char *e = getenv("DFM_FACT_BETA"); return e ? atof(e) : kChebWarmBeta; }();
   return v;
 }
+// A warm start whose first filter has middle steps (degree >= 3) skips the
+// first Rayleigh-Ritz step: the filter is a polynomial in G*, so
+// span(p(G*) Q0 Bm) = span(p(G*) Q0) for any invertible Bm and the next
+// Rayleigh-Ritz step, which reads only the span, loses nothing; the interval
+// end is kWarmFixBeta lambda_k of the BASE fit, one number for the whole
+// job (model-only: the same in every batch, lane and shard).  The guards'
+// branch of filter_end (theta_p) is not taken over: it needs a product, an
+// end short of lambda_{p+1} only slows the filter, and in the CPU model it
+// never binds (theta_p / theta_k of a step on the start block <= 0.022 at
+// C3, <= 0.095 at T = 120, N = 300, against the 0.2 it must exceed).  Gone per solve: step
+// 0's y2, eig_small, pv and ap2; one more middle Horner step instead.  The
+// guard columns are orthonormalised once against the warm vectors
+// (q0_guards_kernel): with raw random guards the filtered block's condition
+// number is ~4e7 (CPU model, tools/eig_proto.py) and the Cholesky of its Gram
+// matrix fails.  The first Rayleigh-Ritz step diagonalises a projected
+// matrix that no earlier step has pre-rotated; its kJacobiSweeps = 2 sweeps
+// still suffice (CPU model: the same retirement as with 4; measured, a cap
+// of 4 there: 47 replicate-steps in 205 k fewer, eig_small +0.05 ms per C3
+// step, profiles/r07_c3_ab.txt).
+// That step runs as loop step 1 (itc = 2 in ap2): decide_converged's
+// previous-residual record needs no initialisation for it — the stagnation
+// test that reads the record is guarded by itc > 2, and loop step 2 reads the
+// slot ((itc - 1) & 1) that loop step 1 wrote, as any later pair of steps.
+// DFM_FACT_STEP0=1 (A/B only) restores the first Rayleigh-Ritz step.
+constexpr double kWarmFixBeta = 0.21;
+static bool warm_keep_step0() {   // (read at every solve: one process can run both schedules)
+  const char *e = getenv("DFM_FACT_STEP0");
+  return e && atoi(e) != 0;
+}
+
+// Guard columns kw..p-1 of the shared warm start Q0 (m rows of ps columns),
+// orthonormalised against the warm columns 0..kw-1 (one projection; the warm
+// columns, left bit-for-bit as they are, are orthogonal eigenvectors) and
+// against each other (Cholesky of their Gram matrix, a forward substitution
+// per row).  One workgroup; every sum runs over fixed row groups in a fixed
+// order, so Q0 is the same in every batch, lane and shard.
+// The kernel also opens the filter-only step's record: active[0] = nb, what
+// a first Rayleigh-Ritz step that retires no replicate would have counted
+// (every replicate runs step 0; count_iters_body prices its products from it).
+constexpr int Q0G_PMAX = 32;                        // the widest block (eig_run_factored: p <= 32)
+constexpr int Q0G_SUMS = Q0G_PMAX * Q0G_PMAX;       // sums per phase: (ng + 1) kw <= 272 (ng + kw <= 32), ng^2 <= 1024
+__global__ __launch_bounds__(1024) void q0_guards_kernel(double *__restrict__ Q0, int m, int ps, int kw, int p,
+                                                         int *__restrict__ active, int nb) {
+  static_assert(Q0G_SUMS <= 1024, "one thread per sum, one partial per thread");
+  __shared__ double part[1024];
+  __shared__ double dots[Q0G_SUMS];   // the cross / norm sums, then the guards' ng x ng Gram matrix
+  __shared__ double Lc[Q0G_PMAX * Q0G_PMAX];
+  const int tid = threadIdx.x, ng = p - kw;
+  if (tid == 0) active[0] = nb;
+  if (ng <= 0 || kw < 0 || p > Q0G_PMAX) return;
+  for (int phase = 0; phase < 2; ++phase) {
+    // phase 0: pair e = j kw + i -> <g_j, w_i> (j < ng), j = ng -> <w_i, w_i>;  phase 1: e = j ng + i -> <g_j, g_i>
+    const int np = phase == 0 ? (ng + 1) * kw : ng * ng;
+    int npp = 1;
+    while (npp < np) npp <<= 1;
+    const int rg = 1024 / npp;   // row groups (np <= Q0G_SUMS: npp <= 1024, rg >= 1)
+    const int e = tid % npp, g = tid / npp;
+    double acc = 0.0;
+    if (e < np && g < rg) {
+      int ca, cb;
+      if (phase == 0) { const int j = e / kw, i = e % kw; ca = j < ng ? kw + j : i; cb = i; }
+      else { ca = kw + e / ng; cb = kw + e % ng; }
+      for (int t = g; t < m; t += rg) acc = fma(Q0[(int64_t)t * ps + ca], Q0[(int64_t)t * ps + cb], acc);
+    }
+    part[tid] = acc;
+    __syncthreads();
+    if (tid < np) {
+      double s = 0.0;
+      for (int q = 0; q < rg; ++q) s += part[q * npp + tid];
+      dots[tid] = s;
+    }
+    __syncthreads();
+    if (phase == 0) {
+      if (kw > 0)
+        for (int x = tid; x < m * ng; x += 1024) {
+          const int t = x / ng, j = x % ng;
+          double v = Q0[(int64_t)t * ps + kw + j];
+          for (int i = 0; i < kw; ++i) {
+            const double n = dots[ng * kw + i];
+            if (n > 0.0) v = fma(-(dots[j * kw + i] / n), Q0[(int64_t)t * ps + i], v);
+          }
+          Q0[(int64_t)t * ps + kw + j] = v;
+        }
+    } else {
+      if (tid == 0) {   // Gram = L L' (a column whose pivot is not positive stays as it is)
+        for (int j = 0; j < ng; ++j) {
+          for (int i = 0; i <= j; ++i) {
+            double s = dots[j * ng + i];
+            for (int q = 0; q < i; ++q) s -= Lc[j * 32 + q] * Lc[i * 32 + q];
+            if (i < j) Lc[j * 32 + i] = Lc[i * 32 + i] > 0.0 ? s / Lc[i * 32 + i] : 0.0;
+            else Lc[j * 32 + j] = s > 0.0 ? sqrt(s) : -1.0;
+          }
+          if (!(Lc[j * 32 + j] > 0.0))
+            for (int i = 0; i < j; ++i) Lc[j * 32 + i] = 0.0;
+        }
+      }
+      __syncthreads();
+      for (int t = tid; t < m; t += 1024) {   // row t: g L^-T by forward substitution
+        double nv[32];
+        for (int j = 0; j < ng; ++j) {
+          double v = Q0[(int64_t)t * ps + kw + j];
+          const double d = Lc[j * 32 + j];
+          if (d > 0.0) {
+            for (int i = 0; i < j; ++i) v -= Lc[j * 32 + i] * nv[i];
+            v /= d;
+          }
+          nv[j] = v;
+          Q0[(int64_t)t * ps + kw + j] = v;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 static int first_filter_degree(double spread) {
   const double ratio = std::max(1.0001, 1.1 * spread);
   const int d = (int)std::floor(std::log(1e6) / std::log(ratio));
@@ -3018,7 +3167,7 @@ static int eig_run_fact2_t(const FactBase &fb, const int32_t *idx, const double 
                            const double *warm, int kw, double tol, int maxit, int poll, char *ws,
                            char *fws, double *lam, double *Uk, double *trace_out, int *status,
                            hipStream_t st, timer_fn tf, void *tctx, int *off, int *lst, long long *cnt,
-                           int subspace, double spread, const PollBuf *pb) {
+                           int subspace, double spread, const PollBuf *pb, double lamk) {
   const int m = fb.T;
   EigWork w = carve(ws, m, nb, P, maxit);
   w.subspace = subspace;
@@ -3078,11 +3227,15 @@ static int eig_run_fact2_t(const FactBase &fb, const int32_t *idx, const double 
   const int d0 = warm_started ? first_filter_degree(spread) : kChebD;
   // a first filter of degree >= 3 has middle Horner steps (boot_cheb_mid_kernel)
   const bool mid = d0 >= 3;
+  // ... and, from a warm start, no Rayleigh-Ritz step in front of it (warm_keep_step0)
+  const double bfix = kWarmFixBeta * lamk;
+  const bool skip0 = warm_started && mid && maxit >= 2 && bfix > 0.0 && p <= Q0G_PMAX && !warm_keep_step0();
   if (tf) tf(tctx, DFM_KC_EIG_OTHER, 1);
   {
     const int64_t n = (int64_t)m * P;
     dim3 grid((unsigned)((n + 255) / 256), 1);
     hipLaunchKernelGGL(eig_init_kernel<P>, grid, dim3(256), 0, st, Q0, m, p, warm, kw, w.done, seed, (int64_t)0, ps);
+    if (skip0) hipLaunchKernelGGL(q0_guards_kernel, dim3(1), dim3(1024), 0, st, Q0, m, ps, kw, p, w.active, nb);
     // the CSR, trace, PF / e2 and the first product's Z0 and ab (the init
     // pass boot_ap2_kernel<init = 1> ran separately before round 6)
     const size_t prep_lds = (size_t)((4 * m + 3) & ~1) * 4 + (size_t)m * 8;
@@ -3090,7 +3243,8 @@ static int eig_run_fact2_t(const FactBase &fb, const int32_t *idx, const double 
       hipFuncSetAttribute((const void *)boot_prep_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
     hipLaunchKernelGGL(prep_a_kernel<P>, dim3(1), dim3(256), 0, st, fb, Q0, ps, apre);
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(256), prep_lds, st,
-                       fb, idx, eta, off, lst, w.trace, mid ? PFb : nullptr, E2b, Q0, ps, Zc, ldz, pz, ab, apre);
+                       fb, idx, eta, off, lst, w.trace, mid ? PFb : nullptr, E2b, Q0, ps, Zc, ldz, pz, ab, apre,
+                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr);
   }
   if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
   const double *ftf = fb.FtF ? fb.FtF : FtF;
@@ -3133,6 +3287,30 @@ static int eig_run_fact2_t(const FactBase &fb, const int32_t *idx, const double 
     const int dg = it == 0 ? d0 : kChebD;
     const double *ca = it == 0 ? ca0 : ca1;
     const double bb = it == 0 ? beta0 : 0.0;
+    if (skip0 && it == 0) {
+      // step 0 is the filter alone: S_d = a_d Q0 (prep left the Z, a, cc, PV, FV
+      // of Q0; a_d goes into the first step's scale), d0 products, the last
+      // step writes the new basis into cur with its Z, a, cc
+      for (int sp = 1; sp <= d0; ++sp) {
+        if (tf) tf(tctx, DFM_KC_GEMM, 1);
+        hipError_t e = launch_gemm_zrm(fb.H, fb.ldH, Zc, pz, zrs, HZ, ldz, m, ncz, m, st, w.done, nullptr, nullptr);
+        if (tf) tf(tctx, DFM_KC_GEMM, 0);
+        if (e != hipSuccess) return 1000 + (int)e;
+        if (tf) tf(tctx, DFM_KC_EIG_APPLY, 1);
+        if (sp < d0)
+          hipLaunchKernelGGL(cmk, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz, pz, ab, ca0[d0 - sp], 0.0, k,
+                             PFb, E2b, w.S, FVb, ftf, Zc, ps, bfix, sp == 1 ? ca0[d0] : 1.0);
+        else
+          hipLaunchKernelGGL(chk, dim3(nb), dim3(64 * BW), (size_t)m * 8 + (size_t)(3 * m + 1) * 4, st, fb, w, m, p,
+                             idx, eta, off, lst, HZ, ldz, pz, ab, ca0[0], 0.0, k, cur, Zc, ps, (const double *)Q0,
+                             (int64_t)0, bfix);
+        if (tf) tf(tctx, DFM_KC_EIG_APPLY, 0);
+      }
+      last_gemm = last_cheb = 0;
+      qin = cur;
+      qs = (int64_t)m * P;
+      continue;
+    }
     if (tf) tf(tctx, DFM_KC_GEMM, 1);
     hipError_t e = launch_gemm_zrm(fb.H, fb.ldH, Zc, pz, zrs, HZ, ldz, m, ncz, m, st, w.done,
                                    cl_on ? alist : nullptr, cl_on ? acount : nullptr);
@@ -3197,10 +3375,11 @@ static int eig_run_fact2_t(const FactBase &fb, const int32_t *idx, const double 
         if (tf) tf(tctx, DFM_KC_EIG_APPLY, 1);
         if (mid && it == 0 && sp < dg)
           hipLaunchKernelGGL(cmk, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz, pz, ab,
-                             ca[dg - sp], bb, k, PFb, E2b, w.S, FVb, ftf, Zc, ps);
+                             ca[dg - sp], bb, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, 0.0, 1.0);
         else
           hipLaunchKernelGGL(chk, dim3(nb), dim3(64 * BW), (size_t)m * 8 + (size_t)(3 * m + 1) * 4,
-                             st, fb, w, m, p, idx, eta, off, lst, HZ, ldz, pz, ab, ca[dg - sp], bb, k, cur, Zc, ps);
+                             st, fb, w, m, p, idx, eta, off, lst, HZ, ldz, pz, ab, ca[dg - sp], bb, k, cur, Zc, ps,
+                             (const double *)w.U, (int64_t)m * P, 0.0);
         if (tf) tf(tctx, DFM_KC_EIG_APPLY, 0);
       }
       last_cheb = it;
@@ -3220,10 +3399,11 @@ static int eig_run_fact2_t(const FactBase &fb, const int32_t *idx, const double 
     const int64_t c0 = count_rep_iters(w.active, std::min(last_cheb, 0), 0, nb, st);
     const int64_t call = count_rep_iters(w.active, last_cheb, 0, nb, st);
     g_last_gemm_products = g_last_rep_iters + c0 * (d0 - 1) + (call - c0) * (kChebD - 1);
+    if (skip0 && last_gemm >= 0) g_last_rep_iters -= nb;   // (step 0's first product belongs to no Rayleigh-Ritz step)
   }
   if (tf) tf(tctx, DFM_KC_EIG_OTHER, 1);
   hipLaunchKernelGGL(eig_final_kernel<P>, dim3(nb), dim3(256), 0, st, w, m, k, lam, Uk, status, trace_out, cnt,
-                     last_gemm, last_cheb, d0 - 1, kChebD - 1);
+                     last_gemm, last_cheb, d0 - 1, kChebD - 1, skip0 ? 1 : 0);
   if (tf) tf(tctx, DFM_KC_EIG_OTHER, 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return 1000 + (int)e;
@@ -3234,14 +3414,14 @@ int eig_run_factored(const FactBase &fb, const int32_t *idx, const double *eta, 
                      const double *warm, int kw, double tol, int maxit, int poll, char *ws, char *fws,
                      double *lam, double *Uk, double *trace_out, int *status, hipStream_t st,
                      timer_fn tf, void *tctx, int *off, int *lst, long long *cnt, int subspace, double spread,
-                     const PollBuf *pb) {
+                     const PollBuf *pb, double lamk) {
   if (p < k || p > 32 || p > fb.T || fb.r > 32) return -1;
   if (fb.r > 16 || fb.T > F2_T_MAX) return -1;   // callers take the direct path
   if (p <= 16)
     return eig_run_fact2_t<16>(fb, idx, eta, nb, k, p, warm, kw, tol, maxit, poll, ws, fws, lam, Uk,
-                               trace_out, status, st, tf, tctx, off, lst, cnt, subspace, spread, pb);
+                               trace_out, status, st, tf, tctx, off, lst, cnt, subspace, spread, pb, lamk);
   return eig_run_fact2_t<32>(fb, idx, eta, nb, k, p, warm, kw, tol, maxit, poll, ws, fws, lam, Uk,
-                             trace_out, status, st, tf, tctx, off, lst, cnt, subspace, spread, pb);
+                             trace_out, status, st, tf, tctx, off, lst, cnt, subspace, spread, pb, lamk);
 }
 int fact_t_max() { return F2_T_MAX; }
 

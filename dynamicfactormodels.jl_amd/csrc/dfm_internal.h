@@ -72,7 +72,7 @@ int eig_run_factored(const FactBase &fb, const int32_t *idx, const double *eta, 
                      const double *warm, int kw, double tol, int maxit, int poll, char *ws, char *fws,
                      double *lam, double *Uk, double *trace_out, int *status, hipStream_t st,
                      timer_fn tf, void *tctx, int *off, int *lst, long long *cnt = nullptr, int subspace = 0,
-                     double spread = 0.0, const PollBuf *pb = nullptr);
+                     double spread = 0.0, const PollBuf *pb = nullptr, double lamk = 0.0);
 int fact_t_max();
 int fact_loadings(const FactBase &fb, const double *Ep, int64_t ld, int N, const double *Lb,
                   const double *Uk, const double *eta, const int *off, const int *lst, int nb,

@@ -2,9 +2,24 @@
 shape, to explore warm starts and filter schedules before touching kernels:
 block p = 16, Rayleigh-Ritz with CholQR, Chebyshev filter on [0, theta_p],
 the eigenvalue (Kato-Temple) stopping rule of decide_converged (1e-12).
-Reports Rayleigh-Ritz steps and G-products per replicate.
+Reports loop steps and G-products per replicate, the worst relative error of
+the retired eigenvalues against LAPACK and the worst column-normalised
+condition number of the block the step after the first filter orthonormalises
+(r / w schedules also: the largest theta_p / theta_k of the first step, the
+level at which filter_end's guard branch would bind).
   python tools/eig_proto.py [nrep] [schedule ...]   schedule e.g. "r8:2,2" "w16:2,2" "w16:3,2"
-"""
+Schedules: <start><kw>[@beta]:<deg0>,<deg1>
+  r / w  warm start of kw base eigenvectors + raw random guards, a
+         Rayleigh-Ritz step first; @beta: first interval end max(theta_p, beta theta_k)
+  f      the same start with the guards orthonormalised against the warm
+         vectors and each other, and NO first Rayleigh-Ritz step: step 0 is the
+         degree-deg0 filter alone on [0, beta lambda_k(base fit)] (a constant
+         of the model); g: the same with raw guards
+Environment: P (block), SHAPE=c1|c2|small (small: T = 120, N = 300, R = 8),
+R, TOL, STRICT=1, JACOBI=n (model eig_small's n threshold-Jacobi sweeps per
+Rayleigh-Ritz step instead of LAPACK's eigh; JACOBI_FIRST: the sweeps of the
+f / g schedules' first Rayleigh-Ritz step, which no earlier step has
+pre-rotated)."""
 import os
 import sys
 
@@ -16,6 +31,8 @@ import host  # noqa: E402
 
 T, N, R = 500, 2000, 8
 P = int(os.environ.get("P", "16"))
+JACOBI = int(os.environ.get("JACOBI", "0"))
+JACOBI_FIRST = int(os.environ.get("JACOBI_FIRST", str(JACOBI)))   # f / g: sweeps of the first Rayleigh-Ritz step
 
 
 def shifted_cheb(d):
@@ -31,20 +48,80 @@ def shifted_cheb(d):
     return t1
 
 
-def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False):
+def jacobi(H, sweeps):
+    """eig_small's parallel cyclic Jacobi: circle-method rounds of disjoint
+    pairs, a pair rotated only while |h_ab| > 4 eps sqrt(|h_aa h_bb|), the
+    sweep loop ending at the first sweep that rotates nothing.  Returns the
+    diagonal (NOT sorted) and the accumulated rotations."""
+    p = H.shape[0]
+    n = p + (p & 1)
+    H = H.copy()
+    V = np.eye(p)
+    order = list(range(n))
+    for _ in range(sweeps):
+        rotated = False
+        for _ in range(n - 1):
+            J = np.eye(p)
+            for i in range(n // 2):
+                a, b = sorted((order[i], order[n - 1 - i]))
+                if b >= p:
+                    continue
+                hab, haa, hbb = H[a, b], H[a, a], H[b, b]
+                if abs(hab) > 1e-300 and hab * hab > 7.921e-31 * abs(haa * hbb):
+                    zeta = (hbb - haa) / (2.0 * hab)
+                    t = (1.0 if zeta >= 0 else -1.0) / (abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+                    c = 1.0 / np.sqrt(1.0 + t * t)
+                    s = t * c
+                    J[a, a] = J[b, b] = c
+                    J[a, b], J[b, a] = s, -s
+                    rotated = True
+            H = J.T @ H @ J
+            V = V @ J
+            order = [order[0], order[-1]] + order[1:-1]
+        if not rotated:
+            break
+    return np.diag(H).copy(), V
+
+
+def colcond(Q):
+    return np.linalg.cond(Q / np.linalg.norm(Q, axis=0))
+
+
+def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False, bfix=0.0):
+    """-> (loop steps, products, Rayleigh-Ritz steps, theta[:k] at retirement, cond after the first filter,
+    theta_p / theta_k of a Rayleigh-Ritz step on the start block: filter_end's guard branch binds when it exceeds beta)"""
     Q = Q0.copy()
     tr = np.trace(G)
     prods = 0
-    for it in range(maxit):
+    it0 = 0
+    cond = 0.0
+    gratio = 0.0
+    if bfix > 0.0:   # step 0: the filter alone, S_d = a_d Q0, S_i = G S_{i+1} / b + a_i Q0
+        a = shifted_cheb(degs[0])
+        S = a[degs[0]] * Q0
+        for i in range(degs[0] - 1, -1, -1):
+            S = G @ S / bfix + a[i] * Q0
+            prods += 1
+        Q = S
+        it0 = 1
+    th = np.zeros(P)
+    for it in range(it0, maxit):
+        if it == 1:
+            cond = colcond(Q)
         Y = G @ Q
         prods += 1
         L = np.linalg.cholesky(Q.T @ Q)
         Li = np.linalg.inv(L)
         Hm = Li @ (Q.T @ Y) @ Li.T
         Hm = 0.5 * (Hm + Hm.T)
-        th, V = np.linalg.eigh(Hm)
-        o = np.argsort(-th)
+        if JACOBI:
+            th, V = jacobi(Hm, JACOBI_FIRST if it0 and it == 1 else JACOBI)
+        else:
+            th, V = np.linalg.eigh(Hm)
+        o = np.argsort(-th, kind="stable")
         th, V = th[o], V[:, o]
+        if it == 0:
+            gratio = th[P - 1] / th[k - 1]
         A = Li.T @ V
         U = Q @ A
         Res = Y @ A - U * th
@@ -55,13 +132,13 @@ def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False):
         if strict:   # subspace rule: res_j <= tol |theta_j - theta_k|
             res = np.sqrt(res2[:k])
             if np.all((res <= tol * np.abs(th[:k] - th[k])) | (res <= 2e-14 * th[0])):
-                return it + 1, prods
+                return it + 1, prods, it + 1 - it0, th[:k], cond, gratio
         else:
             bnd = res2[:k] / (0.5 * gap[:k])
             ok = np.all((bnd <= tol * np.abs(th[:k])) | (np.sqrt(res2[:k]) <= 2e-14 * th[0]))
             vnum = max(abs(tr - th[:k].sum()), 1e-6 * abs(tr))
             if ok and bnd.sum() <= tol * vnum:
-                return it + 1, prods
+                return it + 1, prods, it + 1 - it0, th[:k], cond, gratio
         ZZ = A.T @ (Y.T @ Y) @ A
         L2 = np.linalg.cholesky(0.5 * (ZZ + ZZ.T))
         Bm = A @ np.linalg.inv(L2).T
@@ -79,7 +156,7 @@ def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False):
             prods += 1
             X = X + (a[s] / b ** s) * Kn
         Q = X
-    return maxit, prods
+    return maxit, prods, maxit - it0, th[:k], cond, gratio
 
 
 def main():
@@ -99,6 +176,11 @@ def main():
         rng = np.random.default_rng(20261015 + 2)
         y, x, *_ = host.factor_model_DGP(T, N, 3, model="Breitung_Eickmeier_2011", b=0.5, rng=rng)
         R = int(os.environ.get("R", "4"))
+    elif os.environ.get("SHAPE") == "small":   # the GPU tests' small shape
+        T, N = 120, 300
+        R = int(os.environ.get("R", "8"))
+        rng = np.random.default_rng(8180)
+        y, x, *_ = host.factor_model_DGP(T, N, R, rng=rng)
     else:
         rng = np.random.default_rng(20261015 + 3)
         y, x, *_ = host.factor_model_DGP(T, N, R, rng=rng)
@@ -108,7 +190,7 @@ def main():
         T, N = N, T
     G0 = x @ x.T
     lam, Uall = np.linalg.eigh(G0)
-    Uall = Uall[:, ::-1]
+    lam, Uall = lam[::-1], Uall[:, ::-1]
     F = np.sqrt(T) * Uall[:, :R]
     Lb = x.T @ F / T
     C = F @ Lb.T
@@ -117,13 +199,15 @@ def main():
     idx, eta = host.draw_wild_fast(1_000_003, nrep, Tr)
     hrng = np.random.default_rng(5)
     rnd = hrng.uniform(-1, 1, size=(T, P))
-    Gs = []
-    for b in range(nrep):
+
+    def gram(b):
         if c2:   # rows of the T x N panel are columns here
             Xs = C + eta[b][None, :] * E[:, idx[b]]
         else:
             Xs = C + eta[b][:, None] * E[idx[b]]
-        Gs.append(Xs @ Xs.T)
+        return Xs @ Xs.T
+
+    truth = {}
     for sc in scheds:
         start, degs = sc.split(":")
         degs = [int(v) for v in degs.split(",")]
@@ -131,18 +215,39 @@ def main():
         if "@" in start:
             start, beta = start.split("@")
             beta = float(beta)
-        kw = int(start[1:])
-        Q0 = np.hstack([Uall[:, :min(kw, P)], rnd[:, min(kw, P):]]) if start[0] in "rw" else None
-        res = []
-        for G in Gs:
+        kw = min(int(start[1:]), P)
+        Q0 = np.hstack([Uall[:, :kw], rnd[:, kw:]])
+        bfix = 0.0
+        if start[0] in "fg":
+            bfix, beta = beta * lam[R - 1], 0.0
+        if start[0] == "f":   # guards: one projection off the warm vectors, CholQR among themselves
+            W, Gd = Q0[:, :kw], Q0[:, kw:]
+            Gd = Gd - W @ (W.T @ Gd)
+            Gd = Gd @ np.linalg.inv(np.linalg.cholesky(Gd.T @ Gd)).T
+            Q0 = np.hstack([W, Gd])
+        its, prs, rrs, errs, conds, grs, fails = [], [], [], [], [], [], 0
+        for b in range(nrep):
+            G = gram(b)
+            if b not in truth:
+                truth[b] = np.linalg.eigvalsh(G)[::-1][:R]
             try:
-                res.append(solve(G, Q0, degs, k=R, beta=beta, strict=strict,
-                                 tol=float(os.environ.get("TOL", "1e-12"))))
-            except np.linalg.LinAlgError:
-                res.append((99, 99))
-        its, prs = zip(*res)
-        print(f"{sc:12s} RR steps mean {np.mean(its):.2f} max {max(its)}  products mean {np.mean(prs):.2f}"
-              f"  hist {dict(zip(*np.unique(its, return_counts=True)))}")
+                n, pr, rr, th, cond, gr = solve(G, Q0, degs, k=R, beta=beta, strict=strict, bfix=bfix,
+                                            tol=float(os.environ.get("TOL", "1e-12")))
+            except np.linalg.LinAlgError:   # a Gram matrix that is not positive definite
+                fails += 1
+                continue
+            its.append(n)
+            prs.append(pr)
+            rrs.append(rr)
+            conds.append(cond)
+            grs.append(gr)
+            errs.append(np.max(np.abs(th - truth[b]) / truth[b]))
+        print(f"{sc:14s} loop steps mean {np.mean(its):.3f} max {max(its)}  hist "
+              f"{dict(zip(*[v.tolist() for v in np.unique(its, return_counts=True)]))}  RR steps mean {np.mean(rrs):.3f}"
+              f"  products mean {np.mean(prs):.3f}  max eigenvalue rel err {max(errs):.2e}"
+              f"  cond after first filter median {np.median(conds):.2e} max {max(conds):.2e}  Cholesky failures {fails}"
+              + (f"  theta_p / theta_k at step 0 max {max(grs):.4f}" if max(grs) > 0 else ""),
+              flush=True)
 
 
 if __name__ == "__main__":
