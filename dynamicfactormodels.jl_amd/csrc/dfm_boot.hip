@@ -477,13 +477,22 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
     HIPCHK(ctx, dalloc(&wCh.p, (size_t)nb * chow_wide_work(T, N, r)));
     HIPCHK(ctx, dalloc(&wSc.p, (size_t)3 * nb * N));
   }
+  // what every subspace solve of this job shares; each call adds its batch, block, start and outputs
+  EigArgs ea0;
+  ea0.k = r; ea0.kw = r;
+  ea0.tol = etol; ea0.maxit = ctx->maxit; ea0.poll = ctx->poll;
+  ea0.ws = w.eig; ea0.status = w.status;
+  ea0.st = st; ea0.tf = timer_cb; ea0.tctx = ctx;
+  ea0.subspace = esub;
   // top-r eigenpairs of n Grams (stride mm*mm): subspace iteration or dense
   auto eig_any = [&](const double *G, int mm, int n, const double *warm, double *lam, double *Uk, double *tr,
                      int64_t b0) -> int {
     if (!wide) {
-      const int pj = eig_block_p(mm, r, ctx->block);
-      int rc = eig_run(G, mm, (int64_t)mm * mm, mm, n, r, pj, warm, r, etol, ctx->maxit, ctx->poll, w.eig, lam, Uk,
-                       tr, w.status, nullptr, st, timer_cb, ctx, b0, esub);
+      EigArgs ea = ea0;
+      ea.nb = n; ea.p = eig_block_p(mm, r, ctx->block);
+      ea.warm = warm;
+      ea.lam = lam; ea.Uk = Uk; ea.trace_out = tr;
+      int rc = eig_run(G, mm, (int64_t)mm * mm, mm, ea, nullptr, b0);
       if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
       note_iters(ctx);
       return 0;
@@ -526,11 +535,17 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
       // solve that starts with the filter: a number of the model alone, the same for every batch, lane and shard
       // (fact implies nblk == 1, so M->lam[r - 1] is lambda_r of the one full-sample Gram, not a sum over break blocks)
       const double lamk = spread >= 1.0 ? M->lam[r - 1] : 0.0;
-      int rc = eig_run_factored(fb, idx + b0 * T, et, n, r, pf, M->Ub, r, etol,
-                                ctx->maxit, ctx->poll,
-                                w.eig, w.fact, w.lam, need_fl ? w.Uk : nullptr, w.trace, w.status, st, timer_cb,
-                                ctx, w.off, w.lst,
-                                (M->count_ctx ? M->count_ctx : ctx)->cnt_dev, esub, spread, ctx_poll(ctx), lamk);
+      EigArgs ea = ea0;
+      ea.nb = n; ea.p = pf;
+      ea.warm = M->Ub;
+      ea.lam = w.lam; ea.Uk = need_fl ? w.Uk : nullptr; ea.trace_out = w.trace;
+      FactArgs fa;
+      fa.idx = idx + b0 * T; fa.eta = et; fa.fws = w.fact;
+      fa.off = w.off; fa.lst = w.lst;
+      fa.cnt = (M->count_ctx ? M->count_ctx : ctx)->cnt_dev;
+      fa.spread = spread; fa.lamk = lamk;
+      fa.pb = ctx_poll(ctx);
+      int rc = eig_run_factored(fb, ea, fa);
       if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
       note_iters(ctx);
       if (need_fl) {

@@ -35,8 +35,14 @@ static int run_eig(dfm_ctx *ctx, const double *G, int m, int nb, int k, const do
   // gap (a break fit's LR in tests/test_gpu_breaks.py: 4e-10 off the oracle;
   // the tridiagonal path's inverse-iteration vectors: 9e-10)
   const double tol = nb == 1 ? std::min(ctx->tol, 1e-14) : ctx->tol;
-  int rc = eig_run(G, m, (int64_t)m * m, m, nb, k, p, warm, kw, tol, ctx->maxit, ctx->poll, ws,
-                   lam, Uk, trace, status_dev, nullptr, ctx->stream, timer_cb, ctx, 0);
+  EigArgs ea;
+  ea.nb = nb; ea.k = k; ea.p = p;
+  ea.warm = warm; ea.kw = kw;
+  ea.tol = tol; ea.maxit = ctx->maxit; ea.poll = ctx->poll;
+  ea.ws = ws;
+  ea.lam = lam; ea.Uk = Uk; ea.trace_out = trace; ea.status = status_dev;
+  ea.st = ctx->stream; ea.tf = timer_cb; ea.tctx = ctx;
+  int rc = eig_run(G, m, (int64_t)m * m, m, ea, nullptr, 0);
   hipFreeAsync(ws, ctx->stream);
   hipStreamSynchronize(ctx->stream);
   if (rc != 0) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);

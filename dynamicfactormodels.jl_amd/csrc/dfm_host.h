@@ -2,7 +2,7 @@
 // (dfm_ctx.hip, dfm_fit.hip, dfm_boot.hip, dfm_windows.hip): the context and
 // model objects, error reporting, timing scopes and the small helpers those
 // files share.  Host-side orchestration only; all arithmetic runs in the
-// kernels of dfm_gram.hip (K1), dfm_eig.hip (K2), dfm_model.hip / dfm_chow.hip (K3).
+// kernels of dfm_gram.hip (K1), dfm_eig.hip / dfm_fact.hip (K2), dfm_model.hip / dfm_chow.hip (K3).
 #pragma once
 #include "dfm_internal.h"
 #include "../../include/dfm.h"

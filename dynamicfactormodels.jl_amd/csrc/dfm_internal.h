@@ -1,6 +1,7 @@
 // dfm_internal.h — the one declaration of every libdfm symbol that one .hip
 // file defines and another uses, grouped by the defining file.  Every .hip
-// includes it; default arguments live here only.
+// includes it; default arguments live here only.  (What only dfm_eig.hip and
+// dfm_fact.hip share is in their private dfm_eig.h.)
 #pragma once
 #include "dfm_common.h"
 
@@ -53,7 +54,7 @@ hipError_t launch_gemm(bool a_trans, const double *A, int64_t lda, const double 
                        const int *col_done = nullptr, int col_group = 1, bool b_padded = false,
                        const int *clist = nullptr, const int *ccount = nullptr);
 
-// ---- dfm_eig.hip
+// ---- dfm_eig.hip (the explicit-Gram top-k solver)
 __global__ void eig_trace_kernel(const double *__restrict__ G, int64_t ldg, int64_t strideG, int m,
                                  double *__restrict__ trace);
 const int *eig_iters_ptr(char *ws, int m, int nb, int P, int maxit);
@@ -63,17 +64,41 @@ extern thread_local int64_t g_last_rep_iters;
 extern thread_local int64_t g_last_gemm_products;
 int eig_block_p(int m, int k, int req);
 int fact_block_p(int m, int k, int req);
-int eig_run(const double *G, int64_t ldg, int64_t strideG, int m, int nb, int k, int p,
-            const double *warm, int kw, double tol, int maxit, int poll, char *ws, double *lam,
-            double *Uk, double *trace_out, int *status, int *iters_host, hipStream_t st,
-            timer_fn tf, void *tctx, int64_t rep0, int subspace = 0);
+// What both solvers take besides the matrix.  Callers fill the members by name.
+struct EigArgs {
+  int nb, k, p;                   // problems, wanted pairs, block columns (k <= p <= 32)
+  const double *warm;             // m x kw start vectors shared by all problems (nullptr, 0: hashed start)
+  int kw;
+  double tol;                     // >= 0: eigenvector residual rule; < 0: eigenvalue bound
+  int maxit, poll;
+  char *ws;                       // eig_workspace_bytes_padded
+  double *lam, *Uk, *trace_out;   // nb x k, nb x m x k (nullptr: eigenvalues only), nb
+  int *status;                    // nb
+  hipStream_t st;
+  timer_fn tf;
+  void *tctx;
+  int subspace = 0;               // EigWork::subspace
+};
+int eig_run(const double *G, int64_t ldg, int64_t strideG, int m, const EigArgs &a, int *iters_host, int64_t rep0);
+
+// ---- dfm_fact.hip (the factored bootstrap solver)
 size_t fact_workspace_bytes(int T, int nb, int P);
-int eig_run_factored(const FactBase &fb, const int32_t *idx, const double *eta, int nb, int k, int p,
-                     const double *warm, int kw, double tol, int maxit, int poll, char *ws, char *fws,
-                     double *lam, double *Uk, double *trace_out, int *status, hipStream_t st,
-                     timer_fn tf, void *tctx, int *off, int *lst, long long *cnt = nullptr, int subspace = 0,
-                     double spread = 0.0, const PollBuf *pb = nullptr, double lamk = 0.0);
+// What the factored solver takes on top of EigArgs.
+struct FactArgs {
+  const int32_t *idx;             // nb x T draws
+  const double *eta;
+  char *fws;                      // fact_workspace_bytes
+  int *off, *lst;                 // the draws' CSR (out; fact_loadings reads it)
+  long long *cnt = nullptr;       // device counters of replicate-iterations and GEMM products (nullptr: host stats)
+  double spread = 0.0;            // lambda_1 / lambda_k of the base fit (>= 1: warm schedule)
+  double lamk = 0.0;              // lambda_k of the base fit (> 0: a warm solve may start with the filter)
+  const PollBuf *pb = nullptr;
+};
+int eig_run_factored(const FactBase &fb, const EigArgs &a, const FactArgs &f);
 int fact_t_max();
+hipError_t launch_fact_ftf(const FactBase &fb, double *FtF, hipStream_t st);
+
+// ---- dfm_fact_model.hip (model-level factored precompute, explicit factored Gram, loadings)
 int fact_loadings(const FactBase &fb, const double *Ep, int64_t ld, int N, const double *Lb,
                   const double *Uk, const double *eta, const int *off, const int *lst, int nb,
                   double *Fout, double *Lout, char *ws, hipStream_t st);
@@ -81,12 +106,8 @@ size_t fact_loadings_bytes(int T, int N, int r, int nb);
 hipError_t launch_fact_fsf(int T, int r, const double *Fb, const double *S, double *FSF, int64_t ldH, hipStream_t st);
 hipError_t launch_gram_fact(const FactBase &fb, const double *FSF, const int32_t *idx, const double *eta, int nb,
                             double *G, int64_t ldg, int64_t strideG, hipStream_t st);
-hipError_t launch_fact_ftf(const FactBase &fb, double *FtF, hipStream_t st);
 int fact_precompute(const double *Ep, int64_t ld, int T, int N, int r, const double *Lb, const double *Fb,
                     const double *H, int64_t ldH, double *EL, double *S, double *cF, double *hd, hipStream_t st);
-int spectrum_max();
-hipError_t launch_spectrum_jacobi(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,
-                                  double *ev, hipStream_t st);
 
 // ---- dfm_model.hip
 __global__ void panel_from_colmajor_kernel(const double *__restrict__ X, int64_t ldx, int T, int N,
@@ -138,6 +159,7 @@ hipError_t launch_targeted(int mode, const double *y, const double *w, int q, co
                            size_t ws_bytes, hipStream_t st, int *bad);
 
 // ---- dfm_spec.hip
+int spectrum_max();
 int64_t spectrum_work(int m, int nb);
 int spectrum_any_max();
 hipError_t launch_spectrum_var(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,

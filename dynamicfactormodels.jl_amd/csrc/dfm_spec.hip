@@ -4,7 +4,7 @@
 //   * the PCp criteria's sigma^2 = V(ceil(m/2)) of the unrestricted fit
 //     (src/criteria.jl:18, :23, :28), i.e. the tail sum of the spectrum;
 //   * IC sweeps with kmax > 24 (src/DynamicFactorModel.jl:54, kmax = ceil(m/2)).
-// m <= SPEC_MAX goes to the LDS-resident Jacobi kernel of dfm_eig.hip.
+// m <= JACOBI_MAX goes to the LDS-resident Jacobi kernel (spectrum_kernel).
 // Larger m: Householder tridiagonalisation (one workgroup per matrix, the
 // trailing matrix in HBM, ONE read+write pass per reflector: the previous
 // reflector's rank-2 update is applied lazily in the same pass that forms the
@@ -225,6 +225,98 @@ __global__ __launch_bounds__(256) void bisect_kernel(const double *__restrict__ 
   if (live && g == 0) ev[(int64_t)rep * (dm ? mst : nev) + j] = 0.5 * (lo + hi);
 }
 
+// ------------------------------------------------------------ full spectrum
+// All eigenvalues (descending) of one m x m symmetric matrix, m <= SPEC_MAX,
+// by parallel cyclic Jacobi with the whole matrix resident in LDS (SPEC_MAX
+// is what the LDS holds; launch_spectrum_var sends only m <= JACOBI_MAX
+// here, and dfm_fit.hip reads spectrum_max() as its small-m threshold).  Used for
+// the PCp criteria's unrestricted sigma^2 = V(ceil(m/2)) (src/criteria.jl:18)
+// and for full IC sweeps (k up to ceil(m/2), src/DynamicFactorModel.jl:54).
+constexpr int SPEC_MAX = 140;
+// Matrix rep has size m0 + dm * rep (expanding windows share one prefix Gram);
+// ev rows have stride mst.
+__global__ __launch_bounds__(256) void spectrum_kernel(const double *__restrict__ G, int64_t ldg,
+                                                       int64_t strideG, int mst, int m0, int dm,
+                                                       double *__restrict__ ev) {
+  constexpr int S = SPEC_MAX + 1;
+  __shared__ double H[SPEC_MAX * S];
+  __shared__ double rc[SPEC_MAX / 2], rs[SPEC_MAX / 2];
+  __shared__ int ra[SPEC_MAX / 2], rbb[SPEC_MAX / 2];
+  __shared__ int sdone;
+  const int tid = threadIdx.x, rep = blockIdx.x;
+  const double *g = G + (int64_t)rep * strideG;
+  const int m = m0 + dm * rep;
+  const int n = m + (m & 1);
+  for (int e = tid; e < n * n; e += 256) {
+    const int a = e / n, c = e % n;
+    H[a * S + c] = (a < m && c < m) ? 0.5 * (g[(int64_t)a * ldg + c] + g[(int64_t)c * ldg + a]) : 0.0;
+  }
+  __syncthreads();
+  // classic threshold Jacobi (see eig_small_kernel): rotate while |h_ab| >
+  // 4 eps sqrt(|h_aa h_bb|); stop after a sweep that rotates nothing
+  for (int sweep = 0; sweep < 80; ++sweep) {
+    if (tid == 0) sdone = 1;
+    __syncthreads();
+    for (int r = 0; r < n - 1; ++r) {
+      for (int s = tid; s < n / 2; s += 256) {
+        const int pa = s, pb = n - 1 - s;
+        int a = pa == 0 ? 0 : 1 + (pa - 1 + r) % (n - 1);
+        int b = pb == 0 ? 0 : 1 + (pb - 1 + r) % (n - 1);
+        if (a > b) { const int t = a; a = b; b = t; }
+        double c = 1.0, sn = 0.0;
+        const double hab = H[a * S + b], haa = H[a * S + a], hbb = H[b * S + b];
+        if (fabs(hab) > 1e-300 && fabs(hab) > 8.9e-16 * sqrt(fabs(haa) * fabs(hbb))) {
+          sdone = 0;
+          const double zeta = (hbb - haa) / (2.0 * hab);
+          const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+          c = 1.0 / sqrt(1.0 + t * t);
+          sn = t * c;
+        }
+        ra[s] = a; rbb[s] = b; rc[s] = c; rs[s] = sn;
+      }
+      __syncthreads();
+      for (int e = tid; e < (n / 2) * n; e += 256) {
+        const int s = e / n, kk = e % n;
+        const int a = ra[s], b = rbb[s];
+        const double c = rc[s], sn = rs[s];
+        const double ha = H[kk * S + a], hb = H[kk * S + b];
+        H[kk * S + a] = c * ha - sn * hb;
+        H[kk * S + b] = sn * ha + c * hb;
+      }
+      __syncthreads();
+      for (int e = tid; e < (n / 2) * n; e += 256) {
+        const int s = e / n, kk = e % n;
+        const int a = ra[s], b = rbb[s];
+        const double c = rc[s], sn = rs[s];
+        const double ha = H[a * S + kk], hb = H[b * S + kk];
+        H[a * S + kk] = c * ha - sn * hb;
+        H[b * S + kk] = sn * ha + c * hb;
+      }
+      __syncthreads();
+    }
+    if (sdone) break;
+    __syncthreads();
+  }
+  // sort descending; the padding index (if any) carries an exact 0 that is dropped
+  for (int i = tid; i < n; i += 256) {
+    const double v = H[i * S + i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const double u = H[j * S + j];
+      if (u > v || (u == v && j < i)) ++rank;
+    }
+    if (rank < m) ev[(int64_t)rep * mst + rank] = v;
+  }
+}
+
+int spectrum_max() { return SPEC_MAX; }
+static hipError_t launch_spectrum_jacobi(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,
+                                  double *ev, hipStream_t st) {
+  if (m > SPEC_MAX || m0 < 1 || m0 + dm * (nb - 1) > m) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(spectrum_kernel, dim3(nb), dim3(256), 0, st, G, ldg, strideG, m, m0, dm, ev);
+  return hipGetLastError();
+}
+
 // Jacobi (LDS-resident, 1 WG per CU) only for small matrices: from m ~ 40 on
 // the tridiagonal path's O(m) barriers beat Jacobi's O(sweeps * m).
 constexpr int JACOBI_MAX = 32;
@@ -308,7 +400,7 @@ __global__ __launch_bounds__(TRL_THREADS) void tridiag_lds_kernel(const double *
 
 // All eigenvalues (descending) of nb symmetric matrices G + rep * strideG;
 // matrix rep has size m0 + dm * rep <= m (dm = 0: all m x m), ev rows stride m.
-// work: spectrum_work(m, nb) doubles (none for m <= SPEC_MAX).
+// work: spectrum_work(m, nb) doubles (none for m <= JACOBI_MAX).
 hipError_t launch_spectrum_var(const double *G, int64_t ldg, int64_t strideG, int m, int m0, int dm, int nb,
                                double *ev, double *work, hipStream_t st) {
   if (m0 < 1 || nb < 1 || dm < 0 || m0 + (int64_t)dm * (nb - 1) > m) return hipErrorInvalidValue;

@@ -338,6 +338,11 @@ static int windows_impl(dfm_ctx *ctx, const double *y, const double *w, int q, i
     lam = (double *)dal((size_t)P * kmax * 8); Uk = (double *)dal((size_t)P * m * kmax * 8);
     F = (double *)dal((size_t)P * T * kmax * 8);
     if (!lam || !Uk || !F) return fail(ctx, 1002, "dfm_windows: out of device memory");
+    EigArgs ea;   // cold starts; each branch adds its batch, workspace and outputs
+    ea.k = kmax; ea.p = p;
+    ea.warm = nullptr; ea.kw = 0;
+    ea.tol = ctx->tol; ea.maxit = ctx->maxit; ea.poll = ctx->poll;
+    ea.st = st; ea.tf = timer_cb; ea.tctx = ctx;
     if (orient == 0 && !explicit_gram) {
       char *ews = (char *)dal(eig_workspace_bytes_padded(m, P, Pb, ctx->maxit));
       double *zero = (double *)dal((size_t)T * 8), *hd = (double *)dal((size_t)T * 8);
@@ -349,8 +354,13 @@ static int windows_impl(dfm_ctx *ctx, const double *y, const double *w, int q, i
       if (rc) return fail(ctx, rc, "precompute");
       HIPCHK(ctx, hipMemsetAsync(zero, 0, (size_t)T * 8, st));
       FactBase fb{T, 0, ldH, zero, zero, zero, H, zero, hd};
-      rc = eig_run_factored(fb, didx, deta, P, kmax, p, nullptr, 0, ctx->tol, ctx->maxit, ctx->poll, ews, fws,
-                            lam, Uk, tr, stt, st, timer_cb, ctx, off, lst, nullptr, 0, 0.0, ctx_poll(ctx));
+      ea.nb = P; ea.ws = ews;
+      ea.lam = lam; ea.Uk = Uk; ea.trace_out = tr; ea.status = stt;
+      FactArgs fa;
+      fa.idx = didx; fa.eta = deta; fa.fws = fws;
+      fa.off = off; fa.lst = lst;
+      fa.pb = ctx_poll(ctx);
+      rc = eig_run_factored(fb, ea, fa);
       if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
     } else if (orient == 0) {
       // T > the factored solver's range: the windows' masked T x T Grams in
@@ -368,17 +378,19 @@ static int windows_impl(dfm_ctx *ctx, const double *y, const double *w, int q, i
                              didx + (size_t)c0 * T, deta + (size_t)c0 * T, T, Gc);
           HIPCHK(ctx, hipGetLastError());
         }
-        rc = eig_run(Gc, T, (int64_t)T * T, T, pc, kmax, p, nullptr, 0, ctx->tol, ctx->maxit, ctx->poll, ews,
-                     lam + (size_t)c0 * kmax, Uk + (size_t)c0 * T * kmax, tr + c0, stt + c0, nullptr, st, timer_cb,
-                     ctx, 0);
+        ea.nb = pc; ea.ws = ews;
+        ea.lam = lam + (size_t)c0 * kmax; ea.Uk = Uk + (size_t)c0 * T * kmax;
+        ea.trace_out = tr + c0; ea.status = stt + c0;
+        rc = eig_run(Gc, T, (int64_t)T * T, T, ea, nullptr, 0);
         if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
       }
     } else {
       char *ews = (char *)dal(eig_workspace_bytes_padded(m, P, Pb, ctx->maxit));
       double *Ld = (double *)dal((size_t)P * N * kmax * 8);
       if (!ews || !Ld) return fail(ctx, 1002, "dfm_windows: out of device memory");
-      rc = eig_run(G, N, (int64_t)N * N, N, P, kmax, p, nullptr, 0, ctx->tol, ctx->maxit, ctx->poll, ews, lam, Uk,
-                   tr, stt, nullptr, st, timer_cb, ctx, 0);
+      ea.nb = P; ea.ws = ews;
+      ea.lam = lam; ea.Uk = Uk; ea.trace_out = tr; ea.status = stt;
+      rc = eig_run(G, N, (int64_t)N * N, N, ea, nullptr, 0);
       if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
       Scope sc(ctx, DFM_KC_FACTORS);
       launch_factors(1, msrc, T, N, kmax, P, Uk, F, Ld, nullptr, st);

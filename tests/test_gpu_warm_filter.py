@@ -1,5 +1,5 @@
 """The factored bootstrap's warm solve without a first Rayleigh-Ritz step
-(dfm_eig.hip eig_run_fact2_t: the degree-d0 filter runs on the warm start Q0
+(dfm_fact.hip eig_run_fact2_t: the degree-d0 filter runs on the warm start Q0
 itself, with the interval end a constant of the base fit, and the first
 Rayleigh-Ritz step comes after it).
 
