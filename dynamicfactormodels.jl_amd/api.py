@@ -94,8 +94,11 @@ class Context:
         ri, gp = C.c_int64(), C.c_int64()
         self.check(self.lib.dfm_ctx_rep_iters(self.h, C.byref(ri)))
         self.check(self.lib.dfm_ctx_gemm_products(self.h, C.byref(gp)))
+        g32 = C.c_int64()
+        self.check(self.lib.dfm_ctx_gemm_products_f32(self.h, C.byref(g32)))
         return {"batches": b.value, "iterations": t.value, "max_iterations": m.value,
-                "replicate_iterations": ri.value, "gemm_products": gp.value}
+                "replicate_iterations": ri.value, "gemm_products": gp.value,
+                "gemm_products_f32": g32.value}
 
     def close(self):
         if getattr(self, "h", None) and not _lib.shutting_down():

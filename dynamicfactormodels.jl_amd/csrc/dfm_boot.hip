@@ -97,6 +97,7 @@ static void note_iters(dfm_ctx *ctx) {
   ctx->eig_iters_max = std::max<int64_t>(ctx->eig_iters_max, g_last_iters);
   ctx->rep_iters += g_last_rep_iters;
   ctx->gemm_products += g_last_gemm_products;
+  ctx->gemm_products_f32 += g_last_gemm_products_f32;
 }
 
 // Per-batch device workspace layout for the bootstrap.
@@ -258,7 +259,9 @@ static int bootstrap_lanes(dfm_model *M, int nl, int kind, int64_t B, const int3
     ctx->eig_iters_max = std::max(ctx->eig_iters_max, lc->eig_iters_max);
     ctx->rep_iters += lc->rep_iters;
     ctx->gemm_products += lc->gemm_products;
+    ctx->gemm_products_f32 += lc->gemm_products_f32;
     lc->eig_batches = lc->eig_iters = lc->eig_iters_max = lc->rep_iters = lc->gemm_products = 0;
+    lc->gemm_products_f32 = 0;
   }
   if (rcl[0]) return rcl[0];
   for (int j = 1; j < nl; ++j)
@@ -417,7 +420,14 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
     // F'F once per model (it was one launch per solve on every lane's stream)
     HIPCHK(ctx, dalloc(&M->FtF, 256));
     HIPCHK(ctx, launch_fact_ftf(FactBase{T, r, M->ldH, M->F, M->EL, M->S, M->H, M->cF, M->hd}, M->FtF, st));
+    // H32 = float(H / hmax) for the fp32 middle products (a clone rebuilds it here, on its own stream, as it
+    // rebuilds H: fact_ready is not copied)
+    HIPCHK(ctx, hipMalloc((void **)&M->H32, (size_t)T * M->ldH * sizeof(float)));
+    HIPCHK(ctx, launch_fact_h32(M->H, M->ldH, T, M->hd, M->H32, st));
+    std::vector<double> hdh(T);
+    HIPCHK(ctx, hipMemcpyAsync(hdh.data(), M->hd, (size_t)T * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    M->hmax = fact_hmax(hdh.data(), T);
     M->fact_ready = true;
   }
   if (gwk && !M->Kwk) {
@@ -521,7 +531,7 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
     HIPCHK(ctx, dalloc(&pSig.p, (size_t)nb));
     if (spectrum_work(m, (int)nb) > 0) HIPCHK(ctx, dalloc(&pWk.p, (size_t)spectrum_work(m, (int)nb)));
   }
-  FactBase fb{T, r, M->ldH, M->F, M->EL, M->S, M->H, M->cF, M->hd, M->FtF};
+  FactBase fb{T, r, M->ldH, M->F, M->EL, M->S, M->H, M->cF, M->hd, M->FtF, M->H32, M->hmax};
   for (int64_t b0 = 0; b0 < B; b0 += nb) {
     const int n = (int)std::min<int64_t>(nb, B - b0);
     PanelSrc src{M->Cp, M->Ep, idx + b0 * T, kind == DFM_BOOT_WILD ? eta + b0 * T : nullptr, M->ld, T};

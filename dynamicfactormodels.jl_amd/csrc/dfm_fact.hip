@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <vector>
 
 namespace dfm {
 
@@ -31,6 +32,9 @@ DFM_DEV int64_t zrm_stride(int T, int pz) { return (int64_t)((T + 15) & ~15) * p
 DFM_DEV int64_t zrm_ix(int rep, int s, int c, int pz, int64_t zrs) {
   return (int64_t)rep * zrs + (int64_t)(s >> 4) * (16 * pz) + 16 * c + (s & 15);
 }
+// (the fp32 middle products' Z32 and HZ32 use the same indexing with float
+// elements, Z32 in the first half of Z's region, HZ32 in HZ's: round 8)
+typedef float zf4 __attribute__((ext_vector_type(4)));
 
 // Per replicate: CSR of idx (bucket s lists t ascending — fixed summation
 // order, bit-reproducible), and trace(G*) = sum_t ||x*_t||^2 =
@@ -46,7 +50,7 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
                            const double *set, const int *so, const int *sl, const double *Qn,
                            double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab,
                            const dv4 *aacc, double *sred, int ps, double *zst, const double *apre = nullptr,
-                           double *__restrict__ pvr = nullptr);
+                           double *__restrict__ pvr = nullptr, bool z32 = false);
 // a = F'Q0 of the first product for the whole batch: F and the warm start Q0
 // are shared by every replicate, so boot_prep_kernel's per-workgroup tile
 // loop and fixed-order wave sums are run ONCE, in the same order (one
@@ -104,7 +108,8 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
                                                         const double *__restrict__ Q0, int ps,
                                                         double *__restrict__ Zc, int64_t ldz, int pz,
                                                         double *__restrict__ ab, const double *__restrict__ apre,
-                                                        double *__restrict__ PV, double *__restrict__ FV) {
+                                                        double *__restrict__ PV, double *__restrict__ FV, int z32) {
+  // z32: Z0 leaves as float (the first product runs in fp32); PV, FV, a, cc stay fp64
   static_assert(BW * 64 == 256, "prep runs the factored passes' wave layout");
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
@@ -228,13 +233,17 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
     {
       const int64_t zrs = zrm_stride(T, pz);
       const int npad = ((T + 15) & ~15) - T;
-      for (int e = tid; e < npad * pz; e += 256) Zc[zrm_ix(rep, T + e / pz, e % pz, pz, zrs)] = 0.0;
+      if (z32)
+        for (int e = tid; e < npad * pz; e += 256)
+          reinterpret_cast<float *>(Zc)[zrm_ix(rep, T + e / pz, e % pz, pz, zrs)] = 0.0f;
+      else
+        for (int e = tid; e < npad * pz; e += 256) Zc[zrm_ix(rep, T + e / pz, e % pz, pz, zrs)] = 0.0;
     }
     __syncthreads();   // so / set visible
     // (PV, FV: a warm solve without a first Rayleigh-Ritz step filters V0 = Q0 itself, so the middle Horner
     // steps' PV = P'D V0 is Z0 row by row and FV = F'V0 is a)
     zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, aacc, sred, ps, zst[wave],
-                           apre, PV ? PV + (int64_t)rep * T * P : nullptr);
+                           apre, PV ? PV + (int64_t)rep * T * P : nullptr, z32 != 0);
     if (FV && apre)
       for (int e = tid; e < 16 * P; e += 256) FV[(int64_t)rep * 16 * P + e] = apre[e];
   }
@@ -696,7 +705,7 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
                            const double *set, const int *so, const int *sl, const double *Qn,
                            double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab,
                            const dv4 *aacc, double *sred, int ps, double *zst, const double *apre,
-                           double *__restrict__ pvr) {
+                           double *__restrict__ pvr, bool z32) {
   const int64_t zrs = zrm_stride(T, pz);
   constexpr int NT = P / 16;
   const int li = lane & 15, lk = lane >> 4;
@@ -767,8 +776,14 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
         for (int ct = 0; ct < NT; ++ct)
           if (16 * ct + li < pz) zst[16 * (16 * ct + li) + 4 * g + lk] = s0 + 4 * g + lk < T ? z[g][ct] : 0.0;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
-      for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{zst[2 * e], zst[2 * e + 1]};
+      if (z32) {   // the fp32 H.Z GEMM's operand: the same chunk indexing, float elements (round to nearest)
+        zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+        for (int e = lane; e < 4 * pz; e += 64)
+          zc4[e] = zf4{(float)zst[4 * e], (float)zst[4 * e + 1], (float)zst[4 * e + 2], (float)zst[4 * e + 3]};
+      } else {
+        double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+        for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{zst[2 * e], zst[2 * e + 1]};
+      }
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -1277,7 +1292,15 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_pv_kernel(FactBase fb, EigWor
   }
 }
 
-template <int P, bool FAST>
+// LP (round 8, the fp32 middle products of a warm eigenvalue-rule solve): 0 =
+// HZ and Z in fp64 as described; 1 = HZ arrives as float HZ32 = H32 Z32 in Z's
+// replicate-major chunk layout (this replicate's 16-row tile one contiguous
+// 64 pz-byte piece, fetched as 16-B pieces and transposed through the EL
+// stage) and is scaled by hscale = hmax on the way in, Z leaves as float Z32,
+// rounded to nearest; 2 = HZ32 in, fp64 Z out in the normal layout (the last
+// middle step, whose Z feeds the filter's fp64 product).  All arithmetic, a
+// and cc stay fp64 in every mode; cc is formed from the unrounded Z.
+template <int P, bool FAST, int LP>
 __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, EigWork w, int T, int p,
                                                             const double *__restrict__ HZ, int64_t ldz, int pz,
                                                             double *__restrict__ ab, double fai, double bbeta, int k,
@@ -1287,7 +1310,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
                                                             const double *__restrict__ FV,
                                                             const double *__restrict__ FtF,
                                                             double *__restrict__ Zc, int ps, double bfix,
-                                                            double lead) {
+                                                            double lead, double hscale) {
   // bfix > 0: the interval end of a filter-only first step (boot_cheb_kernel);
   // lead: the scale of the incoming S_{i+1} not yet applied to its Z, a, cc —
   // the filter's leading coefficient a_d at the first step of such a filter
@@ -1354,6 +1377,13 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
       }
     }
     const double e2l = t0 + li < T ? e2r[t0 + li] : 0.0;
+    zf4 h4[NT];   // LP: the tile's HZ32 chunk, piece e = 64 u + lane: column e >> 2, rows 4 (e & 3) .. + 3
+    if constexpr (LP != 0) {
+      const zf4 *hc = reinterpret_cast<const zf4 *>(reinterpret_cast<const float *>(HZ) + (int64_t)rep * zrs +
+                                                     (int64_t)tile * 16 * pz);
+#pragma unroll
+      for (int u = 0; u < NT; ++u) h4[u] = u * 64 + lane < 4 * pz ? hc[u * 64 + lane] : zf4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int s = t0 + 4 * g + lk;
@@ -1361,7 +1391,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
 #pragma unroll
       for (int ct = 0; ct < NT; ++ct) {
         const int c = 16 * ct + li;
-        hz[ct][g] = c < pz ? HZ[(int64_t)sc * ldz + (int64_t)rep * pz + c] : 0.0;
+        if constexpr (LP == 0) hz[ct][g] = c < pz ? HZ[(int64_t)sc * ldz + (int64_t)rep * pz + c] : 0.0;
         pv[ct][g] = c < ps ? pvr[(int64_t)sc * ps + c] : 0.0;
       }
     }
@@ -1398,6 +1428,31 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
       e2v[g] = v ? __shfl(e2l, 4 * g + lk, 16) : 0.0;
       pfa[g] = (v && li < r) ? sP[(4 * g + lk) * RS + li] : 0.0;
       ea[g] = (v && li < r) ? sE[(4 * g + lk) * RS + li] : 0.0;
+    }
+    if constexpr (LP != 0) {
+      // HZ32 through the EL stage (its reads above are complete in this wave's
+      // LDS order): column c at float offset 17 c (17 pz <= 17 P floats fit the
+      // stage's 16 x 17 doubles), read back in the accumulator layout
+      static_assert(17 * P <= 2 * 16 * 17, "the EL stage holds the HZ32 chunk");
+      float *sH = reinterpret_cast<float *>(sE);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int u = 0; u < NT; ++u) {
+        const int e = u * 64 + lane;
+        if (e < 4 * pz) {
+          float *d = sH + 17 * (e >> 2) + 4 * (e & 3);
+          d[0] = h4[u][0]; d[1] = h4[u][1]; d[2] = h4[u][2]; d[3] = h4[u][3];
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) {
+          const int c = 16 * ct + li;
+          hz[ct][g] = c < pz ? hscale * (double)sH[17 * c + 4 * g + lk] : 0.0;
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // before the next tile's EL rows overwrite the stage
     }
     dv4 yP[NT], yE[NT];
 #pragma unroll
@@ -1439,7 +1494,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         if (c < pz) sP[16 * c + 4 * g + lk] = zv[ct][g];
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    {
+    if constexpr (LP == 1) {
+      zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+      for (int e = lane; e < 4 * pz; e += 64)
+        zc4[e] = zf4{(float)sP[4 * e], (float)sP[4 * e + 1], (float)sP[4 * e + 2], (float)sP[4 * e + 3]};
+    } else {
       double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
       for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{sP[2 * e], sP[2 * e + 1]};
     }
@@ -1571,6 +1630,25 @@ constexpr double kWarmFixBeta = 0.21;
 static bool warm_keep_step0() {   // (read at every solve: one process can run both schedules)
   const char *e = getenv("DFM_FACT_STEP0");
   return e && atoi(e) != 0;
+}
+// Under the eigenvalue rule (tol < 0) the middle products of that filter-only
+// step — products 1 .. d0 - 1 of its d0 — run in fp32 (gemmh_zrm_f32_kernel,
+// round 8).  The filter only has to deliver a good subspace: the Rayleigh-Ritz
+// step behind it and the Kato-Temple stopping rule stay fp64 and measure the
+// true residual, the eigenvalue error is quadratic in the subspace error, and
+// the rounding noise (relative to the idiosyncratic part H Z alone: PF bB,
+// EL a and F'F stay fp64) is damped by the fp64 product that follows.  The
+// CPU model (tools/eig_proto.py, F32 / NOISE) retires the same replicates at
+// the same steps with 64 times the fp32 noise in those products.  The last
+// product stays fp64: its rows go to the Rayleigh-Ritz step with no fp64
+// product behind them (the model degrades at 16 times the noise).  The strict
+// and subspace rules keep fp64 throughout: they bound the eigenvector
+// residual, which is linear in the subspace error (the model needs more
+// products there).  DFM_FACT_F32=0 (A/B only, read at every solve) restores
+// the fp64 middle products.
+static bool fact_f32_off() {
+  const char *e = getenv("DFM_FACT_F32");
+  return e && atoi(e) == 0;
 }
 
 // Guard columns kw..p-1 of the shared warm start Q0 (m rows of ps columns),
@@ -1739,7 +1817,11 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   const bool stg_ok = P == 16 && fb.r <= 8 && (fb.r & 1) == 0 && pz <= 16;
   auto chk = stg_ok ? boot_cheb_kernel<P, P == 16> : boot_cheb_kernel<P, false>;
   auto y2k = stg_ok ? boot_y2_kernel<P, P == 16> : boot_y2_kernel<P, false>;
-  auto cmk = stg_ok ? boot_cheb_mid_kernel<P, true> : boot_cheb_mid_kernel<P, false>;
+  // ... whose middle products run in fp32 under the eigenvalue rule (fact_f32_off)
+  const bool lowp = skip0 && a.tol < 0.0 && fb.H32 && std::isfinite(fb.hmax) && fb.hmax > 0.0 && m >= 16 && !fact_f32_off();
+  auto cmk = stg_ok ? boot_cheb_mid_kernel<P, true, 0> : boot_cheb_mid_kernel<P, false, 0>;
+  auto cmk32 = stg_ok ? boot_cheb_mid_kernel<P, true, 1> : boot_cheb_mid_kernel<P, false, 1>;     // HZ32 in, Z32 out
+  auto cmk32l = stg_ok ? boot_cheb_mid_kernel<P, true, 2> : boot_cheb_mid_kernel<P, false, 2>;    // HZ32 in, fp64 Z out
   { TimerScope ts(a, DFM_KC_EIG_OTHER);
     const int64_t n = (int64_t)m * P;
     dim3 grid((unsigned)((n + 255) / 256), 1);
@@ -1753,7 +1835,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     hipLaunchKernelGGL(prep_a_kernel<P>, dim3(1), dim3(256), 0, st, fb, Q0, ps, apre);
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(256), prep_lds, st,
                        fb, idx, eta, off, lst, w.trace, mid ? PFb : nullptr, E2b, Q0, ps, Zc, ldz, pz, ab, apre,
-                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr);
+                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, lowp ? 1 : 0);
     if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
     if (cheb_lds > 65536)   // T > 3276: above the default dynamic-LDS cap
       hipFuncSetAttribute((const void *)chk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cheb_lds);
@@ -1771,11 +1853,19 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
                                          listed ? alist : nullptr, listed ? acount : nullptr);
     return e == hipSuccess ? 0 : 1000 + (int)e;
   };
+  // ... or, a middle product of a lowp step 0, HZ32 = H32 Z32 in fp32 (Z32 in the first half of Z's region, HZ32 in
+  // HZ's, both in Z's chunk layout; every replicate is active there: no col_done, no list)
+  auto hz32 = [&]() -> int {
+    TimerScope ts(a, DFM_KC_GEMM);
+    const hipError_t e = launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
+    return e == hipSuccess ? 0 : 1000 + (int)e;
+  };
   // a middle Horner step S_i = G* S_{i+1} / b + c V0 in row-local form (Z, a, cc only) ...
-  auto horner_mid = [&](double c, double bbeta, double bfx, double lead) {
+  // (lp: 0 = fp64 HZ in, fp64 Z out; 1 = HZ32 in, Z32 out; 2 = HZ32 in, fp64 Z out)
+  auto horner_mid = [&](double c, double bbeta, double bfx, double lead, int lp = 0) {
     TimerScope ts(a, DFM_KC_EIG_APPLY);
-    hipLaunchKernelGGL(cmk, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz, pz, ab, c, bbeta, k, PFb, E2b, w.S,
-                       FVb, ftf, Zc, ps, bfx, lead);
+    hipLaunchKernelGGL(lp == 0 ? cmk : lp == 1 ? cmk32 : cmk32l, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz,
+                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax);
   };
   // ... and the last one, S_0: the new basis into cur, with its Z, a, cc
   auto horner_last = [&](double c, double bbeta, const double *V0, int64_t v0s, double bfx) {
@@ -1807,9 +1897,11 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     // Filter alone: step 0 without its Rayleigh-Ritz step.  S_d = a_d Q0 (prep
     // left the Z, a, cc, PV, FV of Q0; a_d goes into the first step's scale),
     // d0 products, the last step writes the new basis into cur with its Z, a, cc
+    // (lowp: products 1 .. d0 - 1 in fp32 — prep left Z0 as float, each middle step hands the next a float Z, the
+    // last of them an fp64 Z for product d0)
     for (int sp = 1; sp <= d0; ++sp) {
-      if (int rc = hz(false)) return rc;
-      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0);
+      if (int rc = (lowp && sp < d0) ? hz32() : hz(false)) return rc;
+      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, !lowp ? 0 : sp < d0 - 1 ? 1 : 2);
       else horner_last(ca0[0], 0.0, Q0, 0, bfix);
     }
     last_gemm = last_cheb = 0;
@@ -1888,6 +1980,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   }
   if (steps < 0) steps = it;
   g_last_iters = steps;
+  g_last_gemm_products_f32 = lowp ? (int64_t)(d0 - 1) * nb : 0;
   // the Chebyshev GEMM of iteration it runs after that iteration's check
   if (f.cnt) {   // (counted by eig_final_kernel below)
     g_last_rep_iters = g_last_gemm_products = 0;
@@ -1914,4 +2007,63 @@ int eig_run_factored(const FactBase &fb, const EigArgs &a, const FactArgs &f) {
   return eig_run_fact2_t<32>(fb, a, f);
 }
 int fact_t_max() { return F2_T_MAX; }
+
+// ---- dfm_debug_hz_f32 (tests/test_gpu_f32_filter.py): the fp32 H.Z GEMM on
+// operands packed as the solver packs them.
+__global__ void dbg_diag_kernel(const double *__restrict__ H, int64_t ldH, int T, double *__restrict__ hd) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < T) hd[t] = H[(int64_t)t * ldH + t];
+}
+// Z (T x nb pz, row-major, column block = replicate) -> Z32 chunks (zrm_ix, float, chunk rows past T zero)
+__global__ void dbg_pack_z32_kernel(const double *__restrict__ Z, int T, int nb, int pz, float *__restrict__ Z32) {
+  const int64_t zrs = zrm_stride(T, pz), n = (int64_t)nb * zrs;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int rep = (int)(i / zrs);
+  const int64_t o = i - (int64_t)rep * zrs;
+  const int ch = (int)(o / (16 * pz)), w = (int)(o - (int64_t)ch * 16 * pz), c = w >> 4, s = 16 * ch + (w & 15);
+  Z32[zrm_ix(rep, s, c, pz, zrs)] = s < T ? (float)Z[(int64_t)s * nb * pz + (int64_t)rep * pz + c] : 0.0f;
+}
+__global__ void dbg_unpack_hz32_kernel(const float *__restrict__ C32, int T, int nb, int pz, double *__restrict__ out) {
+  const int64_t n = (int64_t)T * nb * pz, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int s = (int)(i / ((int64_t)nb * pz));
+  const int x = (int)(i - (int64_t)s * nb * pz), rep = x / pz, c = x - rep * pz;
+  out[i] = (double)C32[zrm_ix(rep, s, c, pz, zrm_stride(T, pz))];
+}
 }  // namespace dfm
+
+// Debug entry, not part of include/dfm.h.  H: device, T x ldH fp64, ldH >=
+// round_up(T, 16) with zero padding columns; Z: device, T x nb pz fp64
+// (replicate rep's columns rep pz .. rep pz + pz - 1).  Builds H32 =
+// float(H / hmax) (fact_h32_kernel) and Z32, runs gemmh_zrm_f32_kernel and
+// writes out = double(H32 Z32) as T x nb pz — NOT rescaled by hmax, which is
+// returned in *hmax_out (may be null).
+extern "C" int dfm_debug_hz_f32(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
+                                double *out, double *hmax_out) {
+  using namespace dfm;
+  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || ldH < (T + 15) / 16 * 16 || (ldH & 3)) return -1;
+  hipStream_t st = ctx_stream(ctx);
+  const int64_t zrs = (int64_t)((T + 15) & ~15) * pz;
+  char *buf = nullptr;
+  const size_t b_hd = ((size_t)T * 8 + 255) & ~size_t(255), b_h32 = ((size_t)T * ldH * 4 + 255) & ~size_t(255),
+               b_z = ((size_t)nb * zrs * 4 + 255) & ~size_t(255);
+  if (hipMalloc((void **)&buf, b_hd + b_h32 + 2 * b_z) != hipSuccess) return 1002;
+  double *hd = (double *)buf;
+  float *H32 = (float *)(buf + b_hd), *Z32 = (float *)(buf + b_hd + b_h32), *C32 = (float *)(buf + b_hd + b_h32 + b_z);
+  hipLaunchKernelGGL(dbg_diag_kernel, dim3((T + 255) / 256), dim3(256), 0, st, H, ldH, T, hd);
+  hipError_t e = launch_fact_h32(H, ldH, T, hd, H32, st);
+  hipLaunchKernelGGL(dbg_pack_z32_kernel, dim3((unsigned)(((int64_t)nb * zrs + 255) / 256)), dim3(256), 0, st, Z, T, nb,
+                     pz, Z32);
+  if (e == hipSuccess) e = launch_gemm_zrm_f32(H32, ldH, Z32, pz, zrs, C32, T, nb * pz, T, st);
+  hipLaunchKernelGGL(dbg_unpack_hz32_kernel, dim3((unsigned)(((int64_t)T * nb * pz + 255) / 256)), dim3(256), 0, st, C32,
+                     T, nb, pz, out);
+  std::vector<double> hdh(T);
+  if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(buf);
+  if (e != hipSuccess) return 1000 + (int)e;
+  if (hmax_out) *hmax_out = fact_hmax(hdh.data(), T);
+  return 0;
+}

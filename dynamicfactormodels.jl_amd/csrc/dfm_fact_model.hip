@@ -240,6 +240,33 @@ hipError_t launch_gram_fact(const FactBase &fb, const double *FSF, const int32_t
   return hipGetLastError();
 }
 
+// H32 = float(H / hmax), hmax = max_t H[t][t] (fact_hmax: the same number on
+// the host, the max being exact in any order): the fp32 H.Z GEMM's left
+// operand (gemmh_zrm_f32_kernel), a constant of the fit.  H = E E' is
+// positive semidefinite, so |H[s][t]| <= hmax and |H32| <= 1 whatever the
+// panel's scale; H's zero k-padding columns stay zero.  One workgroup per row.
+__global__ __launch_bounds__(256) void fact_h32_kernel(const double *__restrict__ H, int64_t ldH, int T,
+                                                       const double *__restrict__ hd, float *__restrict__ H32) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  double mx = 0.0;
+  for (int s = tid; s < T; s += 256) mx = fmax(mx, hd[s]);
+  red[tid] = mx;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmax(red[tid], red[tid + o]); __syncthreads(); }
+  const double hmax = red[0] > 0.0 ? red[0] : 1.0;
+  for (int64_t c = tid; c < ldH; c += 256) H32[(int64_t)t * ldH + c] = (float)(H[(int64_t)t * ldH + c] / hmax);
+}
+hipError_t launch_fact_h32(const double *H, int64_t ldH, int T, const double *hd, float *H32, hipStream_t st) {
+  hipLaunchKernelGGL(fact_h32_kernel, dim3(T), dim3(256), 0, st, H, ldH, T, hd, H32);
+  return hipGetLastError();
+}
+double fact_hmax(const double *hd_host, int T) {
+  double mx = 0.0;
+  for (int t = 0; t < T; ++t) mx = std::max(mx, hd_host[t]);   // (a NaN entry never wins, as fmax on the device)
+  return mx > 0.0 ? mx : 1.0;
+}
+
 int fact_precompute(const double *Ep, int64_t ld, int T, int N, int r, const double *Lb, const double *Fb,
                     const double *H, int64_t ldH, double *EL, double *S, double *cF, double *hd, hipStream_t st) {
   hipLaunchKernelGGL(fact_pre_kernel, dim3((T + 3) / 4), dim3(256), 0, st, Ep, ld, T, N, r, Lb, Fb, H, ldH,

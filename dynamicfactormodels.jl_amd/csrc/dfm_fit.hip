@@ -105,6 +105,7 @@ int dfm_model_destroy(dfm_model *m) {
   for (double *p : {m->Xp, m->Cp, m->Ep, m->y, m->w, m->F, m->Lall, m->Ub, m->colssr, m->H, m->EL, m->S,
                     m->cF, m->hd, m->FtF, m->FSF, m->Kwk, m->A0wk})
     hipFree(p);
+  hipFree(m->H32);
   for (size_t j = 1; j < m->Ubs.size(); ++j) hipFree(m->Ubs[j]);
   hipFree(m->ws);
   hipFree(m->sd_dev);

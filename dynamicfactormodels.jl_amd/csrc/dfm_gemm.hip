@@ -12,6 +12,8 @@
 // those of the Gram kernel (dfm_gram.hip); grid order is XCD-aware: the row
 // blocks of one column block are issued to one XCD so a B tile is fetched
 // from HBM once and re-read from that XCD's L2.
+// One kernel here is fp32: gemmh_zrm_f32_kernel (v_mfma_f32_32x32x2_f32), the
+// middle products of a warm eigenvalue-rule solve's first filter.
 #include "dfm_internal.h"
 #include <cstdlib>
 
@@ -521,6 +523,148 @@ hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz
   const int ncb8 = (ncb + 7) / 8 * 8;
   hipLaunchKernelGGL(gemmh_zrm_kernel, dim3(nrb * ncb8), dim3(256), 0, st, A, lda, Z, pz, zrs, C, ldc, M, Nc, K, nrb,
                      ncb, col_done, clist, ccount);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// gemmh_zrm_f32_kernel: C32 = H32 Z32 in fp32 (v_mfma_f32_32x32x2_f32) for the
+// middle products of a warm solve's filter-only first step under the
+// eigenvalue rule (round 8; dfm_fact.hip, eig_run_fact2_t: lowp).  H32 is the
+// model's H in float, divided by its largest diagonal entry (|H32| <= 1; lda
+// >= round_up(K, 16), zero k-padding); Z32 and C32 both use the replicate-
+// major 16-row chunk indexing of gemmh_zrm_kernel's Z with float elements
+// (element (s, c) of replicate rep at rep zrs + (s >> 4) 16 pz + 16 c +
+// (s & 15), chunk rows past the matrix zero in Z32, unspecified in C32).
+// 128 x 128 workgroup tile, each wave 64 x 64 as 2 x 2 MFMA tiles (64
+// accumulator VGPRs); 16-deep k stages by LDS-DMA through a 3-deep ring at 3
+// workgroups per CU (16 KB per stage), one barrier per stage as
+// gemmh_zrm_kernel.  Both LDS images are [a][k] with 64-B rows; the 16-B piece
+// q of row a sits at piece q ^ ((a >> 2) & 3), so the ds_read_b128 fragment
+// reads (32 rows x one piece per half-wave) touch 16 distinct 16-B slots in
+// each of the instruction's 16-lane groups.  Lane half h reads k = 8h .. 8h+7
+// of its row in two 16-B pieces and MFMA step e pairs k = e (h = 0) with
+// k = 8 + e (h = 1): a column's sum runs over k in one fixed order whatever
+// its tile, its place in the batch or nb.  The epilogue stores the
+// accumulator's four consecutive rows per register group as one 16-B piece
+// of the column's chunk.  No col_done / clist: every replicate is active in
+// step 0.
+namespace {
+constexpr int F32_GT = 128, F32_KS = 16, F32_STAGE = 2 * F32_GT * F32_KS;   // floats per stage (A + B)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+}  // namespace
+
+__global__ __launch_bounds__(256, 3) void gemmh_zrm_f32_kernel(const float *__restrict__ A, int64_t lda,
+                                                              const float *__restrict__ Z, int pz, int64_t zrs,
+                                                              float *__restrict__ C, int M, int Nc, int K, int nrb,
+                                                              int ncb) {
+  constexpr int NBUF = 3;
+  __shared__ __attribute__((aligned(16))) float lds[NBUF * F32_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
+  const int rb = j % nrb, cb = (j / nrb) * 8 + xcd;
+  if (cb >= ncb) return;
+  const int abase = rb * F32_GT, bbase = cb * F32_GT;
+  const int nst = (K + F32_KS - 1) / F32_KS;
+  // per-lane DMA sources: 16 rows (columns) per instruction, four 16-B pieces
+  // per row, the images' XOR swizzle on the source piece
+  const float *pa[2], *pb[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int a = 16 * (2 * wave + h) + (lane >> 2);
+    const int kq = 4 * ((lane & 3) ^ ((a >> 2) & 3));
+    pa[h] = A + (int64_t)min(abase + a, M - 1) * lda + kq;   // rows past M: finite data, discarded outputs
+    const int xc = min(bbase + a, Nc - 1);                    // columns past Nc likewise
+    const int rep = xc / pz, cc = xc - rep * pz;
+    pb[h] = Z + (int64_t)rep * zrs + 16 * cc + kq;
+  }
+  const int64_t bstep = (int64_t)F32_KS * pz;
+  const int c0 = (2 * wave) * 256, c1 = c0 + 256;
+  auto issue = [&](int s) {
+    float *la = lds + (s % NBUF) * F32_STAGE, *lb = la + F32_GT * F32_KS;
+    __builtin_amdgcn_global_load_lds((gbl_void_t *)pa[0], (lds_void_t *)(la + c0), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void_t *)pb[0], (lds_void_t *)(lb + c0), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void_t *)pa[1], (lds_void_t *)(la + c1), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void_t *)pb[1], (lds_void_t *)(lb + c1), 16, 0, 0);
+    pa[0] += F32_KS; pa[1] += F32_KS; pb[0] += bstep; pb[1] += bstep;
+  };
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[ti][tj][v] = 0.0f;
+  // fragment offsets (floats) inside an image: row r32 of tile t, pieces 2h and 2h + 1
+  const int r32 = lane & 31, hh = lane >> 5;
+  int fo[2][2][2];   // [operand][tile][piece]
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int ra = wr * 64 + 32 * t + r32, rbx = wc * 64 + 32 * t + r32;
+      fo[0][t][q] = ra * F32_KS + 4 * ((2 * hh + q) ^ ((ra >> 2) & 3));
+      fo[1][t][q] = rbx * F32_KS + 4 * ((2 * hh + q) ^ ((rbx >> 2) & 3));
+    }
+  for (int s = 0; s < NBUF - 1 && s < nst; ++s) issue(s);
+  for (int s = 0; s < nst; ++s) {
+    const int ahead = min(NBUF - 2, nst - 1 - s);
+    if (ahead >= 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (s + NBUF - 1 < nst) issue(s + NBUF - 1);
+    const float *la = lds + (s % NBUF) * F32_STAGE, *lb = la + F32_GT * F32_KS;
+    f32x4 af[2][2], bf[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        af[t][q] = *reinterpret_cast<const f32x4 *>(la + fo[0][t][q]);
+        bf[t][q] = *reinterpret_cast<const f32x4 *>(lb + fo[1][t][q]);
+      }
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+          for (int tj = 0; tj < 2; ++tj)
+            acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[ti][q][e], bf[tj][q][e], acc[ti][tj], 0, 0, 0);
+  }
+  // accumulator register v of lane l: row 8 (v >> 2) + 4 (l >> 5) + (v & 3), column l & 31
+#pragma unroll
+  for (int tj = 0; tj < 2; ++tj) {
+    const int x = bbase + wc * 64 + 32 * tj + r32;
+    if (x >= Nc) continue;
+    const int rep = x / pz, cc = x - rep * pz;
+    float *cp = C + (int64_t)rep * zrs + 16 * cc;
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int row = abase + wr * 64 + 32 * ti + 8 * g + 4 * hh;
+        if (row < M)   // (rows row .. row + 3 stay inside the chunk: its pad rows take discarded values)
+          *reinterpret_cast<f32x4 *>(cp + (int64_t)(row >> 4) * (16 * pz) + (row & 15)) =
+              f32x4{acc[ti][tj][4 * g], acc[ti][tj][4 * g + 1], acc[ti][tj][4 * g + 2], acc[ti][tj][4 * g + 3]};
+      }
+  }
+}
+
+// H32 (M x K floats, lda >= round_up(K, 16), zero k-padding) times the
+// replicate-major chunked Z32 of nb = Nc / pz replicates -> C32 in the same
+// chunk layout (gemmh_zrm_f32_kernel); zrs = round_up(K, 16) pz = round_up(M, 16) pz
+hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int pz, int64_t zrs, float *C, int M,
+                               int Nc, int K, hipStream_t st) {
+  const int64_t kpad = (K + F32_KS - 1) / F32_KS * F32_KS;
+  if (M < 1 || lda < kpad || (lda & 3) || pz < 1 || Nc < pz || Nc % pz || M != K || zrs < kpad * pz || (zrs & 3))
+    return hipErrorInvalidValue;
+  const int nrb = (M + F32_GT - 1) / F32_GT, ncb = (Nc + F32_GT - 1) / F32_GT;
+  const int ncb8 = (ncb + 7) / 8 * 8;
+  hipLaunchKernelGGL(gemmh_zrm_f32_kernel, dim3(nrb * ncb8), dim3(256), 0, st, A, lda, Z, pz, zrs, C, M, Nc, K, nrb,
+                     ncb);
   return hipGetLastError();
 }
 

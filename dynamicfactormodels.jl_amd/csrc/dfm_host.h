@@ -41,6 +41,7 @@ struct dfm_ctx {
   double ms[DFM_KC_COUNT] = {};
   int64_t launches[DFM_KC_COUNT] = {};
   int64_t eig_batches = 0, eig_iters = 0, eig_iters_max = 0, rep_iters = 0, gemm_products = 0;
+  int64_t gemm_products_f32 = 0;   // of the factored solver's replicate-products, those run in fp32 (host-counted)
   // factored runs accumulate {replicate-iterations, GEMM replicate-products}
   // here on the device (no host sync after the eigen loop); read on query
   long long *cnt_dev = nullptr;
@@ -142,6 +143,8 @@ struct dfm_model {
   int64_t ldH = 0;
   double *H = nullptr, *EL = nullptr, *S = nullptr, *cF = nullptr, *hd = nullptr;
   double *FtF = nullptr;   // F'F (16 x 16): the factored solver's middle Horner steps
+  float *H32 = nullptr;    // float(H / hmax) (T x ldH): the fp32 middle products of warm eigenvalue-rule solves
+  double hmax = 0.0;       // max_t H[t][t]
   double *FSF = nullptr;   // F S F' (T x ldH): the direct path's identity-based replicate Grams
   // T >= N bootstrap Grams by one weighted-outer-product GEMM (gram_wk_*):
   // K = [E_s' E_s] lower-triangle pairs (Tp x ldk) and A0 = C'C (N x N)

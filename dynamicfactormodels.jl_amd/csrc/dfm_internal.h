@@ -17,6 +17,10 @@ struct FactBase {   // passed by value into the factored kernels
   int64_t ldH;
   const double *F, *EL, *S, *H, *cF, *hd;   // T x r, T x r, r x r, T x ldH, T, T
   const double *FtF = nullptr;   // F'F (16 x 16) when the model holds it (else computed per solve)
+  // H / hmax in float (T x ldH, zero k-padding), hmax = max_t H[t][t] (H is positive semidefinite: |H32| <= 1), for
+  // the fp32 middle products of a warm eigenvalue-rule solve (gemmh_zrm_f32_kernel); nullptr: those stay fp64
+  const float *H32 = nullptr;
+  double hmax = 0.0;
 };
 
 // ---- dfm_ctx.hip
@@ -44,6 +48,8 @@ hipError_t launch_gram_wk(const double *Ep, int64_t ld, int T, int N, int r, con
 hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz, int64_t zrs, double *C,
                            int64_t ldc, int M, int Nc, int K, hipStream_t st, const int *col_done, const int *clist,
                            const int *ccount);
+hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int pz, int64_t zrs, float *C, int M,
+                               int Nc, int K, hipStream_t st);
 hipError_t launch_gemm_loadings(const double *Eaug, int64_t lda, const double *ZF, int Kp, int rp, int N, int nrep,
                                 int K, int r, double invT, double *Lout, hipStream_t st);
 int gram_dma_slots(int m);
@@ -62,6 +68,7 @@ size_t eig_workspace_bytes_padded(int m, int nb, int P, int maxit);
 extern thread_local int g_last_iters;   // per host thread: dfm_bootstrap_multi's shards run concurrently
 extern thread_local int64_t g_last_rep_iters;
 extern thread_local int64_t g_last_gemm_products;
+extern thread_local int64_t g_last_gemm_products_f32;   // of those, the fp32 ones (factored solver, host-counted)
 int eig_block_p(int m, int k, int req);
 int fact_block_p(int m, int k, int req);
 // What both solvers take besides the matrix.  Callers fill the members by name.
@@ -108,6 +115,8 @@ hipError_t launch_gram_fact(const FactBase &fb, const double *FSF, const int32_t
                             double *G, int64_t ldg, int64_t strideG, hipStream_t st);
 int fact_precompute(const double *Ep, int64_t ld, int T, int N, int r, const double *Lb, const double *Fb,
                     const double *H, int64_t ldH, double *EL, double *S, double *cF, double *hd, hipStream_t st);
+hipError_t launch_fact_h32(const double *H, int64_t ldH, int T, const double *hd, float *H32, hipStream_t st);
+double fact_hmax(const double *hd_host, int T);
 
 // ---- dfm_model.hip
 __global__ void panel_from_colmajor_kernel(const double *__restrict__ X, int64_t ldx, int T, int N,

@@ -111,6 +111,10 @@ int dfm_ctx_eig_stats(dfm_ctx *ctx, int64_t *batches, int64_t *iters_total, int6
  * last reset (two per Rayleigh-Ritz iteration with the Chebyshev filter):
  * the GEMM's algorithmic work is 2 T^2 p per product. */
 int dfm_ctx_gemm_products(dfm_ctx *ctx, int64_t *products);
+/* Of those replicate-products, the ones run in fp32: the middle products of a
+ * warm eigenvalue-rule solve's filter-only first step ((d0 - 1) nb per solve;
+ * 0 under the strict rule or with DFM_FACT_F32=0). */
+int dfm_ctx_gemm_products_f32(dfm_ctx *ctx, int64_t *products);
 int dfm_ctx_rep_iters(dfm_ctx *ctx, int64_t *rep_iters);
 const char *dfm_kernel_class_name(int cls);
 

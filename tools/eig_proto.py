@@ -19,7 +19,12 @@ Environment: P (block), SHAPE=c1|c2|small (small: T = 120, N = 300, R = 8),
 R, TOL, STRICT=1, JACOBI=n (model eig_small's n threshold-Jacobi sweeps per
 Rayleigh-Ritz step instead of LAPACK's eigh; JACOBI_FIRST: the sweeps of the
 f / g schedules' first Rayleigh-Ritz step, which no earlier step has
-pre-rotated)."""
+pre-rotated); F32=n (f / g schedules): the first n products of the filter-only
+step 0 apply the idiosyncratic part E* E*' of G* = (G* - E* E*') + E* E*' as
+float32(E* E*') @ float32(S) (sgemm, fp32 accumulation) — the GPU's fp32
+middle products, which round H and Z and keep the factor part in fp64;
+NOISE=x: Gaussian noise of x 6e-8 ||column|| / sqrt(T) per entry added to that
+part (the margin over fp32 rounding)."""
 import os
 import sys
 
@@ -33,6 +38,8 @@ T, N, R = 500, 2000, 8
 P = int(os.environ.get("P", "16"))
 JACOBI = int(os.environ.get("JACOBI", "0"))
 JACOBI_FIRST = int(os.environ.get("JACOBI_FIRST", str(JACOBI)))   # f / g: sweeps of the first Rayleigh-Ritz step
+F32 = int(os.environ.get("F32", "0"))          # f / g: step 0's first F32 products with the E* E*' part in float32
+NOISE = float(os.environ.get("NOISE", "0"))    # ... plus this many times fp32's rounding noise
 
 
 def shifted_cheb(d):
@@ -87,7 +94,15 @@ def colcond(Q):
     return np.linalg.cond(Q / np.linalg.norm(Q, axis=0))
 
 
-def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False, bfix=0.0):
+def lowp_product(G, Hs, S, nrng):
+    """G S with the part Hs S (Hs = E* E*') in float32: rounded operands, fp32 accumulation, optional noise."""
+    W = (Hs.astype(np.float32) @ S.astype(np.float32)).astype(np.float64)
+    if NOISE > 0.0:
+        W = W + nrng.standard_normal(W.shape) * (NOISE * 6e-8 * np.linalg.norm(W, axis=0) / np.sqrt(W.shape[0]))
+    return (G - Hs) @ S + W
+
+
+def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False, bfix=0.0, Hs=None, nrng=None):
     """-> (loop steps, products, Rayleigh-Ritz steps, theta[:k] at retirement, cond after the first filter,
     theta_p / theta_k of a Rayleigh-Ritz step on the start block: filter_end's guard branch binds when it exceeds beta)"""
     Q = Q0.copy()
@@ -100,7 +115,8 @@ def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False, bfix=0.
         a = shifted_cheb(degs[0])
         S = a[degs[0]] * Q0
         for i in range(degs[0] - 1, -1, -1):
-            S = G @ S / bfix + a[i] * Q0
+            low = Hs is not None and prods < F32
+            S = (lowp_product(G, Hs, S, nrng) if low else G @ S) / bfix + a[i] * Q0
             prods += 1
         Q = S
         it0 = 1
@@ -200,12 +216,13 @@ def main():
     hrng = np.random.default_rng(5)
     rnd = hrng.uniform(-1, 1, size=(T, P))
 
-    def gram(b):
+    def gram(b):   # -> G*, and E* E*' (the part the GPU's fp32 products apply) where F32 asks for it
         if c2:   # rows of the T x N panel are columns here
             Xs = C + eta[b][None, :] * E[:, idx[b]]
-        else:
-            Xs = C + eta[b][:, None] * E[idx[b]]
-        return Xs @ Xs.T
+            return Xs @ Xs.T, None
+        Es = eta[b][:, None] * E[idx[b]]
+        Xs = C + Es
+        return Xs @ Xs.T, (Es @ Es.T if F32 > 0 else None)
 
     truth = {}
     for sc in scheds:
@@ -227,12 +244,13 @@ def main():
             Q0 = np.hstack([W, Gd])
         its, prs, rrs, errs, conds, grs, fails = [], [], [], [], [], [], 0
         for b in range(nrep):
-            G = gram(b)
+            G, Hs = gram(b)
             if b not in truth:
                 truth[b] = np.linalg.eigvalsh(G)[::-1][:R]
             try:
                 n, pr, rr, th, cond, gr = solve(G, Q0, degs, k=R, beta=beta, strict=strict, bfix=bfix,
-                                            tol=float(os.environ.get("TOL", "1e-12")))
+                                            tol=float(os.environ.get("TOL", "1e-12")), Hs=Hs,
+                                            nrng=np.random.default_rng(77_000 + b))
             except np.linalg.LinAlgError:   # a Gram matrix that is not positive definite
                 fails += 1
                 continue
