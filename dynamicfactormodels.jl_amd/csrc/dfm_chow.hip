@@ -244,9 +244,6 @@ __global__ __launch_bounds__(256, (chow_waves<R, KS>())) void chow_all_kernel(Pa
   const double *Pc = prep + (size_t)(ok ? rep : rep0) * CP_NMAT * R * R;
   auto PM = [&](int m, int a, int c) -> double { return Pc[m * R * R + a * R + c]; };
   auto stage = [&](int t0) {
-#ifdef DFM_CH_DIAG_NOSTAGE   // (timing diagnostic, WRONG results: tile 0 staged once and reused)
-    if (t0 > 0) return;
-#endif
     for (int e = tid; e < nrw * TR * R; e += nth) {
       const int q = e / (TR * R), f = e % (TR * R), rr = f / R, j = f % R, t = t0 + rr;
       const int64_t base = (int64_t)(rep0 + q) * T * r;
@@ -283,9 +280,6 @@ __global__ __launch_bounds__(256, (chow_waves<R, KS>())) void chow_all_kernel(Pa
     }
 #pragma unroll
     for (int u = 0; u < CU; ++u) {
-#ifdef DFM_CH_DIAG_NOLOAD   // (timing diagnostic, WRONG results: no gathered loads)
-      ee[u] = (double)(ro[u] & 7); if (HAS_C) cc[u] = 0.5 * u;
-#endif
       double x = ee[u];
       if (HAS_ETA) x *= sE[lr][min(rb + KS * u, tn - 1)];
       if (HAS_C) x += cc[u];
@@ -630,19 +624,11 @@ hipError_t launch_chow(int orient, const PanelSrc &src, int T, int N, int r, int
   double *prep = (double *)ws;
   double *Z = (double *)(ws + (size_t)nb * CH_PREP_BYTES);
   double *scr = (double *)(ws + ws_bytes) - (size_t)3 * nb * N;
-#ifdef DFM_CH_R3   // (A/B builds: r = 3 runs exactly 3-wide; bit-identical, profiles/r05_rejected_chow_r3.txt)
-  const int RC = r == 3 ? 3 : (r <= 4 ? 4 : (r <= 8 ? 8 : 16));
-#else
   const int RC = r <= 4 ? 4 : (r <= 8 ? 8 : 16);   // the main kernel's padded R (below)
-#endif
   hipLaunchKernelGGL(chow_prep_kernel, dim3(nb), dim3(256), 0, st, F, T, r, bp, RC, prep, Z);
   double *LR = scr, *LM = scr + (size_t)nb * N, *WD = scr + (size_t)2 * nb * N;
   // R = padded factor count of the per-variable register blocks (zero
   // padding: r <= 4 runs 4-wide, 10 HC0 accumulators instead of 36)
-#ifdef DFM_CH_R3
-  if (r == 3) launch_chow_r<3>(src, blk, T, N, r, bp, nb, F, Z, prep, Lm, LR, LM, WD, LRo, LMo, WDo, out_stride, st);
-  else
-#endif
   if (r <= 4) launch_chow_r<4>(src, blk, T, N, r, bp, nb, F, Z, prep, Lm, LR, LM, WD, LRo, LMo, WDo, out_stride, st);
   else if (r <= 8) launch_chow_r<8>(src, blk, T, N, r, bp, nb, F, Z, prep, Lm, LR, LM, WD, LRo, LMo, WDo, out_stride, st);
   else launch_chow_r<16>(src, blk, T, N, r, bp, nb, F, Z, prep, Lm, LR, LM, WD, LRo, LMo, WDo, out_stride, st);

@@ -33,6 +33,20 @@ DFM_DEV double mfma4(double a, double b, double c) {
   return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
 }
 
+// Transpose-reduce of the four v_mfma_f64_4x4x4_4b blocks of accumulators
+// a[fb] (column block fb): the lane gets the 4 x 16 result's element
+// (row lane >> 4, column lane & 15).
+DFM_DEV double mm4_fold(const double (&a)[4], int lane) {
+  const int b1 = (lane >> 2) & 1, b2 = (lane >> 3) & 1;
+  const double k01 = (b1 ? a[1] : a[0]) + __shfl_xor(b1 ? a[0] : a[1], 4);
+  const double k23 = (b1 ? a[3] : a[2]) + __shfl_xor(b1 ? a[2] : a[3], 4);
+  return (b2 ? k23 : k01) + __shfl_xor(b2 ? k01 : k23, 8);
+}
+DFM_DEV double mm4_fold(double a0, double a1, double a2, double a3, int lane) {
+  const double a[4] = {a0, a1, a2, a3};
+  return mm4_fold(a, lane);
+}
+
 // v_mfma_f64_16x16x4: A[i][k] at lane i + 16k, B[k][j] at lane j + 16k,
 // C[row][col] at lane col + 16 (row % 4), register row / 4 (tools/mfma16_layout.hip).
 typedef double dv4 __attribute__((ext_vector_type(4)));

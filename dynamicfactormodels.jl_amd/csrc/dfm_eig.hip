@@ -217,6 +217,8 @@ __global__ __launch_bounds__(256) void eig_gq_kernel(const double *__restrict__ 
     __syncthreads();
   }
   // transpose-reduce, write Y (global + LDS)
+  // (mm4_fold written out here and in eig_cheb_kernel: through the helper
+  // these kernels' instruction streams change)
   const int b1 = (lane >> 2) & 1, b2 = (lane >> 3) & 1, blk = (lane >> 2) & 3;
   const int oi = lane >> 4, oj = lane & 3;
   double *Yr = w.Y + (int64_t)rep * m * P;
@@ -943,16 +945,6 @@ DFM_DEV int fz_opaque(int x) { asm volatile("" : "+v"(x)); return x; }
 
 DFM_DEV int fz_ix(int r, int c) { return (r << 4) | ((((c >> 2) ^ ((r >> 1) & 3)) << 2) | (c & 3)); }
 
-// Transpose-reduce of the four v_mfma_f64_4x4x4_4b blocks of accumulators
-// a[fb] (column block fb): the lane gets the 4 x 16 result's element
-// (row lane >> 4, column lane & 15).
-DFM_DEV double mm4_fold(const double (&a)[4], int lane) {
-  const int b1 = (lane >> 2) & 1, b2 = (lane >> 3) & 1;
-  const double k01 = (b1 ? a[1] : a[0]) + __shfl_xor(b1 ? a[0] : a[1], 4);
-  const double k23 = (b1 ? a[3] : a[2]) + __shfl_xor(b1 ? a[2] : a[3], 4);
-  return (b2 ? k23 : k01) + __shfl_xor(b2 ? k01 : k23, 8);
-}
-
 // acc[q] = rows of 4-row group g = wave + NW q (NW waves share the rows) of G S (G: m x m in global, S:
 // the LDS image, rows m..mpad-1 zero).  Lane: row 4 g + (lane & 3), k index
 // k0 + 4 (lane >> 4) + ((lane >> 2) & 3) — a G row's 16 k values per chunk are
@@ -1318,10 +1310,7 @@ static int eig_run_t(const double *G, int64_t ldg, int64_t strideG, int m, const
       ChebCo cc;
       shifted_cheb(kChebDirectStrict, cc.c4);
       shifted_cheb(2, cc.c2);
-      size_t lds = (size_t)2 * ((m + 15) & ~15) * P * sizeof(double);
-#ifdef DFM_FUSED_PAD   // (A/B builds: extra dynamic LDS -> fewer resident workgroups per CU)
-      lds += DFM_FUSED_PAD;
-#endif
+      const size_t lds = (size_t)2 * ((m + 15) & ~15) * P * sizeof(double);
       // DFM_EIG_PROF=1: phase profile of replicate 0 of every fused solve -> stderr
       static const bool want_prof = [] { const char *e = getenv("DFM_EIG_PROF"); return e && atoi(e) != 0; }();
       long long *prof = nullptr;

@@ -135,6 +135,8 @@ __global__ __launch_bounds__(256, 2) void gram_kernel(PanelSrc src, int m, int K
     }
   };
 
+  // (this kernel keeps its own copy of dfm_tile.h's k step and epilogue: on
+  // the shared ones its short C2 launch measured 1.2 % slower, profiles/r09_tile_ab.txt section 4)
   double acc[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
@@ -656,7 +658,7 @@ hipError_t launch_gram_wk(const double *Ep, int64_t ld, int T, int N, int r, con
     hipLaunchKernelGGL(gram_wk_b_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, At, Tp, Ep, ld, T, N,
                        rows, nch, Bo);
   }
-  hipError_t e = launch_gemm(false, W, Tp, K, ldk, Q, ldk, nb, (int)ldk, T, st, nullptr, 1, true, nullptr, nullptr);
+  hipError_t e = launch_gemm(W, Tp, K, ldk, Q, ldk, nb, (int)ldk, T, st);   // W, K zero-padded to Tp
   if (e != hipSuccess) return e;
   const int nt = (N + WK_TILE - 1) / WK_TILE;
   hipLaunchKernelGGL(gram_wk_combine_kernel, dim3(nt * (nt + 1) / 2, nb), dim3(256), 0, st, A0, L, Bo, Q, ldk, N, r,

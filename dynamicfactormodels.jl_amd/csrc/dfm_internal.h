@@ -55,10 +55,8 @@ hipError_t launch_gemm_loadings(const double *Eaug, int64_t lda, const double *Z
 int gram_dma_slots(int m);
 hipError_t launch_gram_dma(const double *X, int64_t ld, int m, int K, int S, int ksteps, double *G, int64_t ldg,
                            int64_t strideZ, hipStream_t st, double alpha);
-hipError_t launch_gemm(bool a_trans, const double *A, int64_t lda, const double *B, int64_t ldb,
-                       double *C, int64_t ldc, int M, int Nc, int K, hipStream_t st,
-                       const int *col_done = nullptr, int col_group = 1, bool b_padded = false,
-                       const int *clist = nullptr, const int *ccount = nullptr);
+hipError_t launch_gemm(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M,
+                       int Nc, int K, hipStream_t st);
 
 // ---- dfm_eig.hip (the explicit-Gram top-k solver)
 __global__ void eig_trace_kernel(const double *__restrict__ G, int64_t ldg, int64_t strideG, int m,

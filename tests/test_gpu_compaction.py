@@ -1,6 +1,6 @@
 """The factored bootstrap's straggler phase (once a poll finds < 1/8 of the
 batch active, the H.Z GEMMs tile only the listed stragglers' column groups,
-dfm_fact.hip active_list_kernel + launch_gemm clist) must not change a single
+dfm_fact.hip active_list_kernel + launch_gemm_zrm clist) must not change a single
 bit of any replicate's statistics.  A C3-shaped 512-replicate job (whose
 slowest replicates finish in the compacted phase) is compared with the same
 slowest replicates run as a batch of their own, where every one of them is

@@ -126,7 +126,7 @@ def c2(D, ctx, args):
     gms, gn = tm.get("gram", (0.0, 0))
     if gn:
         flop = B * (args.reps + 1) * N * (N + 1) * T
-        rec["roofline_gram"] = {"kernel": "gram_wk: prep (w, B = F'DPE) + ONE batch GEMM Q = W K on gemmh_kernel_t "
+        rec["roofline_gram"] = {"kernel": "gram_wk: prep (w, B = F'DPE) + ONE batch GEMM Q = W K on gemmh_kernel "
                                           "(v_mfma_f64_4x4x4_4b) + tiled symmetric combine",
                                 "bound": "mfma", "achieved": round(flop / (gms * 1e-3) / 1e12, 3), "peak": 78.6,
                                 "unit": "TFLOP/s", "frac": round(flop / (gms * 1e-3) / 1e12 / 78.6, 4),
