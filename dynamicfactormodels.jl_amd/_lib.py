@@ -84,6 +84,8 @@ SIGNATURES = [
     ("dfm_model_fact_block", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("dfm_chow_all", C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, c_double_p]),
     ("dfm_chow", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p]),
+    ("dfm_chow_sweep", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_double_p, c_double_p, c_double_p,
+                                 c_double_p, c_int64_p]),
     ("dfm_model_criterion", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     ("dfm_get_factors", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_double_p]),
     ("dfm_predict", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_double_p]),

@@ -189,6 +189,20 @@ class Stat:
     def Wald_all(break_period: int):
         return Stat(11, break_period)
 
+    # sup over the break periods lo..hi (0-based rows, inclusive) of the
+    # statistic of every variable: N values per replicate (dfm_chow_sweep)
+    @staticmethod
+    def supLR_all(lo: int, hi: int):
+        return Stat(15, int(lo), int(hi))
+
+    @staticmethod
+    def supLM_all(lo: int, hi: int):
+        return Stat(16, int(lo), int(hi))
+
+    @staticmethod
+    def supWald_all(lo: int, hi: int):
+        return Stat(17, int(lo), int(hi))
+
     @staticmethod
     def iterations():             # diagnostic: the replicate's eigensolver steps
         return Stat(12)
@@ -782,6 +796,70 @@ def LM_test(dfm, break_period: int, variable_index: int) -> float:
 def Wald_test(dfm, break_period: int, variable_index: int) -> float:
     """``src/chowtest.jl:25-33``."""
     return float(_chow_one(dfm, break_period, variable_index)[2])
+
+
+# ------------------------------------------------------ sup-Chow tests
+SUP_CHOW_STATS = ("LR", "LM", "Wald")
+
+
+def sup_chow_range(T: int, r: int, trim: float = 0.15, lo: Optional[int] = None, hi: Optional[int] = None):
+    """The trimmed range of candidate break periods (Andrews 1993): ``lo =
+    max(ceil(trim T), 2 r)``, ``hi = min(floor((1 - trim) T), T - 2 r)``,
+    either overridden by the caller's."""
+    if lo is None:
+        lo = max(int(math.ceil(trim * T)), 2 * r)
+    if hi is None:
+        hi = min(int(math.floor((1.0 - trim) * T)), T - 2 * r)
+    return int(lo), int(hi)
+
+
+@dataclass
+class ChowSweepResult:
+    """``sup[s]`` / ``argsup[s]`` (N-vectors; ``s`` in ``"LR"``, ``"LM"``,
+    ``"Wald"``; argsup = the 0-based break period of the first maximum) over the
+    break periods ``lo..hi``; ``curves[s]`` ((hi - lo + 1) x N) when asked for."""
+    lo: int
+    hi: int
+    sup: dict
+    argsup: dict
+    curves: Optional[dict] = None
+
+
+def chow_sweep(dfm: DynamicFactorModelResult, lo: Optional[int] = None, hi: Optional[int] = None,
+               trim: float = 0.15, curves: bool = False, stats: Sequence[str] = SUP_CHOW_STATS) -> ChowSweepResult:
+    """sup-LR / sup-LM / sup-Wald of Breitung–Eickmeier (2011) for every variable
+    over the candidate break periods ``lo..hi`` (default: the ``trim``-trimmed
+    range), in one device pass (``dfm_chow_sweep``).  ``stats`` selects the
+    statistics computed: the sup-LM alone costs no Wald work."""
+    ctx = dfm._ctx
+    T, N = dfm.x.shape
+    lo, hi = sup_chow_range(T, dfm.number_of_factors, trim, lo, hi)
+    names = [s for s in SUP_CHOW_STATS if s in stats]
+    if not names or len(names) != len(list(stats)):
+        raise ValueError(f"stats must be chosen from {SUP_CHOW_STATS}")
+    mask = sum(1 << SUP_CHOW_STATS.index(s) for s in names)
+    nbp = max(hi - lo + 1, 0)
+    cur = {s: np.zeros((nbp, N)) for s in names} if curves else {}
+    sup = np.zeros((3, N))
+    arg = np.zeros((3, N), dtype=np.int64)
+    cp = [_lib.ptr(cur[s]) if s in cur else None for s in SUP_CHOW_STATS]
+    ctx.check(ctx.lib.dfm_chow_sweep(dfm.handle, lo, hi, mask, cp[0], cp[1], cp[2], _lib.ptr(sup),
+                                     arg.ctypes.data_as(_lib.c_int64_p)))
+    k = {s: SUP_CHOW_STATS.index(s) for s in names}
+    return ChowSweepResult(lo, hi, {s: sup[k[s]].copy() for s in names}, {s: arg[k[s]].copy() for s in names},
+                           cur if curves else None)
+
+
+def sup_chow_pvalues(observed, replicates) -> np.ndarray:
+    """Bootstrap p-values of sup statistics: per variable, the share of the B
+    replicates (rows of ``replicates``, B x N) whose sup is >= the observed one
+    (N).  Host arithmetic; the critical values of a sup over break dates are
+    non-standard (Andrews 1993), hence the bootstrap."""
+    obs = np.asarray(observed, dtype=np.float64)
+    rep = np.asarray(replicates, dtype=np.float64)
+    if rep.ndim != 2 or obs.shape != (rep.shape[1],):
+        raise ValueError("observed must be (N,), replicates (B, N)")
+    return np.mean(rep >= obs[None, :], axis=0)
 
 
 # ------------------------------------------------------- targeted predictors

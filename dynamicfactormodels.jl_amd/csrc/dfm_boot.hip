@@ -181,7 +181,7 @@ static int lane_count(const dfm_model *M, int64_t B, const dfm_stat *stats, int 
   const int p = eig_block_p(M->m, M->r, M->ctx->block);
   if (p > 32 || p < M->r) return 1;
   for (int i = 0; i < ns; ++i)
-    if (stats[i].kind < 0 || stats[i].kind > DFM_STAT_LOADINGS) return 1;
+    if (stats[i].kind < 0 || stats[i].kind > DFM_STAT_SUPWALD_ALL) return 1;
   if (M->r > 16) return 1;   // the subspace solver's paths (not the dense / GEMM-built wide ones)
   if (forced > 0) return std::min(forced, dfm_model::kMaxLanes);
   return 2;
@@ -294,11 +294,11 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
   // stat descriptors
   std::vector<StatDesc> sd(ns);
   int64_t width = 0;
-  bool chow = false, pcp = false;
-  int chow_bp = -1;
+  bool chow = false, pcp = false, sup = false;
+  int chow_bp = -1, sup_lo = -1, sup_hi = -1;
   for (int i = 0; i < ns; ++i) {
     const dfm_stat s = stats[i];
-    if (s.kind < 0 || s.kind > DFM_STAT_LOADINGS) return fail(ctx, -6, "unknown stat kind %d", s.kind);
+    if (s.kind < 0 || s.kind > DFM_STAT_SUPWALD_ALL) return fail(ctx, -6, "unknown stat kind %d", s.kind);
     if (s.kind == DFM_STAT_LOADINGS && (s.arg0 < 0 || s.arg0 >= M->nblk))
       return fail(ctx, -6, "loadings of break block %d outside 0..%d", s.arg0, M->nblk - 1);
     if (s.kind == DFM_STAT_CRIT) {
@@ -316,6 +316,14 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
       if (M->nblk > 64) return fail(ctx, -7, "Chow statistics support at most 64 break blocks");
       chow = true; chow_bp = s.arg0;
       if (s.kind <= DFM_STAT_WALD && (s.arg1 < 0 || s.arg1 >= N)) return fail(ctx, -7, "variable index");
+    }
+    if (sup_stat(s.kind)) {
+      if (s.arg0 > s.arg1 || s.arg0 < r || s.arg1 > T - r)
+        return fail(ctx, -7, "break period range %d..%d outside %d..%d", s.arg0, s.arg1, r, T - r);
+      if (sup && (s.arg0 != sup_lo || s.arg1 != sup_hi)) return fail(ctx, -7, "one break period range per call");
+      if (M->nblk > 1) return fail(ctx, -7, "sup-Chow statistics need a model fitted without breaks");
+      if (r > 16) return fail(ctx, -7, "sup-Chow statistics support r <= 16 (r = %d)", r);
+      sup = true; sup_lo = s.arg0; sup_hi = s.arg1;
     }
     sd[i] = {s.kind, s.arg0, s.arg1, (int)width};
     width += stat_width(M, s.kind);
@@ -341,7 +349,7 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
     const int kd = stats[i].kind;
     subspace_only = subspace_only && (kd == DFM_STAT_V || kd == DFM_STAT_CRIT || kd == DFM_STAT_EIGVAL ||
                                       kd == DFM_STAT_TRACE || kd == DFM_STAT_ITERS || chow_stat(kd) ||
-                                      ((kd == DFM_STAT_COEF || kd == DFM_STAT_TSTAT) && stats[i].arg0 < q));
+                                      sup_stat(kd) || ((kd == DFM_STAT_COEF || kd == DFM_STAT_TSTAT) && stats[i].arg0 < q));
   }
   const int esub = (subspace_only && !values_only) ? 1 : 0;
   // Fields the statistics read (demand-driven, as the stopping rule above):
@@ -353,8 +361,8 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
   for (int i = 0; i < ns; ++i) {
     const int kd = stats[i].kind;
     need_ols = need_ols || kd == DFM_STAT_COEF || kd == DFM_STAT_TSTAT;
-    need_fl = need_fl || kd == DFM_STAT_COEF || kd == DFM_STAT_TSTAT || chow_stat(kd) || kd == DFM_STAT_FACTORS ||
-              kd == DFM_STAT_LOADINGS;
+    need_fl = need_fl || kd == DFM_STAT_COEF || kd == DFM_STAT_TSTAT || chow_stat(kd) || sup_stat(kd) ||
+              kd == DFM_STAT_FACTORS || kd == DFM_STAT_LOADINGS;
   }
   const int p = eig_block_p(m, r, ctx->block);
   // r beyond the subspace eigensolver's block: dense batched eigenpairs,
@@ -478,6 +486,15 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
   // PCp: the unrestricted full-sample Gram of every replicate (no breaks,
   // src/criteria.jl:18), its spectrum, sigma^2 per replicate
   DevBuf pG, pEv, pWk, pSig, wDe, wX, wOls, wCh, wSc;
+  // the sweep's own workspace, bounded by the replicates per sweep launch (not M->ws, which scales with the batch)
+  const size_t sw_bytes = sup ? chow_sweep_workspace_bytes(T, N, r, sup_hi - sup_lo + 1, (int)nb) : 0;
+  if (sw_bytes > M->sw_bytes) {
+    hipFree(M->sw_ws);
+    M->sw_ws = nullptr; M->sw_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&M->sw_ws, sw_bytes));
+    DFM_POISON_SYNC(M->sw_ws, sw_bytes);
+    M->sw_bytes = sw_bytes;
+  }
   if (wide) {
     HIPCHK(ctx, dalloc(&wDe.p, (size_t)nb * dense_eig_work(m, r)));
     if (q + r > 32) HIPCHK(ctx, dalloc(&wOls.p, (size_t)nb * ols_wide_work(T, q + r)));
@@ -692,6 +709,14 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
                                      scr + ((size_t)which * n) * N + sd[i].arg1, (size_t)N * 8, 8, n,
                                      hipMemcpyDeviceToDevice, st));
       }
+    }
+    if (sup) {   // sup over bp of every wanted statistic, written into the caller's rows (timed per kernel)
+      ChowSweepOut so;
+      so.os = width;
+      for (int i = 0; i < ns; ++i)
+        if (sup_stat(sd[i].kind)) so.sup[sd[i].kind - DFM_STAT_SUPLR_ALL] = out + b0 * width + sd[i].off;
+      HIPCHK(ctx, launch_chow_sweep(src, T, N, r, sup_lo, sup_hi, n, w.F, w.L, so, M->sw_ws, sw_bytes, st,
+                                    timer_cb, ctx));
     }
   }
   // the status flag through the context's pinned slot (a pageable read-back

@@ -108,6 +108,7 @@ int dfm_model_destroy(dfm_model *m) {
   hipFree(m->H32);
   for (size_t j = 1; j < m->Ubs.size(); ++j) hipFree(m->Ubs[j]);
   hipFree(m->ws);
+  hipFree(m->sw_ws);
   hipFree(m->sd_dev);
   hipFree(m->flag_dev);
   dfm_ctx *ctx = m->ctx;
@@ -715,6 +716,67 @@ int dfm_chow_all(dfm_model *M, int64_t bp, double *LR, double *LM, double *Wald)
     if (outs[i]) HIPCHK(ctx, hipMemcpyAsync(outs[i], scr + (size_t)i * M->N, (size_t)M->N * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   hipFree(ws);
+  return 0;
+}
+
+// Every break period bp_lo..bp_hi in one device pass (dfm_chow_sweep.hip).
+int dfm_chow_sweep(dfm_model *M, int64_t bp_lo, int64_t bp_hi, int stats, double *LR, double *LM, double *Wald,
+                   double *sup, int64_t *argsup) {
+  if (!M) return -1;
+  dfm_ctx *ctx = M->ctx;
+  if (bp_lo > bp_hi || bp_lo < M->r || bp_hi > M->T - M->r)
+    return fail(ctx, -7, "break period range %lld..%lld outside %d..%d", (long long)bp_lo, (long long)bp_hi, M->r,
+                M->T - M->r);
+  if (M->nblk > 1) return fail(ctx, -7, "dfm_chow_sweep needs a model fitted without breaks");
+  if (M->r > 16) return fail(ctx, -7, "dfm_chow_sweep supports r <= 16 (r = %d)", M->r);
+  if (stats < 0 || stats > 7) return fail(ctx, -2, "dfm_chow_sweep: stats mask %d", stats);
+  if (stats == 0) stats = 7;
+  DeviceShare gate(ctx->device);
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const int N = M->N, nbp = (int)(bp_hi - bp_lo + 1);
+  double *curves[3] = {LR, LM, Wald};
+  const bool red = sup || argsup;
+  DevBuf dcur, dsup;
+  int64_t *darg = nullptr;
+  ChowSweepOut so;
+  so.os = N;
+  int ncur = 0;
+  for (int s = 0; s < 3; ++s) ncur += curves[s] ? 1 : 0;
+  if (ncur) HIPCHK(ctx, dalloc(&dcur.p, (size_t)ncur * nbp * N));
+  if (sup) HIPCHK(ctx, dalloc(&dsup.p, (size_t)3 * N));
+  if (argsup) HIPCHK(ctx, dalloc(&darg, (size_t)3 * N));
+  for (int s = 0, c = 0; s < 3; ++s) {
+    if (curves[s]) so.curve[s] = dcur.p + (size_t)(c++) * nbp * N;
+    if (red && (stats >> s & 1)) {
+      if (sup) so.sup[s] = dsup.p + (size_t)s * N;
+      if (argsup) so.argsup[s] = darg + (size_t)s * N;
+    }
+  }
+  const size_t bytes = chow_sweep_workspace_bytes(M->T, N, M->r, nbp, 1);
+  DevBuf ws;
+  hipError_t e = dalloc(&ws.p, bytes / 8);
+  PanelSrc src{nullptr, M->Xp, nullptr, nullptr, M->ld, 0};
+  if (e == hipSuccess)
+    e = launch_chow_sweep(src, M->T, N, M->r, (int)bp_lo, (int)bp_hi, 1, M->F, M->L, so, (char *)ws.p, bytes, st,
+                          timer_cb, ctx);
+  for (int s = 0; s < 3 && e == hipSuccess; ++s) {
+    if (curves[s])
+      e = hipMemcpyAsync(curves[s], so.curve[s], (size_t)nbp * N * 8, hipMemcpyDeviceToHost, st);
+    const bool done = so.sup[s] || so.argsup[s];
+    if (e == hipSuccess && sup) {
+      if (done) e = hipMemcpyAsync(sup + (size_t)s * N, so.sup[s], (size_t)N * 8, hipMemcpyDeviceToHost, st);
+      else std::fill(sup + (size_t)s * N, sup + (size_t)(s + 1) * N, (double)NAN);
+    }
+    if (e == hipSuccess && argsup) {
+      if (done) e = hipMemcpyAsync(argsup + (size_t)s * N, so.argsup[s], (size_t)N * 8, hipMemcpyDeviceToHost, st);
+      else std::fill(argsup + (size_t)s * N, argsup + (size_t)(s + 1) * N, (int64_t)-1);
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  hipFree(darg);
+  HIPCHK(ctx, e);
+  HIPCHK(ctx, es);
   return 0;
 }
 

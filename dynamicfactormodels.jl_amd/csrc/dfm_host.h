@@ -133,6 +133,10 @@ struct dfm_model {
   int64_t batch = 0;
   char *ws = nullptr;
   size_t ws_bytes = 0;
+  // the sup-Chow sweep's workspace (dfm_chow_sweep.hip): bounded by the replicates per sweep launch, not by the
+  // batch, and kept between calls (allocating and freeing it per job cost more than a sup-LM job's kernels)
+  char *sw_ws = nullptr;
+  size_t sw_bytes = 0;
   StatDesc *sd_dev = nullptr;
   int sd_cap = 0;
   std::vector<StatDesc> sd_host;   // what sd_dev holds (uploaded only when a call's descriptors differ)
@@ -202,7 +206,9 @@ struct Scope {
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline bool chow_stat(int k) { return k >= DFM_STAT_LR && k <= DFM_STAT_WALD_ALL; }
-inline bool all_var_stat(int k) { return k >= DFM_STAT_LR_ALL && k <= DFM_STAT_WALD_ALL; }
+// the sup-Chow stats over a range of break periods (dfm_chow_sweep.hip): arg0..arg1
+inline bool sup_stat(int k) { return k >= DFM_STAT_SUPLR_ALL && k <= DFM_STAT_SUPWALD_ALL; }
+inline bool all_var_stat(int k) { return (k >= DFM_STAT_LR_ALL && k <= DFM_STAT_WALD_ALL) || sup_stat(k); }
 // values a stat adds to a replicate's row
 inline int64_t stat_width(const dfm_model *m, int k) {
   if (all_var_stat(k)) return m->N;

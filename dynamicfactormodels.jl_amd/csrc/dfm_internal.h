@@ -165,6 +165,21 @@ hipError_t launch_targeted(int mode, const double *y, const double *w, int q, co
                            int64_t ld, int T, int N, double cv, double *tstat, uint8_t *mask, char *ws,
                            size_t ws_bytes, hipStream_t st, int *bad);
 
+// ---- dfm_chow_sweep.hip (every break period bp_lo..bp_hi at once; r <= 16, no breaks)
+// Outputs of a sweep (device pointers; any may be nullptr, index 0 / 1 / 2 =
+// LR / LM / Wald): sup[s] + rep * os + i, argsup[s] (nb x N break periods),
+// curve[s] (nb x nbp x N).  A statistic none of whose outputs is set is not computed.
+struct ChowSweepOut {
+  double *sup[3] = {nullptr, nullptr, nullptr};
+  int64_t os = 0;
+  int64_t *argsup[3] = {nullptr, nullptr, nullptr};
+  double *curve[3] = {nullptr, nullptr, nullptr};
+};
+size_t chow_sweep_workspace_bytes(int T, int N, int r, int nbp, int nb);
+hipError_t launch_chow_sweep(const PanelSrc &src, int T, int N, int r, int bp_lo, int bp_hi, int nb, const double *F,
+                             const double *Lm, const ChowSweepOut &out, char *ws, size_t ws_bytes, hipStream_t st,
+                             timer_fn tf = nullptr, void *tctx = nullptr);
+
 // ---- dfm_spec.hip
 int spectrum_max();
 int64_t spectrum_work(int m, int nb);

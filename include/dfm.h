@@ -70,7 +70,10 @@ enum dfm_stat_kind {
   DFM_STAT_FACTORS = 13,   /* the replicate's factors vcat(F_j) (T x r row-major: T r values),
                               src/DynamicFactorModel.jl:18, :131 — the fields a host-side
                               stat::Function closure reads (src/bootstrap.jl:21, :41) */
-  DFM_STAT_LOADINGS = 14   /* break block arg0's loadings L_j (N x r row-major: N r values), :19 */
+  DFM_STAT_LOADINGS = 14,  /* break block arg0's loadings L_j (N x r row-major: N r values), :19 */
+  DFM_STAT_SUPLR_ALL = 15, /* max over bp = arg0..arg1 (inclusive) of LR for every variable (N   */
+  DFM_STAT_SUPLM_ALL = 16, /* values): the sup-Chow statistics of an unknown break date          */
+  DFM_STAT_SUPWALD_ALL = 17 /* (dfm_chow_sweep).  All sup stats of a call share one range        */
 };
 typedef struct dfm_stat { int32_t kind, arg0, arg1, pad; } dfm_stat;
 
@@ -265,6 +268,20 @@ int dfm_chow_all(dfm_model *m, int64_t bp, double *LR, double *LM, double *Wald)
  * 0-based.  The model keeps the all-variables results of the last break
  * period asked for, so a loop over i = 0..N-1 costs one dfm_chow_all. */
 int dfm_chow(dfm_model *m, int64_t bp, int64_t i, double *LR, double *LM, double *Wald);
+
+/* LR/LM/Wald (src/chowtest.jl:19-42) of every variable at every break period
+ * bp_lo..bp_hi (inclusive; each within dfm_chow_all's bounds r..T-r).
+ * curves: LR/LM/Wald, (bp_hi-bp_lo+1) x N row-major; sup: 3 x N (LR, LM, Wald);
+ * argsup: 3 x N break periods (0-based, the first maximum on ties).  Any
+ * pointer may be NULL; a statistic none of whose outputs is wanted is not
+ * computed.  `stats` selects what sup / argsup hold: a bit mask of 1 (LR),
+ * 2 (LM), 4 (Wald), 0 meaning all three; a statistic with its curve pointer
+ * set is computed whatever the mask.  Rows of sup / argsup of a statistic that
+ * was not computed are NaN / -1.  One device pass: the sup-LM alone costs no
+ * Wald work.  Models with r <= 16 fitted without breaks; -7 otherwise and for
+ * a bad range. */
+int dfm_chow_sweep(dfm_model *m, int64_t bp_lo, int64_t bp_hi, int stats, double *LR, double *LM,
+                   double *Wald, double *sup, int64_t *argsup);
 
 /* criterion_<name>(dfm) (src/criteria.jl:17-53) of a fitted model at its r,
  * for any criterion code (not only the one it was fitted with).  PCp's sigma^2

@@ -3,11 +3,15 @@
 C3 (bench.py).  One JSON line per config on stdout; the CPU column is the
 reference-faithful oracle (oracle/dfm_oracle.py) on this host, bounded.
 
-    python tools/bench_configs.py [--configs c1,c2,c4,c5] [--cpu] [--reps K]
+    python tools/bench_configs.py [--configs c1,c2,c2s,c4,c5] [--cpu] [--reps K]
 
 c1  Simulated DFM T=200 N=100 r=3: fit + Bai-Ng IC sweep k<=8 (all 7 criteria)
 c2  FRED-MD-shaped T=600 N=130, r by ICp2 over 1..8, wild bootstrap B=999 with
     LR/LM/Wald for all 130 variables at bp=300 (+ V, ICp2)      [replicates/s]
+c2s the sup-Chow sweep at C2's shape and fit: dfm_chow_sweep (LR/LM/Wald, every
+    date of the 15 %-trimmed range) against the host loop of dfm_chow_all over
+    the same dates, alternating; wild bootstrap B=999 of the sup-LM alone and
+    of all three sup statistics beside the single-date C2 job       [ms]
 c4  Targeted predictors T=400 N=5000: hard per-candidate t-stats, soft
     glmnetcv lasso (100 lambdas x 10 folds), then PCA (r=5) on the soft
     selection                                                  [selections/s]
@@ -245,6 +249,76 @@ def c5(D, ctx, args):
         rec["cpu_baseline"] = {"value": round(1 / el, 5), "unit": "windows/s", "cores": cores(), "kind": "port",
                                "sample": f"1 oracle window (T-1 rows, 8 brute-force refits) in {el:.1f} s"}
     return rec
+
+
+def c2s(D, ctx, args):
+    import torch
+    rng = np.random.default_rng(20261015 + 2)
+    T, N, B, bp = 600, 130, 999, 300
+    y, x, *_ = D.factor_model_DGP(T, N, 3, model="Breitung_Eickmeier_2011", b=0.5, rng=rng)
+    x = D.normalize(x)
+    w = np.ones((T, 1))
+    model = D.DynamicFactorModel(y, w, x, "ICp2", kmax=8, ctx=ctx)
+    r = model.number_of_factors
+    lo, hi = D.sup_chow_range(T, r)
+
+    def loop():
+        return np.array([D.chow_all(model, b) for b in range(lo, hi + 1)])   # (dates, 3, N)
+    res, ref = D.chow_sweep(model, lo, hi), loop()
+    agree = max(float(np.max(np.abs(res.sup[n] - ref[:, k].max(axis=0)) / ref[:, k].max(axis=0)))
+                for k, n in enumerate(D.api.SUP_CHOW_STATS))
+    dates_equal = all(np.array_equal(res.argsup[n], lo + ref[:, k].argmax(axis=0))
+                      for k, n in enumerate(D.api.SUP_CHOW_STATS))
+    # the two alternate, each timed by the host clock around calls that end in a stream synchronise
+    ts, tl = [], []
+    for _ in range(max(args.reps, 5) * 4):
+        t0 = time.perf_counter()
+        for _ in range(20):
+            D.chow_sweep(model, lo, hi)
+        t1 = time.perf_counter()
+        loop()
+        t2 = time.perf_counter()
+        ts.append((t1 - t0) / 20)
+        tl.append(t2 - t1)
+    ctx.reset_timing()
+    ctx.enable_timing(True)
+    D.chow_sweep(model, lo, hi)
+    ctx.enable_timing(False)
+    sweep_kernels_ms = ctx.read_timing()["chow"][0]
+    S = D.Stat
+    idx, eta = D.draw_wild_fast(7, B, T)
+    dev = torch.device("cuda", 0)
+    di, de = torch.from_numpy(idx).to(dev), torch.from_numpy(eta).to(dev)
+    jobs = {"single_date_lr_lm_wald": [S.LR_all(bp), S.LM_all(bp), S.Wald_all(bp)],
+            "sup_lm": [S.supLM_all(lo, hi)],
+            "sup_lr_lm_wald": [S.supLR_all(lo, hi), S.supLM_all(lo, hi), S.supWald_all(lo, hi)]}
+    boot = {}
+    for name, stats in jobs.items():
+        arr = D.api._stat_array(stats)
+        width = int(ctx.lib.dfm_stats_width(model.handle, arr, len(stats)))
+        out = torch.empty((B, width), dtype=torch.float64, device=dev)
+
+        def run():
+            ctx.check(ctx.lib.dfm_bootstrap_dev(model.handle, 0, B, di.data_ptr(), de.data_ptr(), arr, len(stats),
+                                                out.data_ptr()))
+        run()
+        ctx.synchronize()
+        ctx.reset_timing()
+        ctx.enable_timing(True)
+        sec = timed(run, max(args.reps, 5), ctx.synchronize)
+        ctx.enable_timing(False)
+        tm = ctx.read_timing()
+        boot[name] = {"ms_per_job": round(sec * 1e3, 3),
+                      "chow_kernels_ms_per_job": round(tm["chow"][0] / (max(args.reps, 5) + 1), 3)}
+    med = lambda v: float(np.median(v))   # noqa: E731
+    return {"config": "c2s", "workload": f"sup-Chow sweep, T={T} N={N} r={r}, dates {lo}..{hi} ({hi - lo + 1}), "
+                                         "LR/LM/Wald with sup and arg-max (host buffers out)",
+            "sweep_ms": round(med(ts) * 1e3, 4), "sweep_ms_min_max": [round(min(ts) * 1e3, 4), round(max(ts) * 1e3, 4)],
+            "chow_all_loop_ms": round(med(tl) * 1e3, 3),
+            "chow_all_loop_ms_min_max": [round(min(tl) * 1e3, 3), round(max(tl) * 1e3, 3)],
+            "value": round(med(tl) / med(ts), 1), "unit": "x (loop time / sweep time)",
+            "sweep_kernels_ms": round(sweep_kernels_ms, 4), "sup_max_rel_diff_vs_loop": agree,
+            "argsup_equal_loop": dates_equal, "bootstrap_B999": boot}
 
 
 def main():
