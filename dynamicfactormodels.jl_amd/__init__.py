@@ -10,7 +10,7 @@ the repo-root helper ``dfm_pkg.load()`` (the directory name contains a dot).
 """
 from .host import (factor_model_DGP, draw_wild, draw_wild_fast, draw_residual,
                    t_quantile, glmnet_default_folds, lag_vector, lag_matrix, norm_vector, norm_matrix,
-                   possemidef, read_panel_csv, reference_test_design)
+                   possemidef, read_panel_csv, reference_test_design, replicate_table)
 from .api import (Context, DFMError, Stat, DynamicFactorModel, DynamicFactorModelResult,
                   calculate_factors, principal_components, gram_spectrum, calculate_criterion,
                   factor_residual_variance, criterion_value, wild_bootstrap, residual_bootstrap,
@@ -18,7 +18,8 @@ from .api import (Context, DFMError, Stat, DynamicFactorModel, DynamicFactorMode
                   CRITERIA, pseudo_out_of_sample_refits, pseudo_out_of_sample_refits_dev,
                   pseudo_out_of_sample_forecasts, MSE, normalize, normalize_dev, clone_model,
                   lasso_path, lasso_stats, get_factors, predict, pseudo_out_of_sample_windows,
-                  chow_sweep, sup_chow_pvalues, sup_chow_range, ChowSweepResult)
+                  chow_sweep, sup_chow_pvalues, sup_chow_range, ChowSweepResult, monte_carlo,
+                  MonteCarloResult)
 from .api import (criterion_PCp1, criterion_PCp2, criterion_PCp3, criterion_ICp1,  # noqa: F401
                   criterion_ICp2, criterion_ICp3, criterion_BIC)
 from . import _lib
@@ -34,4 +35,5 @@ __all__ = [
     "pseudo_out_of_sample_forecasts", "MSE", "normalize_dev", "clone_model", "lasso_path", "lasso_stats",
     "get_factors", "predict", "pseudo_out_of_sample_windows",
     "chow_sweep", "sup_chow_pvalues", "sup_chow_range", "ChowSweepResult",
+    "monte_carlo", "MonteCarloResult", "replicate_table",
 ]

@@ -31,6 +31,11 @@ class dfm_window_spec(C.Structure):
                 ("kmax", C.c_int32), ("nbreaks", C.c_int32), ("breaks", C.POINTER(C.c_int64))]
 
 
+class dfm_mc_spec(C.Structure):
+    _fields_ = [("r", C.c_int32), ("crit", C.c_int32), ("kmax", C.c_int32), ("normalize", C.c_int32),
+                ("batch", C.c_int32), ("dev", C.c_int32)]
+
+
 # (name, restype, argtypes) — one row per symbol of include/dfm.h
 SIGNATURES = [
     ("dfm_ctx_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -102,6 +107,10 @@ SIGNATURES = [
                                  C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(dfm_window_spec), C.c_int,
                                  c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p]),
+    ("dfm_mc", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                         C.POINTER(dfm_mc_spec), C.POINTER(dfm_stat), C.c_int, c_int64_p, c_double_p, c_double_p,
+                         c_double_p]),
+    ("dfm_mc_stats_width", C.c_int64, [C.c_int64, C.POINTER(dfm_stat), C.c_int]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

@@ -862,6 +862,108 @@ def sup_chow_pvalues(observed, replicates) -> np.ndarray:
     return np.mean(rep >= obs[None, :], axis=0)
 
 
+# ------------------------------------------------------ Monte-Carlo batches
+@dataclass
+class MonteCarloResult:
+    """One ``monte_carlo`` call over M panels: ``rhat[name]`` ((M,) ints, the
+    first arg-min of criterion ``name`` over k = 1..kmax), ``criteria``
+    ((M, 7, kmax), ``CRITERIA`` order), ``eigenvalues`` ((M, kmax), descending),
+    ``r`` ((M,), the r each row was fitted at), ``rows`` ((M, width), the
+    statistics in the order asked for; ``columns(stat)`` slices one)."""
+    rhat: dict
+    criteria: np.ndarray
+    eigenvalues: np.ndarray
+    r: np.ndarray
+    rows: np.ndarray
+    stats: tuple = ()
+    _offsets: dict = field(default_factory=dict, repr=False)
+
+    def columns(self, stat: "Stat") -> np.ndarray:
+        """The columns of ``rows`` that ``stat`` filled: (M,) for a scalar
+        statistic, (M, N) for an all-variables one."""
+        lo, hi = self._offsets[stat]
+        return self.rows[:, lo] if hi - lo == 1 else self.rows[:, lo:hi]
+
+
+def _mc_layout(panels):
+    """(buffer, M, T, N, ldx, stride, dev) of ``dfm_mc``'s layout: M panels,
+    panel b column-major T x N at ``b * stride`` with leading dimension ldx.
+    An (M, T, N) float64 array or device tensor whose strides already are
+    (stride, 1, ldx) is passed as it is; anything else is repacked."""
+    if _is_device_tensor(panels):
+        if panels.dim() != 3 or panels.dtype.itemsize != 8 or not panels.dtype.is_floating_point:
+            raise ValueError("device panels must be a float64 (M, T, N) tensor")
+        M, T, N = (int(v) for v in panels.shape)
+        s0, s1, s2 = (int(v) for v in panels.stride())
+        if M and (s1 != 1 or s2 < T or s0 < s2 * N):
+            raise ValueError("device panels must be column-major per panel: strides (stride, 1, ldx), "
+                             "ldx >= T, stride >= ldx * N")
+        return panels, M, T, N, max(s2, T), max(s0, max(s2, T) * N), True
+    if isinstance(panels, np.ndarray) and panels.ndim == 3 and panels.dtype == np.float64:
+        M, T, N = panels.shape
+        s0, s1, s2 = panels.strides
+        if M and s1 == 8 and s2 % 8 == 0 and s0 % 8 == 0 and s2 >= 8 * T and s0 >= s2 * N:
+            return panels, M, T, N, s2 // 8, s0 // 8, False
+    a = np.asarray(panels, dtype=np.float64)
+    if a.ndim == 1 and a.size == 0:   # an empty list of panels
+        return a, 0, 0, 0, 0, 0, False
+    if a.ndim != 3:
+        raise ValueError("panels must be (M, T, N), or a list of M (T, N) arrays of one shape")
+    M, T, N = a.shape
+    return np.ascontiguousarray(a.transpose(0, 2, 1)), M, T, N, T, T * N, False
+
+
+def monte_carlo(panels, number_of_factors: Optional[int] = None, criterion: str = "ICp2", *,
+                kmax: Optional[int] = None, stats=None, normalize: bool = True, batch: int = 0,
+                ctx: Optional[Context] = None) -> MonteCarloResult:
+    """M independent panels of one shape fitted and tested in one pass
+    (``dfm_mc``): the loop of a Monte-Carlo study — the reference's driver
+    script ``src/Bai_Ng.jl:12-39``, the size / power tables of the Chow tests.
+
+    ``panels``: an (M, T, N) array, a list of (T, N) arrays, or a float64 GPU
+    tensor of shape (M, T, N) with strides (stride, 1, ldx) (each panel
+    column-major, read in place).  ``number_of_factors``: an int fits every
+    panel at that r (clamped to ceil(m/2)); None fits each at its own r^, the
+    first arg-min of ``criterion`` over k = 1..kmax.  ``stats``: ``Stat`` s of
+    the bootstrap menu that need no y / w (V, criterion, eigenvalue, trace, the
+    Chow tests and their sups), 1-based arguments as everywhere.  ``normalize``
+    z-scores every panel's columns first (``src/utils.jl:33``)."""
+    ctx = ctx or default_context()
+    if criterion not in _CRIT_CODE:
+        raise KeyError(f"criterion_{criterion} is not defined")
+    buf, M, T, N, ldx, stride, dev = _mc_layout(panels)
+    mfn = int(math.ceil(min(T, N) / 2)) if min(T, N) > 0 else 0
+    km = min(int(kmax), mfn) if kmax else mfn
+    if number_of_factors is not None and int(number_of_factors) < 1:
+        raise ValueError("number_of_factors must be >= 1")
+    r = 0 if number_of_factors is None else int(number_of_factors)
+    stats = [] if stats is None else (list(stats) if isinstance(stats, (list, tuple)) else [stats])
+    arr = _stat_array(stats)
+    spec = _lib.dfm_mc_spec(r, _CRIT_CODE[criterion], km, int(bool(normalize)), int(batch), int(dev))
+    width = int(ctx.lib.dfm_mc_stats_width(max(N, 1), arr, len(stats)))
+    if width < 0:
+        raise DFMError(width, "dfm_mc serves V, criterion, eigenvalue, trace and the Chow statistics "
+                              "(no y / w in a Monte-Carlo panel batch)")
+    rh = np.zeros((M, 7), dtype=np.int64)
+    ic = np.zeros((M, 7, km))
+    ev = np.zeros((M, km))
+    rows = np.zeros((M, width))
+    xp = None
+    if M:
+        xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data)
+    ctx.check(ctx.lib.dfm_mc(ctx.h, xp, M, T, N, ldx, stride, C.byref(spec), arr, len(stats),
+                             rh.ctypes.data_as(_lib.c_int64_p), _lib.ptr(ic), _lib.ptr(ev),
+                             _lib.ptr(rows) if stats else None))
+    rhat = {n: rh[:, i].copy() for i, n in enumerate(CRITERIA)}
+    fitted = rhat[criterion].copy() if r == 0 else np.full(M, min(r, mfn), dtype=np.int64)
+    off, o = {}, 0
+    for s in stats:
+        wdt = N if (9 <= s.kind <= 11 or 15 <= s.kind <= 17) else 1
+        off[s] = (o, o + wdt)
+        o += wdt
+    return MonteCarloResult(rhat, ic, ev, fitted, rows, tuple(stats), off)
+
+
 # ------------------------------------------------------- targeted predictors
 def targeted_predictors(y, w, x, thresholding: str = "hard", mode: str = "joint",
                         *, return_tstats: bool = False, folds=None,

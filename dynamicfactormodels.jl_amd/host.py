@@ -51,6 +51,41 @@ def factor_model_DGP(T: int, N: int, r: int, model: str = "Bai_Ng_2002", b: floa
     raise ValueError(f"unknown DGP model {model!r}")
 
 
+BAI_NG_CRITERIA = ("PCp1", "PCp2", "PCp3", "ICp1", "ICp2", "ICp3")
+
+
+def replicate_table(sample_tuples, num_reps: int = 1, rng: np.random.Generator | None = None,
+                    criteria: Sequence[str] = BAI_NG_CRITERIA, select=None) -> np.ndarray:
+    """The table of the reference's driver script (``src/Bai_Ng.jl:12-39``,
+    Bai–Ng 2002 Tables 1-3): for every (T, N, r) tuple the mean, over
+    ``num_reps`` panels drawn by ``factor_model_DGP``, of the number of factors
+    each criterion selects — a (tuples x criteria) array.
+
+    ``select(panels)`` takes the tuple's ``num_reps`` raw (T, N) panels and
+    returns a mapping from criterion name to the (num_reps,) selected factor
+    counts; the default is ``monte_carlo(panels).rhat`` (one device pass per
+    tuple: z-score, Gram, spectrum and the sweep of every criterion).
+
+    The draws come from ``rng`` in tuple-then-repetition order, ONE draw per
+    repetition shared by all criteria.  The reference loops over the criteria
+    outermost and so redraws every panel for each of them (``:15-22``): a cost
+    it pays — six draws and six fits where one serves — not part of what the
+    table means; each entry here is the same estimator on a common sample."""
+    rng = rng or np.random.default_rng()
+    if select is None:
+        from .api import monte_carlo
+
+        def select(panels):
+            return monte_carlo(panels).rhat
+    table = np.zeros((len(sample_tuples), len(criteria)))
+    for i, (T, N, r) in enumerate(sample_tuples):
+        panels = [factor_model_DGP(T, N, r, rng=rng)[1] for _ in range(num_reps)]
+        chosen = select(panels)
+        for j, name in enumerate(criteria):
+            table[i, j] = np.mean(np.asarray(chosen[name], dtype=np.float64))
+    return table
+
+
 def draw_wild(rng: np.random.Generator, B: int, T: int):
     """Host RNG contract of the wild bootstrap (``src/bootstrap.jl:44-45``):
     per replicate T row indices (0-based) then T N(0,1) multipliers."""

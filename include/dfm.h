@@ -354,6 +354,50 @@ int dfm_windows_ex(dfm_ctx *ctx, const double *y, const double *w, int q, int64_
                    double *crit_out, double *eig_out, double *coef_out, double *tstat_out,
                    double *pred_out, double *true_out);
 
+/* --------------------------------------------------- Monte-Carlo batches
+ * M independent panels of one shape fitted and tested in one pass: the loop of
+ * the reference's driver script (src/Bai_Ng.jl:12-39: per (T, N, r) tuple and
+ * repetition factor_model_DGP -> normalize -> the IC-sweep constructor ->
+ * number_of_factors) and of the size / power tables of the Chow tests.  Per
+ * panel: the z-score (optional), the Gram, its spectrum, the seven criteria
+ * for k = 1..kmax with their first arg-mins, and — when statistics are asked
+ * for — the principal-components fit at the panel's r with the statistics of
+ * the dfm_bootstrap menu that need no y / w.  No OLS is run.
+ *
+ * Statistics (meaning and 0-based arguments as in dfm_bootstrap): V,
+ * CRIT(code; < 0: spec->crit), EIGVAL(j), TRACE, LR / LM / WALD(bp, i),
+ * LR_ALL / LM_ALL / WALD_ALL(bp) (one bp per call), SUPLR_ALL / SUPLM_ALL /
+ * SUPWALD_ALL(lo, hi) (one range per call).  COEF, TSTAT, ITERS, FACTORS and
+ * LOADINGS return -6.  With r == 0 EIGVAL(j) of a panel whose r^ <= j is NaN.
+ *
+ * Checked before any device work: break periods and sup ranges against
+ * dfm_chow_all's bounds rmax..T-rmax for the largest r a panel can get
+ * (rmax = r, or kmax when r == 0): -7; a fixed r above the fit stage's limit
+ * (32; 16 with a sup statistic) with statistics asked for: -7; min(T, N) <=
+ * dfm_full_spectrum_max(): -31.  After the sweep: a panel whose r^ exceeds
+ * that limit while statistics are asked for fails the call with -7 (the
+ * message names the panel).  M == 0 is a no-op. */
+typedef struct dfm_mc_spec {
+  int32_t r;         /* > 0: every panel is fitted at r (clamped to ceil(m/2), :116-119);
+                        0: each panel at its own r^ = first arg-min of `crit` over k = 1..kmax */
+  int32_t crit;      /* dfm_criterion: selects r^ when r == 0; DFM_STAT_CRIT's default code */
+  int32_t kmax;      /* sweep bound; <= 0: ceil(min(T,N)/2) (D11); larger values are cut to that */
+  int32_t normalize; /* != 0: z-score every panel's columns first (src/utils.jl:33, Bai_Ng.jl:23) */
+  int32_t batch;     /* panels per device pass; 0 = auto (bounded workspace) */
+  int32_t dev;       /* != 0: X is a device pointer on the context's device */
+} dfm_mc_spec;
+
+/* X: M panels, panel b column-major T x N at X + b*stride (ldx >= T, stride >= ldx*N).
+ * r_hat: M x 7 (r^ by each criterion, dfm_criterion order); ic: M x 7 x kmax;
+ * eig: M x kmax (descending); out: M rows of dfm_mc_stats_width doubles.
+ * (kmax: the effective bound, min(spec->kmax or ceil(m/2), ceil(m/2)).)
+ * All outputs are host memory, all are optional (NULL skips), rows are in panel order. */
+int dfm_mc(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+           const dfm_mc_spec *spec, const dfm_stat *stats, int nstats,
+           int64_t *r_hat, double *ic, double *eig, double *out);
+/* Width of one panel's output row; < 0 for a statistic dfm_mc does not serve.  Pure arithmetic. */
+int64_t dfm_mc_stats_width(int64_t N, const dfm_stat *stats, int nstats);
+
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
  * JOINT: OLS of y on [w x], White HC0, |t_x| > crit_value (the reference's

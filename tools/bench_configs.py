@@ -3,7 +3,7 @@
 C3 (bench.py).  One JSON line per config on stdout; the CPU column is the
 reference-faithful oracle (oracle/dfm_oracle.py) on this host, bounded.
 
-    python tools/bench_configs.py [--configs c1,c2,c2s,c4,c5] [--cpu] [--reps K]
+    python tools/bench_configs.py [--configs c1,c2,c2s,c4,c5,mc] [--cpu] [--reps K]
 
 c1  Simulated DFM T=200 N=100 r=3: fit + Bai-Ng IC sweep k<=8 (all 7 criteria)
 c2  FRED-MD-shaped T=600 N=130, r by ICp2 over 1..8, wild bootstrap B=999 with
@@ -12,6 +12,10 @@ c2s the sup-Chow sweep at C2's shape and fit: dfm_chow_sweep (LR/LM/Wald, every
     date of the 15 %-trimmed range) against the host loop of dfm_chow_all over
     the same dates, alternating; wild bootstrap B=999 of the sup-LM alone and
     of all three sup statistics beside the single-date C2 job       [ms]
+mc  Monte-Carlo batch: M=1000 Bai-Ng panels T=100 N=60 r=3, kmax 8 — selection
+    only, and with the sup-LM of every variable at r=3 — monte_carlo (dfm_mc)
+    against the per-panel loop it replaces (DynamicFactorModel + chow_sweep),
+    alternating, end to end with uploads; per-class kernel split    [x, ms]
 c4  Targeted predictors T=400 N=5000: hard per-candidate t-stats, soft
     glmnetcv lasso (100 lambdas x 10 folds), then PCA (r=5) on the soft
     selection                                                  [selections/s]
@@ -319,6 +323,82 @@ def c2s(D, ctx, args):
             "value": round(med(tl) / med(ts), 1), "unit": "x (loop time / sweep time)",
             "sweep_kernels_ms": round(sweep_kernels_ms, 4), "sup_max_rel_diff_vs_loop": agree,
             "argsup_equal_loop": dates_equal, "bootstrap_B999": boot}
+
+
+def mc(D, ctx, args):
+    M, T, N, r, kmax = 1000, 100, 60, 3, 8
+    xs = np.array([D.factor_model_DGP(T, N, r, rng=np.random.default_rng(20261019 + b))[1] for b in range(M)])
+    y, w = np.zeros(T), np.ones((T, 1))
+    lo, hi = D.sup_chow_range(T, r)
+    sup = [D.Stat.supLM_all(lo, hi)]
+
+    def batch_sel():
+        return D.monte_carlo(xs, kmax=kmax, ctx=ctx)
+
+    def batch_sup():
+        return D.monte_carlo(xs, r, kmax=kmax, stats=sup, ctx=ctx)
+
+    # the panels already resident in HBM in dfm_mc's layout: no host repack, no upload
+    import torch
+    xd = torch.from_numpy(np.ascontiguousarray(xs.transpose(0, 2, 1))).to(torch.device("cuda", 0)).permute(0, 2, 1)
+
+    def batch_sel_dev():
+        return D.monte_carlo(xd, kmax=kmax, ctx=ctx)
+
+    def batch_sup_dev():
+        return D.monte_carlo(xd, r, kmax=kmax, stats=sup, ctx=ctx)
+
+    def loop_sel():
+        return [D.DynamicFactorModel(y, w, D.normalize(x, ctx=ctx), "ICp2", kmax=kmax, ctx=ctx) for x in xs]
+
+    def loop_sup():
+        out = []
+        for x in xs:
+            g = D.DynamicFactorModel(y, w, D.normalize(x, ctx=ctx), "ICp2", kmax=kmax, ctx=ctx)
+            out.append((g.number_of_factors, D.chow_sweep(g, lo, hi, stats=["LM"]).sup["LM"]))
+        return out
+    # the same numbers: r^ of every panel, and the sup-LM rows of the panels the loop fitted at r
+    a, b = batch_sel(), loop_sel()
+    assert np.array_equal(a.criteria, batch_sel_dev().criteria)
+    rhat_equal = bool(np.array_equal(a.rhat["ICp2"], [g.number_of_factors for g in b]))
+    a2, b2 = batch_sup(), loop_sup()
+    at_r = [i for i, (k, _) in enumerate(b2) if k == r]
+    sup_diff = max(float(np.max(np.abs(a2.rows[i] - b2[i][1]) / np.abs(b2[i][1]))) for i in at_r)
+    del b, b2
+    # alternating, each call ending in a stream synchronise (host clock, uploads and read-backs in)
+    reps = max(args.reps, 5)
+    t = {"batch_sel": [], "loop_sel": [], "batch_sup": [], "loop_sup": [], "batch_sel_dev": [], "batch_sup_dev": []}
+    for _ in range(reps):
+        for name, fn, inner in (("batch_sel", batch_sel, 10), ("loop_sel", loop_sel, 1), ("batch_sup", batch_sup, 10),
+                                ("loop_sup", loop_sup, 1), ("batch_sel_dev", batch_sel_dev, 10),
+                                ("batch_sup_dev", batch_sup_dev, 10)):
+            t0 = time.perf_counter()
+            for _ in range(inner):
+                fn()
+            t[name].append((time.perf_counter() - t0) / inner)
+    split = {}
+    for name, fn in (("selection", batch_sel), ("sup_lm", batch_sup)):
+        ctx.reset_timing()
+        ctx.enable_timing(True)
+        fn()
+        ctx.enable_timing(False)
+        split[name] = {k: [round(v[0], 4), int(v[1])] for k, v in ctx.read_timing().items() if v[1]}
+    ms = lambda v: {"median": round(float(np.median(v)) * 1e3, 3), "min": round(min(v) * 1e3, 3),   # noqa: E731
+                    "max": round(max(v) * 1e3, 3)}
+    med = lambda k: float(np.median(t[k]))   # noqa: E731
+    return {"config": "mc", "workload": f"Monte-Carlo batch M={M}, T={T} N={N} r={r}, kmax {kmax}: selection (all 7 "
+                                        f"criteria), and + sup-LM of every variable over dates {lo}..{hi} at r={r}; "
+                                        "host panels in, results out",
+            "value": round(med("loop_sel") / med("batch_sel"), 1), "unit": "x (per-panel loop time / monte_carlo time)",
+            "selection_ms": {"monte_carlo": ms(t["batch_sel"]), "loop": ms(t["loop_sel"]),
+                             "monte_carlo_resident_input": ms(t["batch_sel_dev"])},
+            "sup_lm_ms": {"monte_carlo": ms(t["batch_sup"]), "loop": ms(t["loop_sup"]),
+                          "monte_carlo_resident_input": ms(t["batch_sup_dev"])},
+            "sup_lm_ratio": round(med("loop_sup") / med("batch_sup"), 1),
+            "kernel_ms_and_launches_by_class": split,
+            "classes": "misc = layout + z-score (+ relocation lists), gram, eig_other = trace + spectrum, "
+                       "stats = criterion sweep / arg-min (+ V etc.), eig_* / factors / chow = fit stage",
+            "rhat_equal_loop": rhat_equal, "sup_lm_max_rel_diff_vs_loop": sup_diff, "panels_compared": len(at_r)}
 
 
 def main():
