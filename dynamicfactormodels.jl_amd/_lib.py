@@ -36,6 +36,16 @@ class dfm_mc_spec(C.Structure):
                 ("batch", C.c_int32), ("dev", C.c_int32)]
 
 
+class dfm_em_spec(C.Structure):
+    _fields_ = [("r", C.c_int32), ("crit", C.c_int32), ("kmax", C.c_int32), ("standardize", C.c_int32),
+                ("max_iter", C.c_int32), ("dev", C.c_int32), ("tol", C.c_double)]
+
+
+class dfm_em_info(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("r", C.c_int32), ("pad", C.c_int32),
+                ("err", C.c_double), ("n_missing", C.c_int64)]
+
+
 # (name, restype, argtypes) — one row per symbol of include/dfm.h
 SIGNATURES = [
     ("dfm_ctx_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -111,6 +121,13 @@ SIGNATURES = [
                          C.POINTER(dfm_mc_spec), C.POINTER(dfm_stat), C.c_int, c_int64_p, c_double_p, c_double_p,
                          c_double_p]),
     ("dfm_mc_stats_width", C.c_int64, [C.c_int64, C.POINTER(dfm_stat), C.c_int]),
+    ("dfm_em", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
+                         c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                         C.POINTER(dfm_em_info)]),
+    ("dfm_model_fit_em", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.c_int64, C.c_int64, C.POINTER(dfm_em_spec), C.POINTER(C.c_void_p),
+                                   C.POINTER(dfm_em_info)]),
+    ("dfm_model_em_read", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

@@ -702,6 +702,8 @@ def clone_model(dfm: DynamicFactorModelResult, ctx: Context) -> DynamicFactorMod
     res = DynamicFactorModelResult(ctx, h, dfm.y, dfm.w, dfm.x, dfm.number_of_factors_criterion,
                                    dfm.break_indices)
     res.targeted_predictors = getattr(dfm, "targeted_predictors", None)
+    if hasattr(dfm, "em"):   # a DynamicFactorModel_em fit: the clone's device model carries its panel and moments too
+        res.em = dfm.em
     return res
 
 
@@ -962,6 +964,124 @@ def monte_carlo(panels, number_of_factors: Optional[int] = None, criterion: str 
         off[s] = (o, o + wdt)
         o += wdt
     return MonteCarloResult(rhat, ic, ev, fitted, rows, tuple(stats), off)
+
+
+# ------------------------------------------------- missing observations (EM)
+@dataclass
+class EMResult:
+    """Principal components of a panel with missing entries (``dfm_em``): the
+    completed panel standardised (``x_standardized``, what the factors are the
+    PCA of) and in original units (``x_completed``: observed entries untouched,
+    missing ones the de-standardised common component), the last z-score's
+    ``mean`` and ``std``, the T x r ``factors``, N x r ``loadings`` and r
+    ``eigenvalues``, and the iteration's record."""
+    x_standardized: np.ndarray
+    x_completed: np.ndarray
+    mean: np.ndarray
+    std: np.ndarray
+    factors: np.ndarray
+    loadings: np.ndarray
+    eigenvalues: np.ndarray
+    number_of_factors: int
+    iterations: int
+    error: float
+    converged: bool
+    n_missing: int
+
+
+def _em_spec(T, N, number_of_factors, criterion, kmax, tol, max_iter, standardize, dev):
+    if criterion and criterion not in _CRIT_CODE:
+        raise KeyError(f"criterion_{criterion} is not defined")
+    if number_of_factors is None:
+        if not criterion:
+            raise ValueError("selecting the number of factors needs a criterion")
+        r = 0
+    else:
+        r = int(number_of_factors)
+        if r < 1:
+            raise ValueError("number_of_factors must be >= 1")
+    return _lib.dfm_em_spec(r, _CRIT_CODE[criterion] if criterion else -1, int(kmax) if kmax else 0,
+                            int(bool(standardize)), int(max_iter), int(dev), float(tol))
+
+
+def _em_panel(x):
+    """(pointer, T, N, ldx, dev, keep-alive) of a host array or a column-major float64 GPU tensor."""
+    if _is_device_tensor(x):
+        if x.dtype.itemsize != 8 or x.dim() != 2 or x.stride(0) != 1:
+            raise ValueError("x must be a column-major float64 GPU tensor (stride (1, ldx))")
+        return C.c_void_p(x.data_ptr()), int(x.shape[0]), int(x.shape[1]), int(x.stride(1)), 1, x
+    xc = _colmajor(_f64(x, 2))
+    return C.c_void_p(xc.ctypes.data), xc.shape[0], xc.shape[1], xc.shape[0], 0, xc
+
+
+def em_factors(x, number_of_factors: Optional[int] = None, criterion: str = "ICp2", *,
+               kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50, standardize: bool = True,
+               ctx: Optional[Context] = None) -> EMResult:
+    """Factors of a T x N panel whose missing entries are NaN, by the EM
+    iteration of Stock & Watson (2002) as McCracken & Ng (2016) run it for
+    FRED-MD (``dfm_em``; the algorithm is stated in ``include/dfm.h``): fill,
+    z-score, PCA, refill the missing entries from the common component, until
+    the common component's relative squared change is at most ``tol`` or
+    ``max_iter`` iterations ran (``converged`` tells which).  The whole loop
+    runs on the device.  ``number_of_factors``: an int, or None to re-select r
+    in every iteration as the first arg-min of ``criterion`` (ICp1-3 or BIC)
+    over 1..kmax.  ``standardize=False`` takes the panel as the caller scaled
+    it.  ``x`` may be a column-major float64 GPU tensor."""
+    ctx = ctx or default_context()
+    xp, T, N, ldx, dev, keep = _em_panel(x)
+    spec = _em_spec(T, N, number_of_factors, criterion, kmax, tol, max_iter, standardize, dev)
+    mfn = max(1, int(math.ceil(min(T, N) / 2)))
+    cap = min(int(number_of_factors), mfn) if number_of_factors is not None else min(32, mfn)
+    Z = np.zeros((T, N), order="F")
+    X2 = np.zeros((T, N), order="F")
+    mu, sd = np.zeros(N), np.zeros(N)
+    F, L, ev = np.zeros(T * cap), np.zeros(N * cap), np.zeros(cap)
+    info = _lib.dfm_em_info()
+    ctx.check(ctx.lib.dfm_em(ctx.h, xp, T, N, ldx, C.byref(spec), Z.ctypes.data_as(_lib.c_double_p),
+                             X2.ctypes.data_as(_lib.c_double_p), _lib.ptr(mu), _lib.ptr(sd), _lib.ptr(F),
+                             _lib.ptr(L), _lib.ptr(ev), C.byref(info)))
+    del keep
+    r = int(info.r)
+    return EMResult(np.ascontiguousarray(Z), np.ascontiguousarray(X2), mu, sd,
+                    np.ascontiguousarray(F[:T * r].reshape(r, T).T), np.ascontiguousarray(L[:N * r].reshape(r, N).T),
+                    ev[:r].copy(), r, int(info.iterations), float(info.err), bool(info.converged),
+                    int(info.n_missing))
+
+
+def DynamicFactorModel_em(y, w, x, number_of_factors: Optional[int] = None, criterion: str = "ICp2", *,
+                          kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50,
+                          standardize: bool = True, ctx: Optional[Context] = None) -> DynamicFactorModelResult:
+    """``em_factors`` of the panel, then the workhorse fit of (y, w, completed
+    standardised panel) at the final r (``dfm_model_fit_em``): the record of
+    ``DynamicFactorModel(y, w, res.em.x_standardized, res.em.number_of_factors,
+    criterion)`` bit for bit, resident on the device, so ``wild_bootstrap``,
+    ``chow_sweep`` and the rest serve it as any fit.  ``.em`` is the
+    ``EMResult``; ``.x`` is the completed standardised panel."""
+    ctx = ctx or default_context()
+    y = _f64(y).ravel()
+    w = _f64(w, 2)
+    xp, T, N, ldx, dev, keep = _em_panel(x)
+    if len(y) != T or w.shape[0] != T:
+        raise ValueError("y, w and x must have the same number of rows")
+    spec = _em_spec(T, N, number_of_factors, criterion, kmax, tol, max_iter, standardize, dev)
+    wc = _colmajor(w)
+    h = C.c_void_p()
+    info = _lib.dfm_em_info()
+    ctx.check(ctx.lib.dfm_model_fit_em(ctx.h, _lib.ptr(y), wc.ctypes.data_as(_lib.c_double_p), w.shape[1], T, xp,
+                                       T, N, ldx, C.byref(spec), C.byref(h), C.byref(info)))
+    del keep
+    X2 = np.zeros((T, N), order="F")
+    mu, sd = np.zeros(N), np.zeros(N)
+    ctx.check(ctx.lib.dfm_model_em_read(h, X2.ctypes.data_as(_lib.c_double_p), _lib.ptr(mu), _lib.ptr(sd)))
+    X2 = np.ascontiguousarray(X2)
+    # the device's z-score, (x - mu) / sd with IEEE subtraction and division: the same bits on the host
+    Z = (X2 - mu) / sd if standardize else X2.copy()
+    res = DynamicFactorModelResult(ctx, h, y, w, Z, criterion or "")
+    res.targeted_predictors = np.ones(N, dtype=bool)
+    r = res.number_of_factors
+    res.em = EMResult(Z, X2, mu, sd, res.factors[0], res.loadings[0], res.eigenvalues[:r].copy(), r,
+                      int(info.iterations), float(info.err), bool(info.converged), int(info.n_missing))
+    return res
 
 
 # ------------------------------------------------------- targeted predictors

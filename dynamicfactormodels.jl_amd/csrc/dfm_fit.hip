@@ -106,6 +106,7 @@ int dfm_model_destroy(dfm_model *m) {
                     m->cF, m->hd, m->FtF, m->FSF, m->Kwk, m->A0wk})
     hipFree(p);
   hipFree(m->H32);
+  hipFree(m->emX2);
   for (size_t j = 1; j < m->Ubs.size(); ++j) hipFree(m->Ubs[j]);
   hipFree(m->ws);
   hipFree(m->sw_ws);
@@ -982,6 +983,10 @@ extern "C" int dfm_model_clone(const dfm_model *S, dfm_ctx *ctx, dfm_model **out
   }
   M->Ub = M->Ubs.empty() ? nullptr : M->Ubs[0];
   M->L = M->Lall;
+  if (S->emX2 && !bad) {   // a dfm_model_fit_em model stays one
+    bad |= dup(S->emX2, T * N, &M->emX2);
+    M->em_mu = S->em_mu; M->em_sd = S->em_sd;
+  }
   hipSetDevice(ctx->device);
   if (!bad) bad = dalloc(&M->flag_dev, 4) != hipSuccess;
   if (!bad) bad = hipStreamSynchronize(ctx->stream) != hipSuccess;   // every copy landed

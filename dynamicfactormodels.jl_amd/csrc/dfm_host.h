@@ -172,6 +172,10 @@ struct dfm_model {
   LaneWorker *lane_worker[kMaxLanes - 1] = {};
   bool is_lane = false;
   dfm_ctx *count_ctx = nullptr;   // a lane counts its GEMM products into its parent's context
+  // a model of dfm_model_fit_em (dfm_em.hip): the completed panel in original units (column-major T x N) and
+  // the moments of its last z-score; emX2 == nullptr for every other model
+  double *emX2 = nullptr;
+  std::vector<double> em_mu, em_sd;
 };
 
 namespace dfm {

@@ -180,12 +180,16 @@ def possemidef(x) -> bool:
         return False
 
 
-def read_panel_csv(path: str):
+def read_panel_csv(path: str, missing: str = "raise"):
     """The data load of ``test/DynamicFactorModel.jl:6-7``: ``readtable`` of a
     CSV whose first column is the date / id and whose other columns are the
     series; returns (series names, T x (columns-1) float64 matrix).  Missing
-    values raise, as ``convert(Array{Float64}, col)`` does on an NA."""
+    values raise, as ``convert(Array{Float64}, col)`` does on an NA;
+    ``missing="nan"`` turns empty, NA and NaN cells into NaN instead (the
+    marker ``em_factors`` and ``DynamicFactorModel_em`` read)."""
     import csv
+    if missing not in ("raise", "nan"):
+        raise ValueError("missing must be 'raise' or 'nan'")
     with open(path, newline="") as fh:
         rows = list(csv.reader(fh))
     header, body = rows[0], [r for r in rows[1:] if r]
@@ -197,7 +201,10 @@ def read_panel_csv(path: str):
         for c, cell in enumerate(row[1:]):
             cell = cell.strip()
             if cell in ("", "NA", "NaN", "nan"):
-                raise ValueError(f"missing value in column {names[c]!r}, row {t + 2}")
+                if missing == "raise":
+                    raise ValueError(f"missing value in column {names[c]!r}, row {t + 2}")
+                data[t, c] = np.nan
+                continue
             data[t, c] = float(cell)
     return names, data
 

@@ -398,6 +398,59 @@ int dfm_mc(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64
 /* Width of one panel's output row; < 0 for a statistic dfm_mc does not serve.  Pure arithmetic. */
 int64_t dfm_mc_stats_width(int64_t N, const dfm_stat *stats, int nstats);
 
+/* ------------------------------------- missing observations (EM, dfm_em.hip)
+ * Principal components of a panel with missing entries (NaN) by the EM
+ * iteration of Stock & Watson (2002) as McCracken & Ng (2016) run it for
+ * FRED-MD (factors_em, DEMEAN = 2), obs = !isnan(X):
+ *   X2 = X, missing := the mean of the column's observed entries
+ *   (mu, sd) = column mean and sample (n-1) std of X2;  Z = (X2 - mu) / sd
+ *   r fixed, or the first arg-min of `crit` over k = 1..kmax on Z
+ *   (F, L) = principal_components(Z)[:, 1:r];  C = F L'
+ *   it = 0; err = +inf
+ *   while err > tol and it < max_iter:
+ *     it += 1;  X2 = obs ? X : C * sd + mu  (the mu, sd that produced C)
+ *     (mu, sd), Z from the new X2;  r re-selected when it is not fixed
+ *     (F, L) again;  Cnew = F L';  err = ||Cnew - C||_F^2 / ||C||_F^2;  C = Cnew
+ *   converged = (err <= tol)
+ * The loop runs on the device; per iteration only the two sums, two flags and
+ * (when r is selected) kmax eigenvalues and the trace reach the host.  The PCA
+ * is the library's own (X'X for T >= N, XX' for N > T), warm-started from the
+ * previous iteration.  A row with no observed entry is legal.
+ *
+ * Return codes: -8 a column with fewer than 2 observed entries, or a zero std
+ * of a column when standardising (the message names the column, 0-based);
+ * -3 selecting r by a PCp criterion (it needs the full spectrum in every
+ * iteration: use ICp1-3 or BIC) or without one; -7 kmax / r beyond the
+ * eigensolver's subspace block; -2 NaN in y or w (dfm_model_fit_em).  Reaching
+ * max_iter is not an error: converged = 0 says so. */
+typedef struct dfm_em_spec {
+  int32_t r;            /* > 0 fixed; 0: re-selected every iteration by crit over 1..kmax */
+  int32_t crit, kmax;   /* as dfm_model_fit; kmax <= 0 -> min(ceil(m/2), solver limit) */
+  int32_t standardize;  /* 1 (default): z-score every iteration; 0: panel as given */
+  int32_t max_iter;     /* <= 0 -> 50 */
+  int32_t dev;          /* != 0: X is a device pointer */
+  double  tol;          /* < 0 -> 1e-6; 0 runs exactly max_iter iterations */
+} dfm_em_spec;
+typedef struct dfm_em_info { int32_t iterations, converged, r, pad; double err; int64_t n_missing; } dfm_em_info;
+
+/* X column-major T x N (ldx >= T).  Outputs host, column-major, any may be NULL:
+ * Z (T x N standardised completed panel), X2 (T x N completed, original units),
+ * mu (N), sd (N), F (T x r), L (N x r), eigvals (r) — r = info->r; size F, L
+ * and eigvals for spec->r, or for kmax (at most 32) when r is selected. */
+int dfm_em(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *spec,
+           double *Z, double *X2, double *mu, double *sd, double *F, double *L, double *eigvals,
+           dfm_em_info *info);
+/* dfm_em, then the workhorse fit of (y, w, Z) at the final r: a normal
+ * dfm_model — equal to dfm_model_fit(y, w, Z, r, crit, kmax) bit for bit — so
+ * the bootstrap, Chow, sup-Chow, criterion and predict entry points serve it
+ * unchanged.  y and w are host memory. */
+int dfm_model_fit_em(dfm_ctx *ctx, const double *y, const double *w, int q, int64_t ldw, const double *X,
+                     int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *spec, dfm_model **out,
+                     dfm_em_info *info);
+/* The completed panel X2 (T x N column-major, original units) and the last
+ * z-score's mu (N), sd (N) of a dfm_model_fit_em model; -1 for any other model. */
+int dfm_model_em_read(const dfm_model *m, double *X2, double *mu, double *sd);
+
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
  * JOINT: OLS of y on [w x], White HC0, |t_x| > crit_value (the reference's

@@ -3,7 +3,7 @@
 C3 (bench.py).  One JSON line per config on stdout; the CPU column is the
 reference-faithful oracle (oracle/dfm_oracle.py) on this host, bounded.
 
-    python tools/bench_configs.py [--configs c1,c2,c2s,c4,c5,mc] [--cpu] [--reps K]
+    python tools/bench_configs.py [--configs c1,c2,c2s,c4,c5,mc,em] [--cpu] [--reps K]
 
 c1  Simulated DFM T=200 N=100 r=3: fit + Bai-Ng IC sweep k<=8 (all 7 criteria)
 c2  FRED-MD-shaped T=600 N=130, r by ICp2 over 1..8, wild bootstrap B=999 with
@@ -16,6 +16,11 @@ mc  Monte-Carlo batch: M=1000 Bai-Ng panels T=100 N=60 r=3, kmax 8 — selection
     only, and with the sup-LM of every variable at r=3 — monte_carlo (dfm_mc)
     against the per-panel loop it replaces (DynamicFactorModel + chow_sweep),
     alternating, end to end with uploads; per-class kernel split    [x, ms]
+em  EM fit of a panel with missing entries (em_factors, dfm_em), r=8: a
+    FRED-MD-like T=720 N=128 panel (~5 % missing, ragged edges, late starters)
+    and C3's shape T=500 N=2000, against the host loop a caller writes
+    without it (NumPy fill + normalize + principal_components per iteration,
+    the same iteration count), alternating                           [x, ms]
 c4  Targeted predictors T=400 N=5000: hard per-candidate t-stats, soft
     glmnetcv lasso (100 lambdas x 10 folds), then PCA (r=5) on the soft
     selection                                                  [selections/s]
@@ -399,6 +404,77 @@ def mc(D, ctx, args):
             "classes": "misc = layout + z-score (+ relocation lists), gram, eig_other = trace + spectrum, "
                        "stats = criterion sweep / arg-min (+ V etc.), eig_* / factors / chow = fit stage",
             "rhat_equal_loop": rhat_equal, "sup_lm_max_rel_diff_vs_loop": sup_diff, "panels_compared": len(at_r)}
+
+
+def em_panel(D, T, N, r, seed):
+    """A FRED-MD-like panel: r factors + noise, columns on their own scales; ~3 %
+    missing at random, ragged last 1-3 rows on a third of the columns, late
+    starters (first 24-240 rows missing) on a tenth — about 5 % missing in all."""
+    rng = np.random.default_rng(seed)
+    x = D.factor_model_DGP(T, N, r, rng=rng)[1]
+    x = x * rng.uniform(0.5, 3.0, size=N) + rng.uniform(-2.0, 2.0, size=N)
+    miss = rng.uniform(size=(T, N)) < 0.03
+    for j in rng.choice(N, N // 3, replace=False):
+        miss[T - int(rng.integers(1, 4)):, j] = True
+    for j in rng.choice(N, N // 10, replace=False):
+        miss[:int(rng.integers(T // 30, T // 3)), j] = True
+    x[miss] = np.nan
+    return x
+
+
+def em(D, ctx, args):
+    r = 8
+    out = {"config": "em", "workload": f"EM fit with missing entries at r={r}, tol 1e-6: em_factors (device loop) vs the "
+                                       "host loop (NumPy fill + normalize + principal_components per iteration, same "
+                                       "iteration count); host panel in, completed panels / factors / loadings out",
+           "unit": "x (host loop time / em_factors time)", "shapes": {}}
+    for name, T, N in (("fred_md_like", 720, 128), ("c3_shape", 500, 2000)):
+        x = em_panel(D, T, N, r, 20261020 + N)
+        obs = ~np.isnan(x)
+        res = D.em_factors(x, r, ctx=ctx)
+        iters = res.iterations
+
+        def device():
+            return D.em_factors(x, r, ctx=ctx)
+
+        def host_loop():
+            x2 = np.where(obs, x, np.nanmean(x, axis=0))
+            for it in range(iters + 1):
+                mu, sd = x2.mean(axis=0), x2.std(axis=0, ddof=1)
+                z = D.normalize(x2, ctx=ctx)
+                ev, F, L, _ = D.principal_components(z, r, ctx=ctx)
+                c = F @ L.T
+                if it < iters:
+                    x2 = np.where(obs, x, c * sd + mu)
+            return z, c
+        zl, cl = host_loop()
+        cd = res.factors @ res.loadings.T
+        agree = {"z_max_abs_diff": float(np.max(np.abs(zl - res.x_standardized))),
+                 "common_rel_diff": float(np.linalg.norm(cl - cd) / np.linalg.norm(cd))}
+        reps = max(args.reps, 5)
+        td, th = [], []
+        for _ in range(reps):   # alternating; every call ends in a stream synchronise (host clock)
+            t0 = time.perf_counter()
+            for _ in range(5):
+                device()
+            t1 = time.perf_counter()
+            host_loop()
+            t2 = time.perf_counter()
+            td.append((t1 - t0) / 5)
+            th.append(t2 - t1)
+        ctx.reset_timing()
+        ctx.enable_timing(True)
+        device()
+        ctx.enable_timing(False)
+        split = {k: [round(v[0], 4), int(v[1])] for k, v in ctx.read_timing().items() if v[1]}
+        ms = lambda v: {"median": round(float(np.median(v)) * 1e3, 3), "min": round(min(v) * 1e3, 3),   # noqa: E731
+                        "max": round(max(v) * 1e3, 3)}
+        out["shapes"][name] = {"T": T, "N": N, "missing_share": round(float((~obs).mean()), 4), "iterations": iters,
+                               "converged": res.converged, "em_factors_ms": ms(td), "host_loop_ms": ms(th),
+                               "ratio": round(float(np.median(th) / np.median(td)), 2),
+                               "kernel_ms_and_launches_by_class": split, "agreement": agree}
+    out["value"] = out["shapes"]["fred_md_like"]["ratio"]
+    return out
 
 
 def main():
