@@ -642,7 +642,7 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
       }
       Scope sc(ctx, DFM_KC_EIG_OTHER);
       HIPCHK(ctx, launch_spectrum(Gp, m, (int64_t)m * m, m, n, pEv.p, pWk.p, st));
-      hipLaunchKernelGGL(tail_sigma2_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pEv.p, m, (m + 1) / 2, n,
+      hipLaunchKernelGGL(tail_sigma2_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pEv.p, m, n,
                          (double)N * (double)T, pSig.p);
     }
     {

@@ -333,27 +333,12 @@ int dfm_full_spectrum_max(void) { return spectrum_any_max(); }
 int dfm_ic_sweep(const double *eig, int n_eig, int kmax, double trace, int64_t T, int64_t N,
                  double sigma2, double *out) {
   if (!eig || !out || kmax < 1 || n_eig < kmax || T < 1 || N < 1) return -1;
-  const int m = (int)std::min(T, N);
-  if (sigma2 < 0) {
-    const int kh = ceil_half(m);
-    if (n_eig < kh) return -2;
-    double s = trace;
-    for (int j = 0; j < kh; ++j) s -= eig[j];
-    sigma2 = s / ((double)N * (double)T);
+  if (sigma2 < 0) {   // the trace minus the top ceil(m/2) eigenvalues
+    const int m = (int)std::min(T, N);
+    if (n_eig < ceil_half(m)) return -2;
+    sigma2 = sigma2_minus_top(trace, eig, m, (double)N * (double)T);
   }
-  const double c = (double)(N + T) / ((double)N * (double)T);
-  double cum = trace;
-  for (int k = 1; k <= kmax; ++k) {
-    cum -= eig[k - 1];
-    const double V = cum / ((double)N * (double)T);
-    out[0 * kmax + k - 1] = V + k * sigma2 * c * std::log(1.0 / c);
-    out[1 * kmax + k - 1] = V + k * sigma2 * c * std::log((double)m);
-    out[2 * kmax + k - 1] = V + k * sigma2 * std::log((double)m) / m;
-    out[3 * kmax + k - 1] = std::log(V) + k * c * std::log(1.0 / c);
-    out[4 * kmax + k - 1] = std::log(V) + k * c * std::log((double)m);
-    out[5 * kmax + k - 1] = std::log(V) + k * std::log((double)m) / m;
-    out[6 * kmax + k - 1] = V + k * std::log((double)T) / T;
-  }
+  criteria_sweep(eig, kmax, trace, sigma2, T, N, out);
   return 0;
 }
 

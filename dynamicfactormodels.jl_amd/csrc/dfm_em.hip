@@ -38,7 +38,7 @@ constexpr int EM_SW = 16;   // strip width: 16 doubles = one 128-B line per row
 // lines of the row-major panels); thread tid touches the same elements
 // (row tid >> 3 and + 32, column pair tid & 7) in every pass, so it reads back
 // only X2 values it wrote itself.  The statistics are normalize_cols_kernel's
-// (dfm_fit.hip): wave w owns columns 4 w .. 4 w + 3 of the strip, lane l sums
+// (dfm_panel.hip): wave w owns columns 4 w .. 4 w + 3 of the strip, lane l sums
 // rows l, l + 64, ... in order, wave_sum, the variance accumulated with fma
 // around the mean, z = (x - mu) / sd — bit-identical to dfm_normalize_dev for
 // a panel without a missing entry.
@@ -322,21 +322,11 @@ int em_core(dfm_ctx *ctx, const double *X, int64_t T64, int64_t N64, int64_t ldx
   // PCA of the resident Z and the common component over run.Cp; reads back the
   // iteration's scalars.  warm: start from the previous solve's vectors.
   auto step = [&](bool warm) -> int {
-    {
-      Scope sc(ctx, DFM_KC_GRAM);
-      HIPCHK(ctx, launch_gram(orient, src, m, orient == 0 ? N : T, T, run.G, m, (int64_t)m * m, 1, st));
-    }
-    EigArgs ea;
-    ea.nb = 1; ea.k = k; ea.p = p;
-    ea.warm = warm ? run.Uk[run.cur] : nullptr;
-    ea.kw = warm ? k : 0;
-    ea.tol = std::min(ctx->tol, 1e-14);   // a single fit's rule (run_eig, dfm_fit.hip)
-    ea.maxit = ctx->maxit; ea.poll = ctx->poll;
-    ea.ws = run.ews;
-    ea.lam = run.lam; ea.Uk = run.Uk[run.cur ^ 1]; ea.trace_out = run.tr; ea.status = status;
-    ea.st = st; ea.tf = timer_cb; ea.tctx = ctx;
-    const int erc = eig_run(run.G, m, (int64_t)m * m, m, ea, nullptr, 0);
-    if (erc != 0) return fail(ctx, erc > 0 ? erc : -21, "eigensolver failed (%d)", erc);
+    HIPCHK(ctx, panel_gram(ctx, orient, src, T, N, run.G));
+    // (the run's own workspace: no allocation, free or synchronise per solve)
+    if ((rc = run_eig(ctx, run.G, m, k, run.lam, run.Uk[run.cur ^ 1], run.tr, status, run.ews,
+                      warm ? run.Uk[run.cur] : nullptr)))
+      return rc;
     run.cur ^= 1;
     const double *U = run.Uk[run.cur];
     if (select) {   // r^ = first arg-min of crit over 1..k on this Z: the k eigenvalues and the trace
@@ -348,10 +338,7 @@ int em_core(dfm_ctx *ctx, const double *X, int64_t T64, int64_t N64, int64_t ldx
       if (islot[1]) return fail(ctx, 2, "eigensolver did not converge");
       std::vector<double> ic((size_t)7 * k);
       dfm_ic_sweep(slot + 3, k, k, slot[2], T, N, NAN, ic.data());
-      int best = 0;
-      for (int j = 1; j < k; ++j)
-        if (ic[(size_t)crit * k + j] < ic[(size_t)crit * k + best]) best = j;
-      r = best + 1;
+      r = first_argmin(&ic[(size_t)crit * k], k);
     }
     if (r < k) {   // the first r of the k vectors, contiguous
       HIPCHK(ctx, hipMemcpy2DAsync(run.Ur, (size_t)r * 8, U, (size_t)k * 8, (size_t)r * 8, m, hipMemcpyDeviceToDevice,
@@ -421,15 +408,6 @@ int em_core(dfm_ctx *ctx, const double *X, int64_t T64, int64_t N64, int64_t ldx
   return 0;
 }
 
-int rows_to_host_colmajor(dfm_ctx *ctx, const double *src, int rows, int cols, double *dst) {
-  std::vector<double> tmp((size_t)rows * cols);
-  HIPCHK(ctx, hipMemcpyAsync(tmp.data(), src, tmp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < rows; ++i)
-    for (int j = 0; j < cols; ++j) dst[(size_t)j * rows + i] = tmp[(size_t)i * cols + j];
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -448,8 +426,8 @@ int dfm_em(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, con
   if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, run.mu, (size_t)N * 8, hipMemcpyDeviceToHost, st));
   if (sd) HIPCHK(ctx, hipMemcpyAsync(sd, run.sd, (size_t)N * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  if (F && (rc = rows_to_host_colmajor(ctx, run.F, (int)T, run.r, F))) return rc;
-  if (L && (rc = rows_to_host_colmajor(ctx, run.L, (int)N, run.r, L))) return rc;
+  if (F && (rc = read_rows_colmajor(ctx, run.F, (int)T, run.r, F))) return rc;
+  if (L && (rc = read_rows_colmajor(ctx, run.L, (int)N, run.r, L))) return rc;
   if (eigvals) std::copy(run.hlam.begin(), run.hlam.begin() + run.r, eigvals);
   if (info) *info = run.info;
   return 0;

@@ -1,85 +1,18 @@
 // dfm_fit.hip — the fit and everything read from or computed on a fitted
 // model: dfm_model_fit(_breaks), the model readers / setters, destroy and
-// clone, the stand-alone PCA / spectrum / criterion / Chow / hard-threshold
-// entry points, predict / get_factors and normalize.
+// clone, the model-level criterion / Chow / hard-threshold entry points and
+// predict / get_factors.  (The steps over a bare panel are in dfm_panel.hip.)
 #include "dfm_host.h"
 
-// ---------------------------------------------------------------- internals
-// Top-k eigen-decomposition of nb Grams + trace; G workspace provided.
-static int run_eig(dfm_ctx *ctx, const double *G, int m, int nb, int k, const double *warm, int kw,
-                   double *lam, double *Uk, double *trace, int *status_dev) {
-  const int p = eig_block_p(m, k, ctx->block);
-  if ((p > 32 || p < k) && nb == 1 && m >= 2 && m <= dense_eig_max()) {
-    // k beyond the subspace block: tridiagonalisation + inverse iteration (dfm_spec.hip)
-    double *wk = nullptr;
-    HIPCHK(ctx, hipMalloc(&wk, (size_t)dense_eig_work(m, k) * 8));
-    hipError_t e;
-    {
-      Scope sc(ctx, DFM_KC_EIG_OTHER);
-      e = launch_dense_eig(G, m, m, k, lam, Uk, trace, status_dev, wk, ctx->stream);
-    }
-    hipStreamSynchronize(ctx->stream);
-    hipFree(wk);
-    if (e != hipSuccess) return fail(ctx, 1000 + (int)e, "dense eigensolver: %s", hipGetErrorString(e));
-    return 0;
-  }
-  if (p > 32 || p < k) return fail(ctx, -20, "eigensolver block %d unsupported for k=%d m=%d", p, k, m);
-  const int P = p <= 16 ? 16 : 32;
-  const size_t bytes = eig_workspace_bytes_padded(m, nb, P, ctx->maxit);
-  char *ws = nullptr;   // stream-ordered pool memory: no device-wide sync in the free
-  HIPCHK(ctx, stream_malloc((void **)&ws, bytes, ctx->stream));
-  // a single fit's eigenvectors are polished to the rounding floor (the
-  // residual rule at 1e-14; the floor and stagnation tests end it): statistics
-  // of the fit with a near-zero value (an LR of ~0.4 between two nearly equal
-  // SSRs) move by ~1e-10 relative when its eigenvectors stop at 1e-12 of the
-  // gap (a break fit's LR in tests/test_gpu_breaks.py: 4e-10 off the oracle;
-  // the tridiagonal path's inverse-iteration vectors: 9e-10)
-  const double tol = nb == 1 ? std::min(ctx->tol, 1e-14) : ctx->tol;
-  EigArgs ea;
-  ea.nb = nb; ea.k = k; ea.p = p;
-  ea.warm = warm; ea.kw = kw;
-  ea.tol = tol; ea.maxit = ctx->maxit; ea.poll = ctx->poll;
-  ea.ws = ws;
-  ea.lam = lam; ea.Uk = Uk; ea.trace_out = trace; ea.status = status_dev;
-  ea.st = ctx->stream; ea.tf = timer_cb; ea.tctx = ctx;
-  int rc = eig_run(G, m, (int64_t)m * m, m, ea, nullptr, 0);
-  hipFreeAsync(ws, ctx->stream);
-  hipStreamSynchronize(ctx->stream);
-  if (rc != 0) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
-  return 0;
-}
-
-namespace dfm {
-// X column-major T x N (leading dimension ldx) in host memory, or already in
-// HBM when dev (then it is transposed in place of the copy, never duplicated)
-int upload_panel(dfm_ctx *ctx, const double *X, int T, int N, int64_t ldx, DevPanel &dp, bool dev) {
-  hipStream_t st = ctx->stream;
-  dp.ld = round_up(N, 16);
-  dp.st = st;
-  HIPCHK(ctx, stream_malloc((void **)&dp.P, (size_t)T * dp.ld * 8, st));
-  const double *src = X;
-  int64_t lds = ldx;
-  if (!dev) {
-    HIPCHK(ctx, stream_malloc((void **)&dp.raw, (size_t)T * N * 8, st));
-    HIPCHK(ctx, hipMemcpy2DAsync(dp.raw, (size_t)T * 8, X, (size_t)ldx * 8, (size_t)T * 8, N,
-                                 hipMemcpyHostToDevice, st));
-    src = dp.raw;
-    lds = T;
-  }
-  hipLaunchKernelGGL(panel_from_colmajor_kernel, dim3((unsigned)((dp.ld + 31) / 32), (T + 31) / 32),
-                     dim3(256), 0, st, src, lds, T, N, dp.P, dp.ld);
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-}  // namespace dfm
-static void rows_to_colmajor_host(const std::vector<double> &src, int rows, int cols, double *dst) {
-  for (int i = 0; i < rows; ++i)
-    for (int j = 0; j < cols; ++j) dst[(size_t)j * rows + i] = src[(size_t)i * cols + j];
-}
-
-// dfm_model_fit_breaks: a failed step frees the temporaries and the model (bail)
-#define CKB(x) do { int r_ = (x); if (r_) return bail(r_); } while (0)
-#define TALLOC(p, n) do { HIPCHK_BAIL(ctx, dalloc(&(p), (n))); tmp.push_back((double *)(p)); } while (0)
+// the half-built model of a fit: destroyed on every return that does not release it
+struct ModelGuard {
+  dfm_model *m;
+  explicit ModelGuard(dfm_model *m_) : m(m_) {}
+  ModelGuard(const ModelGuard &) = delete;
+  ModelGuard &operator=(const ModelGuard &) = delete;
+  ~ModelGuard() { if (m) dfm_model_destroy(m); }
+  dfm_model *release() { dfm_model *r = m; m = nullptr; return r; }
+};
 
 extern "C" {
 
@@ -144,6 +77,7 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
   const int T = (int)T64, N = (int)N64, m = std::min(T, N);
   const int mfn = ceil_half(m);  // max_factor_number, src/DynamicFactorModel.jl:101
   dfm_model *M = new dfm_model();
+  ModelGuard guard(M);   // declared before the temporaries: they are freed first
   ++ctx->refs;
   M->ctx = ctx; M->T = T; M->N = N; M->q = q; M->crit = crit; M->m = m;
   // src/DynamicFactorModel.jl:77 (T >= N) vs :86 (N > T), with the FULL-sample
@@ -159,62 +93,31 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
     M->bm.push_back(M->orient == 0 ? e - a : N);   // size of the block's Gram
   }
   const bool nob = nblk == 1;
-  std::vector<double *> Gb(nblk, nullptr), lamd(nblk, nullptr), Ukd(nblk, nullptr);
-  std::vector<double *> tmp;   // freed on every exit path below
-  auto tfree = [&]() {
-    for (int j = 0; j < nblk; ++j) {
-      if (!nob) hipFree(Gb[j]);
-      hipFree(lamd[j]); hipFree(Ukd[j]);
-      Gb[j] = lamd[j] = Ukd[j] = nullptr;
-    }
-    for (double *p : tmp) hipFree(p);
-    tmp.clear();
-  };
-  auto bail = [&](int code) { tfree(); dfm_model_destroy(M); return code; };
+  // per block: the Gram (block 0 borrows Gfull when there are no breaks) and the eigenpairs of the last solve
+  std::vector<const double *> Gb(nblk, nullptr);
+  std::vector<DevBuf<>> Gown(nblk), lamd(nblk), Ukd(nblk);
+  DevBuf<> Xraw, Gfull, tr_d;
+  DevBuf<int> st_d;
   const size_t panel = (size_t)T * M->ld;
-  HIPCHK_BAIL(ctx, dalloc(&M->Xp, panel));
-  HIPCHK_BAIL(ctx, dalloc(&M->Cp, panel));
-  HIPCHK_BAIL(ctx, dalloc(&M->Ep, panel));
-  HIPCHK_BAIL(ctx, dalloc(&M->y, T));
-  HIPCHK_BAIL(ctx, dalloc(&M->w, (size_t)T * std::max(q, 1)));
-  double *Xraw = nullptr;
-  TALLOC(Xraw, (size_t)T * N);
+  HIPCHK(ctx, dalloc(&M->Xp, panel));
+  HIPCHK(ctx, dalloc(&M->Cp, panel));
+  HIPCHK(ctx, dalloc(&M->Ep, panel));
+  HIPCHK(ctx, dalloc(&M->y, T));
+  HIPCHK(ctx, dalloc(&M->w, (size_t)T * std::max(q, 1)));
+  HIPCHK(ctx, Xraw.alloc((size_t)T * N));
   // host or device inputs (hipMemcpyDefault: the windows driver refits from a resident panel)
-  HIPCHK_BAIL(ctx, hipMemcpy2DAsync(Xraw, (size_t)T * 8, X, (size_t)ldx * 8, (size_t)T * 8, N, hipMemcpyDefault, st));
-  HIPCHK_BAIL(ctx, hipMemcpyAsync(M->y, y, (size_t)T * 8, hipMemcpyDefault, st));
+  HIPCHK(ctx, hipMemcpy2DAsync(Xraw.p, (size_t)T * 8, X, (size_t)ldx * 8, (size_t)T * 8, N, hipMemcpyDefault, st));
+  HIPCHK(ctx, hipMemcpyAsync(M->y, y, (size_t)T * 8, hipMemcpyDefault, st));
   if (q > 0)
-    HIPCHK_BAIL(ctx, hipMemcpy2DAsync(M->w, (size_t)T * 8, w, (size_t)ldw * 8, (size_t)T * 8, q, hipMemcpyDefault, st));
+    HIPCHK(ctx, hipMemcpy2DAsync(M->w, (size_t)T * 8, w, (size_t)ldw * 8, (size_t)T * 8, q, hipMemcpyDefault, st));
   {
     Scope sc(ctx, DFM_KC_MISC);
     hipLaunchKernelGGL(panel_from_colmajor_kernel, dim3((unsigned)((M->ld + 31) / 32), (T + 31) / 32),
-                       dim3(256), 0, st, Xraw, (int64_t)T, T, N, M->Xp, M->ld);
+                       dim3(256), 0, st, Xraw.p, (int64_t)T, T, N, M->Xp, M->ld);
   }
-  HIPCHK_BAIL(ctx, hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   // block j's panel: rows ba[j] .. ba[j] + bt[j] - 1 of X
   auto block_src = [&](int j) { return PanelSrc{nullptr, M->Xp + (size_t)M->ba[j] * M->ld, nullptr, nullptr, M->ld, 0}; };
-  auto block_gram = [&](int j, double *G) -> hipError_t {
-    Scope sc(ctx, DFM_KC_GRAM);
-    return launch_gram(M->orient, block_src(j), M->bm[j], M->orient == 0 ? N : M->bt[j], M->bt[j], G,
-                       M->bm[j], (int64_t)M->bm[j] * M->bm[j], 1, st);
-  };
-  auto spectrum = [&](const double *G, int mm, std::vector<double> &sp) -> int {
-    double *ev = nullptr;
-    HIPCHK(ctx, dalloc(&ev, mm));
-    tmp.push_back(ev);
-    double *wk = nullptr;
-    if (spectrum_work(mm, 1) > 0) {
-      HIPCHK(ctx, dalloc(&wk, (size_t)spectrum_work(mm, 1)));
-      tmp.push_back(wk);
-    }
-    {
-      Scope sc(ctx, DFM_KC_EIG_OTHER);
-      HIPCHK(ctx, launch_spectrum(G, mm, (int64_t)mm * mm, mm, 1, ev, wk, st));
-    }
-    sp.resize(mm);
-    HIPCHK(ctx, hipMemcpyAsync(sp.data(), ev, (size_t)mm * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
-  };
   const bool pcp = crit >= 0 && crit <= 2;
   if (kmax <= 0) kmax = mfn;  // src/DynamicFactorModel.jl:54 (D11)
   kmax = std::min(kmax, mfn);
@@ -222,49 +125,38 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
   const double NT = (double)N * (double)T;
   // --- PCp's sigma^2 = V(ceil(m/2)) of the UNRESTRICTED fit DynamicFactorModel(y, w, x):
   // full sample, no breaks (src/criteria.jl:18, :23, :28)
-  double *Gfull = nullptr;
   std::vector<double> spec_full;
   // the sweep reports all 7 criteria: PCp rows need sigma^2 (NaN when the full
   // spectrum is out of reach and the chosen criterion is not a PCp one)
   const bool full_spec = pcp || (nob && r <= 0 && (kmax > 24 || m <= spectrum_max()));
-  if (full_spec && m > spectrum_any_max()) {
-    return bail(fail(ctx, -30, "PCp criteria / kmax > 24 need the full spectrum; supported for "
-                               "min(T,N) <= %d (got %d)", spectrum_any_max(), m));
-  }
+  if (full_spec && m > spectrum_any_max())
+    return fail(ctx, -30, "PCp criteria / kmax > 24 need the full spectrum; supported for "
+                          "min(T,N) <= %d (got %d)", spectrum_any_max(), m);
+  int rc = 0;
   if (nob || full_spec) {
-    TALLOC(Gfull, (size_t)m * m);
-    PanelSrc src{nullptr, M->Xp, nullptr, nullptr, M->ld, 0};
-    Scope sc(ctx, DFM_KC_GRAM);
-    HIPCHK_BAIL(ctx, launch_gram(M->orient, src, m, M->orient == 0 ? N : T, T, Gfull, m, (int64_t)m * m, 1, st));
+    HIPCHK(ctx, Gfull.alloc((size_t)m * m));
+    HIPCHK(ctx, panel_gram(ctx, M->orient, PanelSrc{nullptr, M->Xp, nullptr, nullptr, M->ld, 0}, T, N, Gfull.p));
   }
   if (full_spec) {
-    CKB(spectrum(Gfull, m, spec_full));
-    double s = 0.0;
-    for (double v : spec_full) s += v;
-    for (int j = 0; j < mfn; ++j) s -= spec_full[j];
-    M->sigma2 = s / NT;
+    if ((rc = gram_spectrum(ctx, Gfull.p, m, spec_full))) return rc;
+    M->sigma2 = sigma2_total_minus_top(spec_full.data(), m, NT);
   }
   // --- per block: Gram, the eigenvalues the sweep needs, trace
   std::vector<int> kk(nblk, 0);
   std::vector<std::vector<double>> bev(nblk), blam(nblk);
   std::vector<double> btr(nblk, 0.0);
-  double *tr_d = nullptr;
-  int *st_d = nullptr;
-  TALLOC(tr_d, 1);
-  HIPCHK_BAIL(ctx, dalloc(&st_d, 1));
-  tmp.push_back((double *)st_d);
+  HIPCHK(ctx, tr_d.alloc(1));
+  HIPCHK(ctx, st_d.alloc(1));
   auto top_eig = [&](int j, int k) -> int {
-    hipFree(lamd[j]); hipFree(Ukd[j]);
-    lamd[j] = Ukd[j] = nullptr;
-    HIPCHK(ctx, dalloc(&lamd[j], k)); HIPCHK(ctx, dalloc(&Ukd[j], (size_t)M->bm[j] * k));
+    HIPCHK(ctx, lamd[j].alloc(k)); HIPCHK(ctx, Ukd[j].alloc((size_t)M->bm[j] * k));
     kk[j] = k;
-    int rc2 = run_eig(ctx, Gb[j], M->bm[j], 1, k, nullptr, 0, lamd[j], Ukd[j], tr_d, st_d);
+    int rc2 = run_eig(ctx, Gb[j], M->bm[j], k, lamd[j].p, Ukd[j].p, tr_d.p, st_d.p);
     if (rc2) return rc2;
     int est = 0;
     blam[j].resize(k);
-    HIPCHK(ctx, hipMemcpyAsync(blam[j].data(), lamd[j], (size_t)k * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(&btr[j], tr_d, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(&est, st_d, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(blam[j].data(), lamd[j].p, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(&btr[j], tr_d.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(&est, st_d.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (est) return fail(ctx, 2, "eigensolver did not converge");
     return 0;
@@ -273,33 +165,33 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
   for (int j = 0; j < nblk; ++j) {
     // the reference slices F_j[:, 1:k] (:33, :131): a block needs >= k eigenpairs
     if (M->bm[j] < r_req)
-      CKB(fail(ctx, -9, "break block %d has %d rows: fewer than the %d factors requested", j, M->bt[j], r_req));
-    if (nob) Gb[j] = Gfull;
+      return fail(ctx, -9, "break block %d has %d rows: fewer than the %d factors requested", j, M->bt[j], r_req);
+    if (nob) Gb[j] = Gfull.p;
     else {
-      CKB(dalloc(&Gb[j], (size_t)M->bm[j] * M->bm[j]) == hipSuccess ? 0 : fail(ctx, 1002, "out of memory"));
-      CKB(block_gram(j, Gb[j]) == hipSuccess ? 0 : fail(ctx, 1001, "block Gram failed"));
+      if (Gown[j].alloc((size_t)M->bm[j] * M->bm[j]) != hipSuccess) return fail(ctx, 1002, "out of memory");
+      if (panel_gram(ctx, M->orient, block_src(j), M->bt[j], N, Gown[j].p) != hipSuccess)
+        return fail(ctx, 1001, "block Gram failed");
+      Gb[j] = Gown[j].p;
     }
     if (r <= 0) {   // the sweep's eigenvalues of this block
       if (nob && full_spec) bev[j] = spec_full;
       else if (!nob && M->bm[j] <= spectrum_any_max() && (kmax > 24 || pcp)) {
-        std::vector<double> sp;
-        CKB(spectrum(Gb[j], M->bm[j], sp));
-        bev[j] = sp;
+        if ((rc = gram_spectrum(ctx, Gb[j], M->bm[j], bev[j]))) return rc;
       } else if (kmax > 24) {
-        CKB(fail(ctx, -30, "kmax > 24 needs the full spectrum of every block; supported for Gram "
-                           "size <= %d (block %d: %d)", spectrum_any_max(), j, M->bm[j]));
+        return fail(ctx, -30, "kmax > 24 needs the full spectrum of every block; supported for Gram "
+                              "size <= %d (block %d: %d)", spectrum_any_max(), j, M->bm[j]);
       }
       if (bev[j].empty()) {   // top-k pairs: the sweep's eigenvalues and the trace
-        CKB(top_eig(j, kmax));
+        if ((rc = top_eig(j, kmax))) return rc;
         bev[j] = blam[j];
       } else {                // a spectrum gave the eigenvalues: only the trace (the Gram's diagonal)
         hipLaunchKernelGGL(eig_trace_kernel, dim3(1), dim3(64), 0, st, Gb[j], (int64_t)M->bm[j],
-                           (int64_t)M->bm[j] * M->bm[j], M->bm[j], tr_d);
-        HIPCHK_BAIL(ctx, hipMemcpyAsync(&btr[j], tr_d, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK_BAIL(ctx, hipStreamSynchronize(st));
+                           (int64_t)M->bm[j] * M->bm[j], M->bm[j], tr_d.p);
+        HIPCHK(ctx, hipMemcpyAsync(&btr[j], tr_d.p, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
       }
     } else {
-      CKB(top_eig(j, r_req));
+      if ((rc = top_eig(j, r_req))) return rc;
       bev[j] = blam[j];
     }
   }
@@ -314,15 +206,12 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
     M->swept = true;
     M->ic.assign(7 * kmax, 0.0);
     dfm_ic_sweep(ev.data(), (int)ev.size(), kmax, trace, T, N, full_spec ? M->sigma2 : NAN, M->ic.data());
-    int best = 0;
-    for (int k = 1; k < kmax; ++k)   // first argmin, indmin (src/DynamicFactorModel.jl:65)
-      if (M->ic[crit * kmax + k] < M->ic[crit * kmax + best]) best = k;
-    r = best + 1;
+    r = first_argmin(&M->ic[(size_t)crit * kmax], kmax);
   }
   r = std::min(r, mfn);   // src/DynamicFactorModel.jl:116-119
   M->r = r;
   for (int j = 0; j < nblk; ++j)
-    if (r > kk[j]) CKB(top_eig(j, r));   // the sweep used spectra: now the r eigenvectors
+    if (r > kk[j] && (rc = top_eig(j, r))) return rc;   // the sweep used spectra: now the r eigenvectors
   // eigenvalues reported: kmax of the sweep (when it ran) or r; per block summed
   {
     const size_t ne = (size_t)(M->swept ? std::max(kmax, r) : r);
@@ -338,38 +227,37 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
   }
   M->k_eig = kk[0];
   // --- factors, loadings per block for r (first r canonical eigenvectors)
-  HIPCHK_BAIL(ctx, dalloc(&M->F, (size_t)T * r));
-  HIPCHK_BAIL(ctx, dalloc(&M->colssr, N));
+  HIPCHK(ctx, dalloc(&M->F, (size_t)T * r));
+  HIPCHK(ctx, dalloc(&M->colssr, N));
   M->Ubs.assign(nblk, nullptr);
   M->Ls.assign(nblk, nullptr);
-  HIPCHK_BAIL(ctx, dalloc(&M->Lall, (size_t)nblk * N * r));
+  HIPCHK(ctx, dalloc(&M->Lall, (size_t)nblk * N * r));
   for (int j = 0; j < nblk; ++j) {
     const int mj = M->bm[j];
-    HIPCHK_BAIL(ctx, dalloc(&M->Ubs[j], (size_t)mj * r));
+    HIPCHK(ctx, dalloc(&M->Ubs[j], (size_t)mj * r));
     M->Ls[j] = M->Lall + (size_t)j * N * r;
     if (j == 0) { M->Ub = M->Ubs[0]; M->L = M->Ls[0]; }
-    HIPCHK_BAIL(ctx, hipMemcpy2DAsync(M->Ubs[j], (size_t)r * 8, Ukd[j], (size_t)kk[j] * 8, (size_t)r * 8, mj,
-                        hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpy2DAsync(M->Ubs[j], (size_t)r * 8, Ukd[j].p, (size_t)kk[j] * 8, (size_t)r * 8, mj,
+                                 hipMemcpyDeviceToDevice, st));
   }
   for (int j = 0; j < nblk; ++j) {
     Scope sc(ctx, DFM_KC_FACTORS);
     if (r <= 32) {
       if (launch_factors(M->orient, block_src(j), M->bt[j], N, r, 1, M->Ubs[j], M->F + (size_t)M->ba[j] * r,
                          M->Ls[j], nob ? M->colssr : nullptr, st, (double)T, 0))
-        CKB(fail(ctx, -4, "r=%d too large", r));
+        return fail(ctx, -4, "r=%d too large", r);
     } else if (launch_factors_wide(M->orient, M->Xp + (size_t)M->ba[j] * M->ld, M->ld, M->bt[j], N, r, M->Ubs[j],
                                    M->F + (size_t)M->ba[j] * r, M->Ls[j], nob ? M->colssr : nullptr, st,
                                    (double)T)) {
-      CKB(fail(ctx, 1001, "factor kernels failed"));
+      return fail(ctx, 1001, "factor kernels failed");
     }
     if (nob && M->orient == 1) {
-      double *lr = nullptr;
-      HIPCHK_BAIL(ctx, dalloc(&lr, r));
-      HIPCHK_BAIL(ctx, hipMemcpyAsync(lr, lamd[0], (size_t)r * 8, hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(colssr_cols_kernel, dim3((N + 255) / 256, 1), dim3(256), 0, st, Gfull, m,
-                         (int64_t)m * m, N, r, lr, M->Ub, M->colssr);
-      HIPCHK_BAIL(ctx, hipStreamSynchronize(st));
-      hipFree(lr);
+      DevBuf<> lr;
+      HIPCHK(ctx, lr.alloc(r));
+      HIPCHK(ctx, hipMemcpyAsync(lr.p, lamd[0].p, (size_t)r * 8, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(colssr_cols_kernel, dim3((N + 255) / 256, 1), dim3(256), 0, st, Gfull.p, m,
+                         (int64_t)m * m, N, r, lr.p, M->Ub, M->colssr);
+      HIPCHK(ctx, hipStreamSynchronize(st));
     }
   }
   for (int j = 0; j < nblk; ++j) {   // :33 per subperiod
@@ -379,53 +267,47 @@ int dfm_model_fit_breaks(dfm_ctx *ctx, const double *y, const double *w, int q, 
                        st, M->Xp + o, M->ld, M->bt[j], N, r, M->F + (size_t)M->ba[j] * r, M->Ls[j], M->Cp + o,
                        M->Ep + o);
   }
-  HIPCHK_BAIL(ctx, hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   if (!nob)
     hipLaunchKernelGGL(col_ssq_kernel, dim3((N + 255) / 256), dim3(256), 0, st, M->Ep, M->ld, T, N, M->colssr);
   // --- V(r) by brute force over the explicit residual panel (src/criteria.jl:5)
   double essq = 0.0;
-  {
-    double *rows = nullptr, *tot = nullptr;
-    TALLOC(rows, T); TALLOC(tot, 1);
-    hipLaunchKernelGGL(panel_row_ssq_kernel, dim3(T), dim3(256), 0, st, M->Ep, M->ld, T, rows);
-    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, st, rows, T, tot);
-    HIPCHK_BAIL(ctx, hipMemcpyAsync(&essq, tot, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK_BAIL(ctx, hipStreamSynchronize(st));
-  }
+  DevBuf<> rows, tot;
+  HIPCHK(ctx, rows.alloc(T)); HIPCHK(ctx, tot.alloc(1));
+  hipLaunchKernelGGL(panel_row_ssq_kernel, dim3(T), dim3(256), 0, st, M->Ep, M->ld, T, rows.p);
+  hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, st, rows.p, T, tot.p);
+  HIPCHK(ctx, hipMemcpyAsync(&essq, tot.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   // --- OLS + HC2 on [w vcat(F_j)] (:40-48, :130-133)
   const int d = q + r;
-  if (d > T) return bail(fail(ctx, -5, "q + r = %d regressors exceed the %d observations", d, T));
-  double *coef = nullptr, *tst = nullptr, *cov = nullptr, *res = nullptr;
-  int *ost = nullptr;
-  TALLOC(coef, d); TALLOC(tst, d); TALLOC(cov, (size_t)d * d); TALLOC(res, T);
-  HIPCHK_BAIL(ctx, dalloc(&ost, 1));
-  tmp.push_back((double *)ost);
+  if (d > T) return fail(ctx, -5, "q + r = %d regressors exceed the %d observations", d, T);
+  DevBuf<> coef, tst, cov, res, wk;
+  DevBuf<int> ost;
+  HIPCHK(ctx, coef.alloc(d)); HIPCHK(ctx, tst.alloc(d)); HIPCHK(ctx, cov.alloc((size_t)d * d));
+  HIPCHK(ctx, res.alloc(T)); HIPCHK(ctx, ost.alloc(1));
   if (d <= 32) {
     Scope sc(ctx, DFM_KC_OLS);
-    launch_ols(1, st, M->y, M->w, q, M->F, T, r, nullptr, nullptr, coef,
-                       tst, cov, res, ost);
+    launch_ols(1, st, M->y, M->w, q, M->F, T, r, nullptr, nullptr, coef.p, tst.p, cov.p, res.p, ost.p);
   } else {   // wide design: GEMM-built OLS (dfm_wide.hip)
-    double *wk = nullptr;
-    TALLOC(wk, (size_t)ols_wide_work(T, d));
+    HIPCHK(ctx, wk.alloc((size_t)ols_wide_work(T, d)));
     Scope sc(ctx, DFM_KC_OLS);
-    HIPCHK_BAIL(ctx, launch_ols_wide(M->y, M->w, q, M->F, T, r, coef, tst, cov, res, ost, wk, st));
+    HIPCHK(ctx, launch_ols_wide(M->y, M->w, q, M->F, T, r, coef.p, tst.p, cov.p, res.p, ost.p, wk.p, st));
   }
-  HIPCHK_BAIL(ctx, hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   M->coef.resize(d); M->tstat.resize(d); M->cov.resize((size_t)d * d); M->resid.resize(T);
   int ols_bad = 0;
-  HIPCHK_BAIL(ctx, hipMemcpyAsync(M->coef.data(), coef, (size_t)d * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK_BAIL(ctx, hipMemcpyAsync(M->tstat.data(), tst, (size_t)d * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK_BAIL(ctx, hipMemcpyAsync(M->cov.data(), cov, (size_t)d * d * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK_BAIL(ctx, hipMemcpyAsync(M->resid.data(), res, (size_t)T * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK_BAIL(ctx, hipMemcpyAsync(&ols_bad, ost, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK_BAIL(ctx, hipStreamSynchronize(st));
-  tfree();
-  if (ols_bad) return bail(fail(ctx, 3, "singular design matrix D'D"));
+  HIPCHK(ctx, hipMemcpyAsync(M->coef.data(), coef.p, (size_t)d * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(M->tstat.data(), tst.p, (size_t)d * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(M->cov.data(), cov.p, (size_t)d * d * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(M->resid.data(), res.p, (size_t)T * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(&ols_bad, ost.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  if (ols_bad) return fail(ctx, 3, "singular design matrix D'D");
   M->trace = trace;
   M->V = essq / NT;
-  if (crit >= 0) M->critval = crit_formula(crit, M->V, r, M->sigma2, T, N);
-  HIPCHK_BAIL(ctx, dalloc(&M->flag_dev, 4));
-  *out = M;
+  if (crit >= 0) M->critval = criterion(crit, M->V, r, M->sigma2, T, N);
+  HIPCHK(ctx, dalloc(&M->flag_dev, 4));
+  *out = guard.release();
   return 0;
 }
 
@@ -438,13 +320,8 @@ int dfm_model_block(const dfm_model *m, int j, int64_t *row0, int64_t *rows, dou
   if (rows) *rows = m->bt[j];
   if (eigvals) std::copy(m->blam[j].begin(), m->blam[j].end(), eigvals);
   if (L) {
-    dfm_ctx *ctx = m->ctx;
-    hipSetDevice(ctx->device);
-    std::vector<double> tmp((size_t)m->N * m->r);
-    HIPCHK(ctx, hipMemcpyAsync(tmp.data(), m->Ls[j], tmp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < m->N; ++i)
-      for (int c = 0; c < m->r; ++c) L[(size_t)c * m->N + i] = tmp[(size_t)i * m->r + c];
+    hipSetDevice(m->ctx->device);
+    return read_rows_colmajor(m->ctx, m->Ls[j], m->N, m->r, L);
   }
   return 0;
 }
@@ -472,33 +349,21 @@ int dfm_model_read(const dfm_model *m, double *eigvals, double *coef, double *ts
   dfm_ctx *ctx = m->ctx;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
-  const int d = m->q + m->r;
   if (eigvals) std::copy(m->lam.begin(), m->lam.end(), eigvals);
   if (coef) std::copy(m->coef.begin(), m->coef.end(), coef);
   if (tstat) std::copy(m->tstat.begin(), m->tstat.end(), tstat);
   if (coef_cov) std::copy(m->cov.begin(), m->cov.end(), coef_cov);
   if (ols_resid) std::copy(m->resid.begin(), m->resid.end(), ols_resid);
   if (ic_values && !m->ic.empty()) std::copy(m->ic.begin(), m->ic.end(), ic_values);
-  (void)d;
-  std::vector<double> tmp;
-  auto rows_to_colmajor = [&](const double *src, int rows, int cols, double *dst) -> int {
-    tmp.resize((size_t)rows * cols);
-    if (hipMemcpyAsync(tmp.data(), src, tmp.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return 1;
-    if (hipStreamSynchronize(st) != hipSuccess) return 1;
-    for (int i = 0; i < rows; ++i)
-      for (int j = 0; j < cols; ++j) dst[(size_t)j * rows + i] = tmp[(size_t)i * cols + j];
-    return 0;
-  };
-  if (F && rows_to_colmajor(m->F, m->T, m->r, F)) return fail(ctx, 1001, "copy F");
-  if (L && rows_to_colmajor(m->L, m->N, m->r, L)) return fail(ctx, 1001, "copy L");
+  if (F && read_rows_colmajor(ctx, m->F, m->T, m->r, F)) return fail(ctx, 1001, "copy F");
+  if (L && read_rows_colmajor(ctx, m->L, m->N, m->r, L)) return fail(ctx, 1001, "copy L");
   if (E) {
-    double *d_out = nullptr;
-    HIPCHK(ctx, dalloc(&d_out, (size_t)m->T * m->N));
+    DevBuf<> d_out;
+    HIPCHK(ctx, d_out.alloc((size_t)m->T * m->N));
     hipLaunchKernelGGL(colmajor_from_rows_kernel, dim3((m->N + 31) / 32, (m->T + 31) / 32), dim3(256), 0,
-                       st, m->Ep, m->ld, m->T, m->N, d_out);
-    HIPCHK(ctx, hipMemcpyAsync(E, d_out, (size_t)m->T * m->N * 8, hipMemcpyDeviceToHost, st));
+                       st, m->Ep, m->ld, m->T, m->N, d_out.p);
+    HIPCHK(ctx, hipMemcpyAsync(E, d_out.p, (size_t)m->T * m->N * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    hipFree(d_out);
   }
   return 0;
 }
@@ -531,95 +396,6 @@ int64_t dfm_stats_width(const dfm_model *m, const dfm_stat *stats, int nstats) {
   return w;
 }
 
-int dfm_pca(dfm_ctx *ctx, const double *X, int64_t T64, int64_t N64, int64_t ldx, int k,
-            double *eigvals, double *F, double *L, double *trace_G) {
-  if (!ctx) return -1;
-  if (!X || T64 < 1 || N64 < 1 || ldx < T64 || k < 1) return fail(ctx, -2, "dfm_pca: bad arguments");
-  const int T = (int)T64, N = (int)N64, m = std::min(T, N);
-  if (k > m) return fail(ctx, -2, "dfm_pca: k=%d > min(T,N)=%d", k, m);
-  DeviceShare gate(ctx->device);
-  hipSetDevice(ctx->device);
-  hipStream_t st = ctx->stream;
-  DevPanel dp;
-  int rc = upload_panel(ctx, X, T, N, ldx, dp);
-  if (rc) return rc;
-  const int orient = (N > T) ? 0 : 1;
-  double *G = nullptr, *lam = nullptr, *Uk = nullptr, *tr = nullptr, *Fd = nullptr, *Ld = nullptr;
-  int *sd = nullptr;
-  HIPCHK(ctx, dalloc(&G, (size_t)m * m));
-  HIPCHK(ctx, dalloc(&lam, k)); HIPCHK(ctx, dalloc(&Uk, (size_t)m * k)); HIPCHK(ctx, dalloc(&tr, 1));
-  HIPCHK(ctx, dalloc(&Fd, (size_t)T * k)); HIPCHK(ctx, dalloc(&Ld, (size_t)N * k)); HIPCHK(ctx, dalloc(&sd, 1));
-  PanelSrc src{nullptr, dp.P, nullptr, nullptr, dp.ld, 0};
-  {
-    Scope sc(ctx, DFM_KC_GRAM);
-    HIPCHK(ctx, launch_gram(orient, src, m, orient == 0 ? N : T, T, G, m, (int64_t)m * m, 1, st));
-  }
-  rc = run_eig(ctx, G, m, 1, k, nullptr, 0, lam, Uk, tr, sd);
-  int est = 0;
-  if (!rc) {
-    Scope sc(ctx, DFM_KC_FACTORS);
-    if (k <= 32 ? launch_factors(orient, src, T, N, k, 1, Uk, Fd, Ld, nullptr, st)
-                : launch_factors_wide(orient, dp.P, dp.ld, T, N, k, Uk, Fd, Ld, nullptr, st, (double)T))
-      rc = fail(ctx, 1001, "factor kernels failed");
-  }
-  std::vector<double> hF((size_t)T * k), hL((size_t)N * k);
-  if (!rc) {
-    if (eigvals) HIPCHK(ctx, hipMemcpyAsync(eigvals, lam, (size_t)k * 8, hipMemcpyDeviceToHost, st));
-    if (trace_G) HIPCHK(ctx, hipMemcpyAsync(trace_G, tr, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(hF.data(), Fd, hF.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(hL.data(), Ld, hL.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(&est, sd, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (F) rows_to_colmajor_host(hF, T, k, F);
-    if (L) rows_to_colmajor_host(hL, N, k, L);
-  }
-  for (double *p : {G, lam, Uk, tr, Fd, Ld}) hipFree(p);
-  hipFree(sd);
-  if (rc) return rc;
-  if (est) return fail(ctx, 2, "eigensolver did not converge");
-  return 0;
-}
-
-int dfm_gram_spectrum(dfm_ctx *ctx, const double *X, int64_t T64, int64_t N64, int64_t ldx,
-                      double *eigvals_m, double *trace_G) {
-  if (!ctx) return -1;
-  if (!X || !eigvals_m || T64 < 1 || N64 < 1 || ldx < T64) return fail(ctx, -2, "bad arguments");
-  const int T = (int)T64, N = (int)N64, m = std::min(T, N);
-  if (m > spectrum_any_max()) return fail(ctx, -30, "full spectrum supported for min(T,N) <= %d", spectrum_any_max());
-  DeviceShare gate(ctx->device);
-  hipSetDevice(ctx->device);
-  hipStream_t st = ctx->stream;
-  DevPanel dp;
-  int rc = upload_panel(ctx, X, T, N, ldx, dp);
-  if (rc) return rc;
-  const int orient = (N > T) ? 0 : 1;
-  DevBuf Gb, evb, wk;
-  HIPCHK(ctx, dalloc(&Gb.p, (size_t)m * m));
-  HIPCHK(ctx, dalloc(&evb.p, m));
-  double *G = Gb.p, *ev = evb.p;
-  if (spectrum_work(m, 1) > 0) HIPCHK(ctx, dalloc(&wk.p, (size_t)spectrum_work(m, 1)));
-  PanelSrc src{nullptr, dp.P, nullptr, nullptr, dp.ld, 0};
-  {
-    Scope sc(ctx, DFM_KC_GRAM);
-    HIPCHK(ctx, launch_gram(orient, src, m, orient == 0 ? N : T, T, G, m, (int64_t)m * m, 1, st));
-  }
-  {
-    Scope sc(ctx, DFM_KC_EIG_OTHER);
-    HIPCHK(ctx, launch_spectrum(G, m, (int64_t)m * m, m, 1, ev, wk.p, st));
-  }
-  HIPCHK(ctx, hipMemcpyAsync(eigvals_m, ev, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-  if (trace_G) {
-    std::vector<double> g((size_t)m * m);
-    HIPCHK(ctx, hipMemcpyAsync(g.data(), G, g.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    double s = 0;
-    for (int i = 0; i < m; ++i) s += g[(size_t)i * m + i];
-    *trace_G = s;
-  }
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  return 0;
-}
-
 // criterion_<name>(dfm) of a fitted model (src/criteria.jl:17-53) at its r:
 // V(r) is the model's; PCp's sigma^2 is V(ceil(m/2)) of the unrestricted
 // 3-arg fit DynamicFactorModel(y, w, x) (:18, :23, :28; no breaks, D2): the
@@ -634,29 +410,15 @@ int dfm_model_criterion(dfm_model *M, int crit, double *value) {
     if (m > spectrum_any_max())
       return fail(ctx, -30, "PCp criteria need the full spectrum: supported for min(T,N) <= %d", spectrum_any_max());
     hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    DevBuf Gb, evb, wk;
-    HIPCHK(ctx, dalloc(&Gb.p, (size_t)m * m));
-    HIPCHK(ctx, dalloc(&evb.p, m));
-    if (spectrum_work(m, 1) > 0) HIPCHK(ctx, dalloc(&wk.p, (size_t)spectrum_work(m, 1)));
-    PanelSrc src{nullptr, M->Xp, nullptr, nullptr, M->ld, 0};
-    {
-      Scope sc(ctx, DFM_KC_GRAM);
-      HIPCHK(ctx, launch_gram(M->orient, src, m, M->orient == 0 ? M->N : M->T, M->T, Gb.p, m, (int64_t)m * m, 1, st));
-    }
-    {
-      Scope sc(ctx, DFM_KC_EIG_OTHER);
-      HIPCHK(ctx, launch_spectrum(Gb.p, m, (int64_t)m * m, m, 1, evb.p, wk.p, st));
-    }
-    std::vector<double> ev(m);
-    HIPCHK(ctx, hipMemcpyAsync(ev.data(), evb.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    double s = 0.0;   // trace minus the top ceil(m/2), as the fit's sigma^2
-    for (double v : ev) s += v;
-    for (int j = 0; j < ceil_half(m); ++j) s -= ev[j];
-    M->sigma2 = s / ((double)M->N * M->T);
+    DevBuf<> G;
+    HIPCHK(ctx, G.alloc((size_t)m * m));
+    HIPCHK(ctx, panel_gram(ctx, M->orient, PanelSrc{nullptr, M->Xp, nullptr, nullptr, M->ld, 0}, M->T, M->N, G.p));
+    std::vector<double> ev;
+    const int rc = gram_spectrum(ctx, G.p, m, ev);
+    if (rc) return rc;
+    M->sigma2 = sigma2_total_minus_top(ev.data(), m, (double)M->N * M->T);   // as the fit's sigma^2
   }
-  *value = crit_formula(crit, M->V, M->r, M->sigma2, M->T, M->N);
+  *value = criterion(crit, M->V, M->r, M->sigma2, M->T, M->N);
   return 0;
 }
 
@@ -877,58 +639,6 @@ extern "C" int dfm_predict(dfm_model *m, int64_t n_new, const double *w_new, int
                            int64_t ldx, double *out) {
   if (!out) return m ? fail(m->ctx, -2, "dfm_predict: output required") : -1;
   return predict_impl(m, n_new, w_new, ldw, x_new, ldx, nullptr, out);
-}
-
-// ------------------------------------------------------------------ normalize
-// normalize (src/utils.jl:33): (A .- mean(A, 1)) ./ std(A, 1) — column z-score
-// with the sample std (n - 1 denominator), two passes over the column (mean,
-// then the centred sum of squares), then the scaled write.  One wave per
-// column of the column-major panel (contiguous in Julia's layout: coalesced);
-// Y may alias X.
-__global__ __launch_bounds__(256) void normalize_cols_kernel(const double *X, int64_t ldx, int T, int N, double *Y,
-                                                             int64_t ldy) {
-  const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= N) return;
-  const double *x = X + (int64_t)c * ldx;
-  double s = 0.0;
-  for (int t = lane; t < T; t += 64) s += x[t];
-  const double mu = wave_sum(s) / T;
-  double v = 0.0;
-  for (int t = lane; t < T; t += 64) { const double d = x[t] - mu; v = fma(d, d, v); }
-  const double sd = sqrt(wave_sum(v) / (T - 1));
-  double *y = Y + (int64_t)c * ldy;
-  for (int t = lane; t < T; t += 64) y[t] = (x[t] - mu) / sd;
-}
-
-extern "C" int dfm_normalize_dev(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, double *out,
-                                 int64_t ldo) {
-  if (!ctx) return -1;
-  if (!X || !out || T < 2 || N < 1 || ldx < T || ldo < T || T > INT32_MAX || N > INT32_MAX)
-    return fail(ctx, -2, "dfm_normalize: bad arguments");
-  DeviceShare gate(ctx->device);
-  hipSetDevice(ctx->device);
-  Scope sc(ctx, DFM_KC_MISC);
-  hipLaunchKernelGGL(normalize_cols_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ctx->stream, X, ldx, (int)T,
-                     (int)N, out, ldo);
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-
-extern "C" int dfm_normalize(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, double *out,
-                             int64_t ldo) {
-  if (!ctx) return -1;
-  if (!X || !out || T < 2 || N < 1 || ldx < T || ldo < T) return fail(ctx, -2, "dfm_normalize: bad arguments");
-  DeviceShare gate(ctx->device);
-  hipSetDevice(ctx->device);
-  hipStream_t st = ctx->stream;
-  DevBuf d;
-  HIPCHK(ctx, dalloc(&d.p, (size_t)T * N));
-  HIPCHK(ctx, hipMemcpy2DAsync(d.p, (size_t)T * 8, X, (size_t)ldx * 8, (size_t)T * 8, N, hipMemcpyHostToDevice, st));
-  int rc = dfm_normalize_dev(ctx, d.p, T, N, T, d.p, T);
-  if (rc) return rc;
-  HIPCHK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, d.p, (size_t)T * 8, (size_t)T * 8, N, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  return 0;
 }
 
 // ------------------------------------------------------------ multi-device

@@ -1,8 +1,10 @@
 // dfm_host.h — private to the host layer of the C ABI of include/dfm.h
-// (dfm_ctx.hip, dfm_fit.hip, dfm_boot.hip, dfm_windows.hip): the context and
-// model objects, error reporting, timing scopes and the small helpers those
-// files share.  Host-side orchestration only; all arithmetic runs in the
-// kernels of dfm_gram.hip (K1), dfm_eig.hip / dfm_fact.hip (K2), dfm_model.hip / dfm_chow.hip (K3).
+// (dfm_ctx.hip, dfm_panel.hip, dfm_fit.hip, dfm_boot.hip, dfm_windows.hip,
+// dfm_mc.hip, dfm_em.hip): the context and model objects, error reporting,
+// timing scopes, the owning device buffer and the small helpers those files
+// share.  The criteria themselves are in dfm_criteria.h.  Host-side
+// orchestration only; all arithmetic runs in the kernels of dfm_gram.hip (K1),
+// dfm_eig.hip / dfm_fact.hip (K2), dfm_model.hip / dfm_chow.hip (K3).
 #pragma once
 #include "dfm_internal.h"
 #include "../../include/dfm.h"
@@ -186,20 +188,12 @@ void timer_cb(void *p, int cls, int begin);
 void merge_kid(dfm_ctx *ctx, dfm_ctx *kid);   // a lane context's timings into its parent's
 void ctx_release(dfm_ctx *ctx);
 
-// On a HIP error: return fail(...), or — inside the fit, which frees its
-// temporaries and the half-built model through its bail() — return bail(fail(...)).
 #define HIPCHK(ctx, x)                                                                            \
   do {                                                                                            \
     hipError_t e_ = (x);                                                                          \
     if (e_ != hipSuccess)                                                                         \
       return fail(ctx, 1000 + (int)e_, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
                   __LINE__);                                                                      \
-  } while (0)
-#define HIPCHK_BAIL(ctx, x)                                                                                  \
-  do {                                                                                                       \
-    hipError_t e_ = (x);                                                                                     \
-    if (e_ != hipSuccess)                                                                                    \
-      return bail(fail(ctx, 1000 + (int)e_, "HIP %s line %d", hipGetErrorString(e_), __LINE__));            \
   } while (0)
 
 struct Scope {
@@ -220,22 +214,6 @@ inline int64_t stat_width(const dfm_model *m, int k) {
   if (k == DFM_STAT_LOADINGS) return (int64_t)m->N * m->r;
   return 1;
 }
-inline int ceil_half(int m) { return (m + 1) / 2; }
-// src/criteria.jl:17-53 at k factors: V(k), PCp's sigma^2 (V of the
-// unrestricted fit), c = (N + T) / (N T), m = min(T, N)
-inline double crit_formula(int crit, double V, int k, double sigma2, int T, int N) {
-  const double NT = (double)N * (double)T, c = (double)(N + T) / NT, m = (double)std::min(T, N);
-  switch (crit) {
-    case 0: return V + k * sigma2 * c * std::log(1.0 / c);
-    case 1: return V + k * sigma2 * c * std::log(m);
-    case 2: return V + k * sigma2 * std::log(m) / m;
-    case 3: return std::log(V) + k * c * std::log(1.0 / c);
-    case 4: return std::log(V) + k * c * std::log(m);
-    case 5: return std::log(V) + k * std::log(m) / m;
-    case 6: return V + k * std::log((double)T) / T;
-  }
-  return NAN;
-}
 // T >= N, no breaks, small N: the batch's Grams by one weighted GEMM (gram_wk).
 // Its prep kernel stages the replicate's draws and F (T x r) in LDS: only
 // while that fits the default 64 KB dynamic-LDS launch; larger T r take the
@@ -252,10 +230,19 @@ inline hipError_t dalloc(T **p, size_t n) {
   return e;
 }
 
-// device buffer freed on every return path
+// Owning device buffer (hipMalloc through dalloc / hipFree): move-only, freed on every return path
+template <class T = double>
 struct DevBuf {
-  double *p = nullptr;
+  T *p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
   ~DevBuf() { hipFree(p); }
+  hipError_t alloc(size_t n) {   // a block held from an earlier alloc is freed first
+    if (p) hipFree(p);
+    p = nullptr;
+    return dalloc(&p, n);
+  }
 };
 
 struct DevPanel {   // stream-ordered (pool) allocations: no device-wide sync in hipFree
@@ -267,7 +254,20 @@ struct DevPanel {   // stream-ordered (pool) allocations: no device-wide sync in
     if (P) hipFreeAsync(P, st);
   }
 };
-// ---- dfm_fit.hip
+// ---- dfm_panel.hip: the model-less steps over one resident panel
 int upload_panel(dfm_ctx *ctx, const double *X, int T, int N, int64_t ldx, DevPanel &dp, bool dev = false);
+// Gram (m x m, m = orient == 0 ? T : N) of the T rows of src, under the Gram timing scope
+hipError_t panel_gram(dfm_ctx *ctx, int orient, const PanelSrc &src, int T, int N, double *G);
+// every eigenvalue of one m x m Gram, descending (m <= spectrum_any_max()); synchronises
+int gram_spectrum(dfm_ctx *ctx, const double *G, int m, std::vector<double> &ev);
+// the EigArgs fields a context decides: p, tol (a single fit's rule), maxit, poll, st, tf, tctx
+EigArgs ctx_eig_args(dfm_ctx *ctx, int m, int k);
+// Top-k eigenpairs + trace of one Gram.  ws == nullptr: run_eig allocates and frees the workspace and
+// synchronises; a caller's ws (eig_workspace_bytes_padded, k inside the subspace block) adds neither.
+// warm: m x k start vectors (nullptr: hashed start).
+int run_eig(dfm_ctx *ctx, const double *G, int m, int k, double *lam, double *Uk, double *trace, int *status_dev,
+            char *ws = nullptr, const double *warm = nullptr);
+// row-major rows x cols device block -> column-major host array; synchronises
+int read_rows_colmajor(dfm_ctx *ctx, const double *src, int rows, int cols, double *dst);
 
 }  // namespace dfm

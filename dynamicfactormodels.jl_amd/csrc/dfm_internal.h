@@ -4,6 +4,7 @@
 // dfm_fact.hip share is in their private dfm_eig.h.)
 #pragma once
 #include "dfm_common.h"
+#include "dfm_criteria.h"
 
 struct dfm_ctx;   // dfm_host.h
 
@@ -133,7 +134,7 @@ __global__ void ordered_sum_kernel(const double *__restrict__ v, int n, double *
 hipError_t launch_ols(int nb, hipStream_t st, const double *y, const double *w, int q, const double *F, int Tphys,
                       int kF, const int *Tn, const int *kr, double *coef, double *tstat, double *cov_out,
                       double *resid_out, int *status, const int *R0 = nullptr);
-__global__ void tail_sigma2_kernel(const double *__restrict__ ev, int m, int h, int nb, double NT,
+__global__ void tail_sigma2_kernel(const double *__restrict__ ev, int m, int nb, double NT,
                                    double *__restrict__ sig2);
 __global__ void stats_kernel(int nb, int T, int N, int r, int q, int crit, double sigma2,
                              const double *__restrict__ sig2v,

@@ -36,7 +36,7 @@ constexpr int MC_SPEC_SLICE = DFM_MC_SPEC_SLICE;       // launch_spectrum's LDS 
 
 // Strip (blockIdx.x) of 16 columns of panel blockIdx.y: wave w owns columns
 // 4 w .. 4 w + 3 of the strip.  Column statistics exactly as
-// normalize_cols_kernel (dfm_fit.hip) — one wave per column, lane-strided
+// normalize_cols_kernel (dfm_panel.hip) — one wave per column, lane-strided
 // sums, wave_sum, the variance accumulated with fma, (x - mu) / sd — so the
 // values are bit-identical to dfm_normalize_dev of the panel alone.  Reads run
 // along a column (64 consecutive doubles per wave); the tile goes out row by
@@ -101,43 +101,20 @@ __global__ void mc_group_kernel(const int *__restrict__ list, int T, int32_t *__
   if (t == 0 && sig2 && sig2g) sig2g[j] = sig2[b];
 }
 
-// One thread per panel: dfm_ic_sweep (dfm_ctx.hip) in its operation order on
-// the panel's spectrum (descending, row stride m) and trace, with PCp's
-// sigma^2 = sum_{j >= ceil(m/2)} lambda_j / (N T) summed as tail_sigma2_kernel
-// does; the first arg-min of each criterion over k = 1..kmax.
+// One thread per panel, on the panel's spectrum (descending, row stride m) and
+// trace: PCp's sigma^2 as the spectral tail (tail_sigma2_kernel's order), the
+// panel's 7 x kmax table and the first arg-min of each row by criteria_sweep.
 __global__ void mc_select_kernel(const double *__restrict__ ev, const double *__restrict__ trace, int m, int n, int T,
                                  int N, int kmax, int crit, double *__restrict__ sig2, int *__restrict__ rsel,
                                  int64_t *__restrict__ r_hat, double *__restrict__ ic, double *__restrict__ eig) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n) return;
   const double *e = ev + (int64_t)b * m;
-  const double NT = (double)N * (double)T;
-  double s = 0.0;
-  for (int j = m - 1; j >= (m + 1) / 2; --j) s += e[j];
-  const double sigma2 = s / NT;
+  const double sigma2 = sigma2_tail(e, m, (double)N * (double)T);
   sig2[b] = sigma2;
-  const double c = (double)(N + T) / NT, lm = log((double)m), lc = log(1.0 / c), lT = log((double)T);
-  double best[7] = {0, 0, 0, 0, 0, 0, 0};
-  int arg[7] = {1, 1, 1, 1, 1, 1, 1};
-  double cum = trace[b];
-  for (int k = 1; k <= kmax; ++k) {
-    cum -= e[k - 1];
-    const double V = cum / NT;
-    double v[7];
-    v[0] = V + k * sigma2 * c * lc;
-    v[1] = V + k * sigma2 * c * lm;
-    v[2] = V + k * sigma2 * lm / m;
-    v[3] = log(V) + k * c * lc;
-    v[4] = log(V) + k * c * lm;
-    v[5] = log(V) + k * lm / m;
-    v[6] = V + k * lT / T;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-      if (k == 1 || v[q] < best[q]) { best[q] = v[q]; arg[q] = k; }
-      ic[((int64_t)b * 7 + q) * kmax + k - 1] = v[q];
-    }
-    eig[(int64_t)b * kmax + k - 1] = e[k - 1];
-  }
+  for (int k = 0; k < kmax; ++k) eig[(int64_t)b * kmax + k] = e[k];
+  int arg[7];
+  criteria_sweep(e, kmax, trace[b], sigma2, T, N, ic + (int64_t)b * 7 * kmax, arg);
 #pragma unroll
   for (int q = 0; q < 7; ++q) r_hat[(int64_t)b * 7 + q] = arg[q];
   rsel[b] = crit >= 0 ? arg[crit] : 0;
@@ -463,13 +440,10 @@ extern "C" int dfm_mc(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int
         // degree 2): a group of one is solved as two copies of its Gram (stride 0), so a panel's
         // eigenvectors do not depend on how many panels share its r in its chunk
         const int nbe = ng == 1 ? 2 : ng;
-        EigArgs ea;
-        ea.nb = nbe; ea.k = r; ea.p = eig_block_p(m, r, ctx->block);
-        ea.warm = nullptr; ea.kw = 0;
-        ea.tol = std::min(ctx->tol, 1e-14); ea.maxit = ctx->maxit; ea.poll = ctx->poll;
+        EigArgs ea = ctx_eig_args(ctx, m, r);
+        ea.nb = nbe;
         ea.ws = w.eigws;
         ea.lam = lam; ea.Uk = Uk; ea.trace_out = tr; ea.status = status;
-        ea.st = st; ea.tf = timer_cb; ea.tctx = ctx;
         const int rc = eig_run(Gg, m, ng == 1 ? 0 : (int64_t)m * m, m, ea, nullptr, 0);
         if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);
         ctx->eig_batches++;

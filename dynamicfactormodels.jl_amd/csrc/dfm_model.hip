@@ -554,32 +554,13 @@ hipError_t launch_ols(int nb, hipStream_t st, const double *y, const double *w, 
 }
 
 // ---------------------------------------------------------------- stats
-// Criteria, src/criteria.jl:17-53 (V from the trace identity).
-DFM_DEV double criterion_dev(int code, double V, int k, int T, int N, double sigma2) {
-  const double c = (double)(N + T) / ((double)N * (double)T);
-  const double m = (double)min(T, N);
-  switch (code) {
-    case 0: return V + k * sigma2 * c * log(1.0 / c);
-    case 1: return V + k * sigma2 * c * log(m);
-    case 2: return V + k * sigma2 * log(m) / m;
-    case 3: return log(V) + k * c * log(1.0 / c);
-    case 4: return log(V) + k * c * log(m);
-    case 5: return log(V) + k * log(m) / m;
-    case 6: return V + k * log((double)T) / T;
-  }
-  return NAN;
-}
-
-// PCp's sigma^2 of each replicate's unrestricted fit (src/criteria.jl:18):
-// V(h) = sum_{j >= h} lambda_j / (N T), h = ceil(m/2), from its full spectrum
-// (descending), summed in a fixed order.
-__global__ void tail_sigma2_kernel(const double *__restrict__ ev, int m, int h, int nb, double NT,
+// PCp's sigma^2 of each replicate's unrestricted fit (src/criteria.jl:18) from
+// its full spectrum (descending), summed from the small end (dfm_criteria.h).
+__global__ void tail_sigma2_kernel(const double *__restrict__ ev, int m, int nb, double NT,
                                    double *__restrict__ sig2) {
   const int rep = blockIdx.x * blockDim.x + threadIdx.x;
   if (rep >= nb) return;
-  double s = 0.0;
-  for (int j = m - 1; j >= h; --j) s += ev[(int64_t)rep * m + j];
-  sig2[rep] = s / NT;
+  sig2[rep] = sigma2_tail(ev + (int64_t)rep * m, m, NT);
 }
 
 // One thread per replicate.  out row stride = width.
@@ -605,7 +586,7 @@ __global__ void stats_kernel(int nb, int T, int N, int r, int q, int crit, doubl
     double v = NAN;
     switch (st.kind) {
       case 0: v = V; break;
-      case 1: v = criterion_dev(st.arg0 >= 0 ? st.arg0 : crit, V, r, T, N, sig2v ? sig2v[rep] : sigma2); break;
+      case 1: v = criterion(st.arg0 >= 0 ? st.arg0 : crit, V, r, sig2v ? sig2v[rep] : sigma2, T, N); break;   // V: the trace identity
       case 2: v = st.arg0 < r ? lam[(int64_t)rep * r + st.arg0] : NAN; break;
       case 3: v = st.arg0 < d ? coef[(int64_t)rep * d + st.arg0] : NAN; break;
       case 4: v = st.arg0 < d ? tstat[(int64_t)rep * d + st.arg0] : NAN; break;

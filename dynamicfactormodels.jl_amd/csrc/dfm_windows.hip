@@ -410,10 +410,7 @@ static int windows_impl(dfm_ctx *ctx, const double *y, const double *w, int q, i
   } else {
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (int wi = 0; wi < P; ++wi) {   // eigenvalues and trace from the window's spectrum
-      const int mw = orient == 0 ? nw(wi) : N;
-      double s = 0.0;
-      for (int j = mw - 1; j >= 0; --j) s += hev[(size_t)wi * pst + j];
-      ht[wi] = s;
+      ht[wi] = tail_sum(&hev[(size_t)wi * pst], orient == 0 ? nw(wi) : N, 0);
       for (int j = 0; j < kmax; ++j) hl[(size_t)wi * kmax + j] = hev[(size_t)wi * pst + j];
     }
   }
@@ -423,22 +420,15 @@ static int windows_impl(dfm_ctx *ctx, const double *y, const double *w, int q, i
   for (int wi = 0; wi < P; ++wi) {
     const int n = nw(wi);
     double s2 = NAN;
-    if (pcp) {   // src/criteria.jl:18: V(ceil(m_w/2)) of the window's unrestricted fit = spectral tail
-      const int mw = std::min(n, N), h = (mw + 1) / 2;
-      double s = 0.0;
-      for (int j = mw - 1; j >= h; --j) s += hev[(size_t)wi * pst + j];
-      s2 = s / ((double)N * n);
-    }
+    // src/criteria.jl:18: V(ceil(m_w/2)) of the window's unrestricted fit = spectral tail
+    if (pcp) s2 = sigma2_tail(&hev[(size_t)wi * pst], std::min(n, N), (double)N * n);
     const int kw = kmax_w(wi);
     int rsel = kw;
     double cv = NAN;
     if (ws.r == 0) {
       dfm_ic_sweep(&hl[(size_t)wi * kmax], kw, kw, ht[wi], n, N, s2, ic.data());
-      int best = 0;
-      for (int k = 1; k < kw; ++k)
-        if (ic[(size_t)crit * kw + k] < ic[(size_t)crit * kw + best]) best = k;
-      rsel = best + 1;
-      cv = ic[(size_t)crit * kw + best];
+      rsel = first_argmin(&ic[(size_t)crit * kw], kw);
+      cv = ic[(size_t)crit * kw + rsel - 1];
     } else if (crit >= 0) {   // the workhorse constructor's criterion at r_w (:50)
       dfm_ic_sweep(&hl[(size_t)wi * kmax], kw, kw, ht[wi], n, N, s2, ic.data());
       cv = ic[(size_t)crit * kw + kw - 1];
