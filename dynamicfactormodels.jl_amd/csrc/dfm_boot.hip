@@ -571,6 +571,9 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
       fa.off = w.off; fa.lst = w.lst;
       fa.cnt = (M->count_ctx ? M->count_ctx : ctx)->cnt_dev;
       fa.spread = spread; fa.lamk = lamk;
+      // M->F = sqrt(T) M->Ub element by element (factors_rows_kernel: fact implies the N > T branch, one break
+      // block and r <= 32), so the solver's P'D F is that multiple of its P'D Q0's first r columns
+      fa.fscale = sqrt((double)T);
       fa.pb = ctx_poll(ctx);
       int rc = eig_run_factored(fb, ea, fa);
       if (rc) return fail(ctx, rc > 0 ? rc : -21, "eigensolver failed (%d)", rc);

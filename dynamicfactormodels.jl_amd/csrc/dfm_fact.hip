@@ -168,6 +168,16 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
   for (int q = tid; q <= T; q += 256) so[q] = q ? cnt[q - 1] : 0;
   for (int t = tid; t < T; t += 256) set[t] = et ? et[t] : 1.0;
   __syncthreads();
+  if (E2 && !PF)   // P'D^2 1 alone: the middle steps take P'D F from PV's rows (boot_cheb_mid_kernel's NOPF)
+    for (int s = tid; s < T; s += 256) {   // the same walk and sums as below, LDS only
+      const int b0 = s ? cnt[s - 1] : 0, b1 = cnt[s];
+      double a2 = 0.0;
+      for (int q = b0; q < b1; ++q) {
+        const double h = set[L[q]];
+        a2 = fma(h, h, a2);
+      }
+      E2[(int64_t)rep * T + s] = a2;
+    }
   if (PF)   // P'D F (row stride r) and P'D^2 1 of the middle Horner steps (boot_cheb_mid_kernel):
     for (int s = tid; s < T; s += 256) {   // this thread's own sorted buckets, t ascending
       const int b0 = s ? cnt[s - 1] : 0, b1 = cnt[s];
@@ -644,7 +654,7 @@ struct Ap2Tile {
 // layout as ap2_load.
 template <int P>
 DFM_DEV void ap2_load_lds(Ap2Tile<P> &L, int tile, int T, int r, int lane, int init, const double *__restrict__ Qr,
-                          const double *Yr, const FactBase &fb, double *tq, double *ty, int ps) {
+                          const double *Yr, const FactBase &fb, double *tq, double *ty, int ps, bool ldf = true) {
   constexpr int NT = P / 16, KP = P / 4, PER = P / 4;   // doubles per lane per matrix
   const int li = lane & 15, lk = lane >> 4, t0 = tile * 16;
   if (!init) {
@@ -682,7 +692,8 @@ DFM_DEV void ap2_load_lds(Ap2Tile<P> &L, int tile, int T, int r, int lane, int i
     const int tc = min(t, T - 1);
     // only lanes holding a factor column of a row < T load (r = 0, the
     // expanding windows' case without base factors, loads nothing)
-    L.fa[g] = (t < T && li < r) ? fb.F[(int64_t)tc * r + li] : 0.0;
+    // (ldf = false, ap2's probe pass: no a = F'Qn there, no F rows)
+    L.fa[g] = (ldf && t < T && li < r) ? fb.F[(int64_t)tc * r + li] : 0.0;
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) L.q[ct][g] = (init && 16 * ct + li < ps) ? Qr[(int64_t)tc * ps + 16 * ct + li] : 0.0;
   }
@@ -824,6 +835,16 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
 // and is gathered back through the CSR after the barrier: same-CU L1, so the
 // workgroup-scope fence of __syncthreads makes it visible.  Dynamic LDS:
 // eta (T doubles), off (T+1 ints), lst (T ints) of this replicate.
+// probe (ignored with init): decide before writing.  A first pass over the
+// tiles forms only u = Q A, Y A and the residuals (Q and Y tiles in, the sAm
+// MFMAs, no stores); the verdict follows as in the one-pass form.  A
+// replicate that retires (or a last launch) takes the exit without ever
+// having written V0 and Qn; one that goes on then runs the one-pass tile
+// loop, its residuals discarded.  Every value that leaves the kernel is
+// formed by the same instructions in the same order from the same inputs in
+// both forms: rows, done, iters, the active counters and the residual record
+// do not depend on probe.  The host sets it on the steps replicates are
+// expected to retire at (eig_run_fact2_t).
 template <int P>
 // 4 workgroups per CU (see boot_y2_kernel)
 __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWork w, int T, int k, int p, double tol,
@@ -832,10 +853,12 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
                                                        const int *__restrict__ off, const int *__restrict__ lst,
                                                        const double *__restrict__ Qc, int64_t qs,
                                                        double *__restrict__ Yq, double *__restrict__ Zc, int64_t ldz,
-                                                       int pz, double *__restrict__ ab, uint64_t seed, int ps) {
+                                                       int pz, double *__restrict__ ab, uint64_t seed, int ps,
+                                                       int probe) {
   constexpr int NT = P / 16, KP = P / 4;
   const int rep = blockIdx.x;
   if (!init && w.done[rep]) return;
+  const bool two = probe && !init;
   extern __shared__ double sdyn[];
   double *set = sdyn;                          // eta_t
   int *so = (int *)(sdyn + T), *sl = so + T + 1;
@@ -883,70 +906,104 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
   const int ntile = (T + 15) >> 4;
   // each tile's operands load at the top of its iteration (occupancy hides the latency)
   Ap2Tile<P> cur;
-  for (int tile = wave; tile < ntile; tile += BW) {
-    ap2_load_lds<P>(cur, tile, T, r, lane, init, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps);
-    const int t0 = tile * 16;
-    double qv[NT][4];
-    if (init) {
+  // the one-pass tile loop: u, Y A and the residuals, V0 and Qn out, a = F'Qn
+  auto tile_loop = [&]() {
+    for (int tile = wave; tile < ntile; tile += BW) {
+      ap2_load_lds<P>(cur, tile, T, r, lane, init, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps);
+      const int t0 = tile * 16;
+      double qv[NT][4];
+      if (init) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int ct = 0; ct < NT; ++ct) qv[ct][g] = (t0 + 4 * g + lk < T) ? cur.q[ct][g] : 0.0;
+      } else {
+        dv4 u[NT], ya[NT], qn[NT], qb[NT];
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) {
+          u[ct] = dv4{0.0, 0.0, 0.0, 0.0}; ya[ct] = u[ct]; qn[ct] = u[ct]; qb[ct] = u[ct];
+        }
+#pragma unroll
+        for (int kk = 0; kk < KP; ++kk)
+#pragma unroll
+          for (int ct = 0; ct < NT; ++ct) {
+            const double am = sAm[(4 * kk + lk) * P + 16 * ct + li], bm = sBm[(4 * kk + lk) * P + 16 * ct + li];
+            u[ct] = mfma16(cur.qa[kk], am, u[ct]);
+            ya[ct] = mfma16(cur.yo[kk], am, ya[ct]);
+            qn[ct] = mfma16(cur.yo[kk], bm, qn[ct]);
+            if (cheb) qb[ct] = mfma16(cur.qa[kk], bm, qb[ct]);
+          }
+        if (cheb) {   // V0 = Q Bm for the filter's later steps (boot_cheb_kernel), kept in w.U
+          double *Xr = w.U + (int64_t)rep * T * P;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int t = t0 + 4 * g + lk;
+            if (t < T)
+#pragma unroll
+              for (int ct = 0; ct < NT; ++ct) {
+                const int c = 16 * ct + li;
+                double x = qb[ct][g];
+                if (c < p && dd[ct]) x = hash_unit(seed, t, 1000003ull * (it + 1) + c);   // = S
+                if (c >= p) x = 0.0;
+                if (c < ps) Xr[(int64_t)t * ps + c] = x;
+              }
+          }
+        }
+        // every wave reads only its own tiles' Y rows, loaded (above) before
+        // these stores: Qn may overwrite this tile's Y rows
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int t = t0 + 4 * g + lk;
+          const bool v = t < T;
+#pragma unroll
+          for (int ct = 0; ct < NT; ++ct) {
+            const int c = 16 * ct + li;
+            const double wr = ya[ct][g] - th[ct] * u[ct][g];
+            if (v && c < k) res2[ct] = fma(wr, wr, res2[ct]);
+            // the filter's first Horner term S_{d-1} = (a_d / b) K_1 + a_{d-1} V0
+            // (K_1 = Y Bm = G* V0), or the plain power step Y Bm
+            double q = cheb ? fma(cf1, qn[ct][g], cf0 * qb[ct][g]) : qn[ct][g];
+            if (c < p && dd[ct]) q = hash_unit(seed, t, 1000003ull * (it + 1) + c);
+            if (c >= p || !v) q = 0.0;
+            qv[ct][g] = q;
+            if (v && c < ps) Yr[(int64_t)t * ps + c] = q;
+          }
+        }
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) qv[ct][g] = (t0 + 4 * g + lk < T) ? cur.q[ct][g] : 0.0;
-    } else {
-      dv4 u[NT], ya[NT], qn[NT], qb[NT];
+        for (int ct = 0; ct < NT; ++ct) aacc[ct] = mfma16(cur.fa[g], qv[ct][g], aacc[ct]);
+    }
+  };
+  // probe: first only u, Y A and the residuals (no stores); the tile loop after the verdict, if the replicate goes on
+  if (two) {
+    for (int tile = wave; tile < ntile; tile += BW) {
+      ap2_load_lds<P>(cur, tile, T, r, lane, 0, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps, false);
+      const int t0 = tile * 16;
+      dv4 u[NT], ya[NT];
 #pragma unroll
-      for (int ct = 0; ct < NT; ++ct) { u[ct] = dv4{0.0, 0.0, 0.0, 0.0}; ya[ct] = u[ct]; qn[ct] = u[ct]; qb[ct] = u[ct]; }
+      for (int ct = 0; ct < NT; ++ct) { u[ct] = dv4{0.0, 0.0, 0.0, 0.0}; ya[ct] = u[ct]; }
 #pragma unroll
       for (int kk = 0; kk < KP; ++kk)
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-          const double am = sAm[(4 * kk + lk) * P + 16 * ct + li], bm = sBm[(4 * kk + lk) * P + 16 * ct + li];
+          const double am = sAm[(4 * kk + lk) * P + 16 * ct + li];
           u[ct] = mfma16(cur.qa[kk], am, u[ct]);
           ya[ct] = mfma16(cur.yo[kk], am, ya[ct]);
-          qn[ct] = mfma16(cur.yo[kk], bm, qn[ct]);
-          if (cheb) qb[ct] = mfma16(cur.qa[kk], bm, qb[ct]);
         }
-      if (cheb) {   // V0 = Q Bm for the filter's later steps (boot_cheb_kernel), kept in w.U
-        double *Xr = w.U + (int64_t)rep * T * P;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int t = t0 + 4 * g + lk;
-          if (t < T)
-#pragma unroll
-            for (int ct = 0; ct < NT; ++ct) {
-              const int c = 16 * ct + li;
-              double x = qb[ct][g];
-              if (c < p && dd[ct]) x = hash_unit(seed, t, 1000003ull * (it + 1) + c);   // = S
-              if (c >= p) x = 0.0;
-              if (c < ps) Xr[(int64_t)t * ps + c] = x;
-            }
-        }
-      }
-      // every wave reads only its own tiles' Y rows, loaded (above) before
-      // these stores: Qn may overwrite this tile's Y rows
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int t = t0 + 4 * g + lk;
-        const bool v = t < T;
+        const bool v = t0 + 4 * g + lk < T;
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-          const int c = 16 * ct + li;
           const double wr = ya[ct][g] - th[ct] * u[ct][g];
-          if (v && c < k) res2[ct] = fma(wr, wr, res2[ct]);
-          // the filter's first Horner term S_{d-1} = (a_d / b) K_1 + a_{d-1} V0
-          // (K_1 = Y Bm = G* V0), or the plain power step Y Bm
-          double q = cheb ? fma(cf1, qn[ct][g], cf0 * qb[ct][g]) : qn[ct][g];
-          if (c < p && dd[ct]) q = hash_unit(seed, t, 1000003ull * (it + 1) + c);
-          if (c >= p || !v) q = 0.0;
-          qv[ct][g] = q;
-          if (v && c < ps) Yr[(int64_t)t * ps + c] = q;
+          if (v && 16 * ct + li < k) res2[ct] = fma(wr, wr, res2[ct]);
         }
       }
     }
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) aacc[ct] = mfma16(cur.fa[g], qv[ct][g], aacc[ct]);
+  } else {
+    tile_loop();
   }
   // residuals: sum over the 4 row-lanes of a column, then over waves (fixed order)
   if (!init) {
@@ -1009,6 +1066,10 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
       }
     }
     return;
+  }
+  if (two) {
+    tile_loop();   // (its residuals are not read again)
+    __syncthreads();   // every wave's Qn rows visible to the CSR gather (one pass: the verdict's barriers)
   }
   // Z = P' D Qn by CSR gather (bucket s lists t ascending), cc = EL' Z
   const double *Qn = init ? Qr : Yr;
@@ -1296,7 +1357,18 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_pv_kernel(FactBase fb, EigWor
 // rounded to nearest; 2 = HZ32 in, fp64 Z out in the normal layout (the last
 // middle step, whose Z feeds the filter's fp64 product).  All arithmetic, a
 // and cc stay fp64 in every mode; cc is formed from the unrounded Z.
-template <int P, bool FAST, int LP>
+//
+// NOPF (a warm solve that starts with the filter, eig_run_fact2_t; selected by
+// DFM_FACT_PF=0 only, see fact_pf_stored): no stored PF.  There V0 = Q0, whose
+// first r columns are the warm vectors bit for bit (eig_init_kernel;
+// q0_guards_kernel leaves them), and F = pfs * warm[:, :r]
+// with one rounding per element (FactArgs::fscale), so
+//   PF = P'D F = pfs * (P'D Q0)[:, :r] = pfs * PV[:, :r]
+// up to the rounding of the bucket sums.  The tile's 16 PV rows — one
+// contiguous range of 16 ps doubles — arrive as 16-B pieces in the stage the
+// PF rows take otherwise, and pA, pfa (columns < r, times pfs) and pv are read
+// from there: no PF loads, no PV row gathers.  PF and pfr are not read.
+template <int P, bool FAST, int LP, bool NOPF = false>
 __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, EigWork w, int T, int p,
                                                             const double *__restrict__ HZ, int64_t ldz, int pz,
                                                             double *__restrict__ ab, double fai, double bbeta, int k,
@@ -1306,7 +1378,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
                                                             const double *__restrict__ FV,
                                                             const double *__restrict__ FtF,
                                                             double *__restrict__ Zc, int ps, double bfix,
-                                                            double lead, double hscale) {
+                                                            double lead, double hscale, double pfs) {
   // bfix > 0: the interval end of a filter-only first step (boot_cheb_kernel);
   // lead: the scale of the incoming S_{i+1} not yet applied to its Z, a, cc —
   // the filter's leading coefficient a_d at the first step of such a filter
@@ -1325,8 +1397,10 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   // contiguous in the replicate-major layout) leaves as whole 16-B pieces
   // instead of one 128-B-strided element per lane
   // stage 0 holds the PF rows (16 x (r | 1) <= 16 x 17) and then the Z chunk (16 x pz <= 16 x P)
-  constexpr int MID_STG = 16 * (P > 17 ? P : 17);
+  // (NOPF: the PV rows instead, 16 x (ps | 1) <= 16 x (P + 1))
+  constexpr int MID_STG = NOPF ? 16 * (P + 1) : 16 * (P > 17 ? P : 17);
   static_assert(MID_STG >= 16 * P && MID_STG >= 16 * 17, "the stage holds a Z chunk of pz <= P columns and 16 PF rows");
+  static_assert(!NOPF || MID_STG >= 16 * (P | 1), "... or 16 PV rows of ps <= P columns at an odd stride");
   __shared__ double stgP[BW][MID_STG], stgE[BW][16 * 17];
   double *abr = ab + (int64_t)rep * 32 * P;
   for (int e = tid; e < 16 * P; e += 64 * BW) sa[e] = abr[e];
@@ -1352,6 +1426,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   for (int ct = 0; ct < NT; ++ct) { aacc[ct] = dv4{0.0, 0.0, 0.0, 0.0}; cacc[ct] = aacc[ct]; }
   const int ntile = (T + 15) >> 4;
   const int RS = r | 1;   // staged row stride (odd: the 16-row reads spread over the banks)
+  const int hps = ps >> 1, RP = NOPF ? (ps | 1) : RS;   // NOPF: 16-B pieces per PV row; stage 0's row stride
   double *sP = stgP[wave], *sE = stgE[wave];
   const int64_t zrs = zrm_stride(T, pz);
   for (int tile = wave; tile < ntile; tile += BW) {
@@ -1360,15 +1435,23 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
     double hz[NT][4], pv[NT][4], e2v[4];
     double pst[4], est[4];
     double2 pst2 = double2{0.0, 0.0}, est2 = double2{0.0, 0.0};
+    double2 pvp[2 * NT];   // NOPF: the tile's PV rows (16 ps doubles from t0 ps, 16-B aligned: ps even)
+    if constexpr (NOPF) {
+      const double2 *pc = reinterpret_cast<const double2 *>(pvr + (int64_t)t0 * ps);
+      const int npc = min(16, T - t0) * hps;   // pieces of the rows < T; the pad rows stage as zero
+#pragma unroll
+      for (int u = 0; u < 2 * NT; ++u) pvp[u] = u * 64 + lane < npc ? pc[u * 64 + lane] : double2{0.0, 0.0};
+    }
     if constexpr (FAST) {   // even r <= 8: the 8 r <= 64 pieces of 16 B, one round
       const bool ok = 2 * lane < nr;
-      pst2 = ok ? reinterpret_cast<const double2 *>(pfr + (int64_t)t0 * r)[lane] : double2{0.0, 0.0};
+      if constexpr (!NOPF)
+        pst2 = ok ? reinterpret_cast<const double2 *>(pfr + (int64_t)t0 * r)[lane] : double2{0.0, 0.0};
       est2 = ok ? reinterpret_cast<const double2 *>(fb.EL + (int64_t)t0 * r)[lane] : double2{0.0, 0.0};
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {   // 16 r <= 256 doubles: four rounds of 64 lanes
         const int e = u * 64 + lane;
-        pst[u] = e < nr ? pfr[(int64_t)t0 * r + e] : 0.0;
+        pst[u] = (!NOPF && e < nr) ? pfr[(int64_t)t0 * r + e] : 0.0;
         est[u] = e < nr ? fb.EL[(int64_t)t0 * r + e] : 0.0;
       }
     }
@@ -1388,13 +1471,13 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
       for (int ct = 0; ct < NT; ++ct) {
         const int c = 16 * ct + li;
         if constexpr (LP == 0) hz[ct][g] = c < pz ? HZ[(int64_t)sc * ldz + (int64_t)rep * pz + c] : 0.0;
-        pv[ct][g] = c < ps ? pvr[(int64_t)sc * ps + c] : 0.0;
+        if constexpr (!NOPF) pv[ct][g] = c < ps ? pvr[(int64_t)sc * ps + c] : 0.0;
       }
     }
     if constexpr (FAST) {
       if (2 * lane < 16 * r) {
         const int e = 2 * lane, row = e / r, j = e - row * r;
-        sP[row * RS + j] = pst2.x; sP[row * RS + j + 1] = pst2.y;
+        if constexpr (!NOPF) { sP[row * RS + j] = pst2.x; sP[row * RS + j + 1] = pst2.y; }
         sE[row * RS + j] = est2.x; sE[row * RS + j + 1] = est2.y;
       }
     } else {
@@ -1403,8 +1486,18 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         const int e = u * 64 + lane;
         if (e < 16 * r) {
           const int row = e / r, j = e - row * r;
-          sP[row * RS + j] = pst[u];
+          if constexpr (!NOPF) sP[row * RS + j] = pst[u];
           sE[row * RS + j] = est[u];
+        }
+      }
+    }
+    if constexpr (NOPF) {
+#pragma unroll
+      for (int u = 0; u < 2 * NT; ++u) {
+        const int e = u * 64 + lane;
+        if (e < 16 * hps) {
+          const int row = e / hps, j = 2 * (e - row * hps);
+          sP[row * RP + j] = pvp[u].x; sP[row * RP + j + 1] = pvp[u].y;
         }
       }
     }
@@ -1414,7 +1507,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
     for (int kk = 0; kk < 4; ++kk) {
       const int j = 4 * kk + lk;
       const bool ok = kk < KR && j < r && t0 + li < T;
-      pA[kk] = ok ? sP[li * RS + j] : 0.0;
+      pA[kk] = ok ? (NOPF ? pfs * sP[li * RP + j] : sP[li * RP + j]) : 0.0;
       eA[kk] = ok ? sE[li * RS + j] : 0.0;
     }
 #pragma unroll
@@ -1422,8 +1515,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
       const int s = t0 + 4 * g + lk;
       const bool v = s < T;
       e2v[g] = v ? __shfl(e2l, 4 * g + lk, 16) : 0.0;
-      pfa[g] = (v && li < r) ? sP[(4 * g + lk) * RS + li] : 0.0;
+      pfa[g] = (v && li < r) ? (NOPF ? pfs * sP[(4 * g + lk) * RP + li] : sP[(4 * g + lk) * RP + li]) : 0.0;
       ea[g] = (v && li < r) ? sE[(4 * g + lk) * RS + li] : 0.0;
+      if constexpr (NOPF)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) pv[ct][g] = 16 * ct + li < ps ? sP[(4 * g + lk) * RP + 16 * ct + li] : 0.0;
     }
     if constexpr (LP != 0) {
       // HZ32 through the EL stage (its reads above are complete in this wave's
@@ -1646,6 +1742,30 @@ static bool fact_f32_off() {
   const char *e = getenv("DFM_FACT_F32");
   return e && atoi(e) == 0;
 }
+// ap2 decides before it writes (boot_ap2_kernel's probe) on the Rayleigh-Ritz
+// steps it >= first_poll: the step most replicates are expected to retire at,
+// and on — every step of a warm solve (C3: 97 % retire at the first one and,
+// under eigenvalue-only statistics, leave without V0, Qn and their MFMAs).
+// The earlier steps of a cold solve keep the one-pass form: everybody goes
+// on there and the second read of Q and Y would be pure cost.  The bits do
+// not depend on it.  DFM_AP2_PROBE=0 (A/B only, read at every solve) keeps
+// the one-pass form throughout.
+static bool ap2_probe_off() {
+  const char *e = getenv("DFM_AP2_PROBE");
+  return e && atoi(e) == 0;
+}
+// The middle steps of a solve that starts with the filter read stored PF
+// (boot_prep_kernel writes it), as every other solve's do.  DFM_FACT_PF=0
+// (A/B only, read at every solve) selects the NOPF kernels instead: measured
+// at C3 (profiles/r10_c3_ab.txt) they move 0.30 GB less per launch and take
+// 0.19 ms off a 9.34 ms step (prep -0.10, the five middle steps -0.09: the
+// pass is bound by its load latency, not its bytes) — 2.3 times the parent's
+// run-to-run spread, short of the 3 times this project asks of a change, so
+// the stored form stays the default.
+static bool fact_pf_stored() {
+  const char *e = getenv("DFM_FACT_PF");
+  return !(e && *e && atoi(e) == 0);
+}
 
 // Guard columns kw..p-1 of the shared warm start Q0 (m rows of ps columns),
 // orthonormalised against the warm columns 0..kw-1 (one projection; the warm
@@ -1815,9 +1935,18 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   auto y2k = stg_ok ? boot_y2_kernel<P, P == 16> : boot_y2_kernel<P, false>;
   // ... whose middle products run in fp32 under the eigenvalue rule (fact_f32_off)
   const bool lowp = skip0 && a.tol < 0.0 && fb.H32 && std::isfinite(fb.hmax) && fb.hmax > 0.0 && m >= 16 && !fact_f32_off();
-  auto cmk = stg_ok ? boot_cheb_mid_kernel<P, true, 0> : boot_cheb_mid_kernel<P, false, 0>;
-  auto cmk32 = stg_ok ? boot_cheb_mid_kernel<P, true, 1> : boot_cheb_mid_kernel<P, false, 1>;     // HZ32 in, Z32 out
-  auto cmk32l = stg_ok ? boot_cheb_mid_kernel<P, true, 2> : boot_cheb_mid_kernel<P, false, 2>;    // HZ32 in, fp64 Z out
+  // ... and may take PF = P'D F from PV's rows (boot_cheb_mid_kernel's NOPF; off by default, fact_pf_stored):
+  // that step filters V0 = Q0, whose first kw >= r columns are the warm vectors, and F = fscale * warm[:, :r].
+  // The middle steps behind a first Rayleigh-Ritz step (warm_keep_step0; PV = P'D (Q Bm), boot_pv_kernel) have
+  // no such identity and always read stored PF.
+  const bool nopf = skip0 && f.fscale > 0.0 && a.kw >= fb.r && !fact_pf_stored();
+  // (lp 0: fp64 HZ in, fp64 Z out; 1: HZ32 in, Z32 out; 2: HZ32 in, fp64 Z out)
+  auto cmk = nopf ? (stg_ok ? boot_cheb_mid_kernel<P, true, 0, true> : boot_cheb_mid_kernel<P, false, 0, true>)
+                  : (stg_ok ? boot_cheb_mid_kernel<P, true, 0> : boot_cheb_mid_kernel<P, false, 0>);
+  auto cmk32 = nopf ? (stg_ok ? boot_cheb_mid_kernel<P, true, 1, true> : boot_cheb_mid_kernel<P, false, 1, true>)
+                    : (stg_ok ? boot_cheb_mid_kernel<P, true, 1> : boot_cheb_mid_kernel<P, false, 1>);
+  auto cmk32l = nopf ? (stg_ok ? boot_cheb_mid_kernel<P, true, 2, true> : boot_cheb_mid_kernel<P, false, 2, true>)
+                     : (stg_ok ? boot_cheb_mid_kernel<P, true, 2> : boot_cheb_mid_kernel<P, false, 2>);
   { TimerScope ts(a, DFM_KC_EIG_OTHER);
     const int64_t n = (int64_t)m * P;
     dim3 grid((unsigned)((n + 255) / 256), 1);
@@ -1830,7 +1959,8 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
       hipFuncSetAttribute((const void *)boot_prep_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
     hipLaunchKernelGGL(prep_a_kernel<P>, dim3(1), dim3(256), 0, st, fb, Q0, ps, apre);
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(256), prep_lds, st,
-                       fb, idx, eta, off, lst, w.trace, mid ? PFb : nullptr, E2b, Q0, ps, Zc, ldz, pz, ab, apre,
+                       fb, idx, eta, off, lst, w.trace, mid && !nopf ? PFb : nullptr, mid ? E2b : nullptr, Q0, ps, Zc,
+                       ldz, pz, ab, apre,
                        skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, lowp ? 1 : 0);
     if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
     if (cheb_lds > 65536)   // T > 3276: above the default dynamic-LDS cap
@@ -1861,7 +1991,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   auto horner_mid = [&](double c, double bbeta, double bfx, double lead, int lp = 0) {
     TimerScope ts(a, DFM_KC_EIG_APPLY);
     hipLaunchKernelGGL(lp == 0 ? cmk : lp == 1 ? cmk32 : cmk32l, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz,
-                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax);
+                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale);
   };
   // ... and the last one, S_0: the new basis into cur, with its Z, a, cc
   auto horner_last = [&](double c, double bbeta, const double *V0, int64_t v0s, double bfx) {
@@ -1887,6 +2017,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // blocking poll every `poll` steps, every step in the tail.
   const int first_poll = warm_started ? 1 : poll - 1;
   const bool ahead = pb && pb->host && pb->cap >= maxit + 2;
+  const bool probe = !ap2_probe_off();
   int it = 0, last_gemm = -1, last_cheb = -1, next_poll = first_poll, pend = -1, steps = -1;
   bool tail = false;
   if (skip0) {
@@ -1926,7 +2057,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
                            pz, ab, seed, w.S, FVb, ps);
       hipLaunchKernelGGL(boot_ap2_kernel<P>, dim3(nb), dim3(64 * BW), ap2_lds, st, fb, w, m, k, p, a.tol, it, 0,
                          it == maxit - 1 ? 1 : 0, cheb, ca[dg], ca[dg - 1], bb, eta, off, lst, qin, qs, alt, Zc, ldz,
-                         pz, ab, seed, ps);
+                         pz, ab, seed, ps, probe && it >= first_poll ? 1 : 0);
     }
     if (it >= first_poll) {
       if (ahead) {

@@ -98,6 +98,7 @@ struct FactArgs {
   long long *cnt = nullptr;       // device counters of replicate-iterations and GEMM products (nullptr: host stats)
   double spread = 0.0;            // lambda_1 / lambda_k of the base fit (>= 1: warm schedule)
   double lamk = 0.0;              // lambda_k of the base fit (> 0: a warm solve may start with the filter)
+  double fscale = 0.0;            // s > 0: fb.F = s * warm[:, :r], one rounding per element (0: no such identity)
   const PollBuf *pb = nullptr;
 };
 int eig_run_factored(const FactBase &fb, const EigArgs &a, const FactArgs &f);
