@@ -36,6 +36,58 @@ template <int P> constexpr int small_stride() { return 2 * P * P + 4 * P; }
 constexpr int kJacobiSweeps = 2;
 constexpr int kChebDMax = 8;   // highest filter degree (shifted_cheb's coefficient arrays hold kChebDMax + 1)
 
+// The stopping rule of both solvers (check_converged in dfm_eig.hip,
+// decide_converged in dfm_fact.hip: each sums its residual partials and
+// records next[j] = res in its own order, then asks here).
+// Wanted Ritz pair j < k with squared residual rs, th0 = |theta_1|, itc = the
+// Rayleigh-Ritz steps taken, prev = the previous step's residuals.
+//   tol >= 0, the strict rule: res_j <= tol gap_j (eigenvector error ~
+//   res / gap), gap_j the distance to the neighbouring Ritz values or, in the
+//   subspace form (EigWork::subspace; k == p has no unwanted value: the
+//   neighbours), to the first unwanted one theta_k; or the rounding floor
+//   res_j <= 2e-14 th0; or res_j <= 1e-11 th0 and stagnating (no 2x decrease).
+//   tol < 0, eigenvalue-only statistics (V, criteria, eigenvalues, trace): a
+//   Ritz value's error is quadratic in its residual, |theta_j - lambda_j| <=
+//   bnd_j = res_j^2 / (gap_j / 2) (Kato-Temple, neighbour gap halved for
+//   safety) <= -tol |theta_j|, or the floor; the caller sums bnd_j and
+//   theta_j over its columns for energy_converged.
+struct ColumnVerdict {
+  bool ok, floor;   // this column passes; it sits at the rounding floor
+  double res, bnd;  // sqrt(rs); the eigenvalue bound (tol < 0, else 0)
+};
+DFM_DEV ColumnVerdict column_verdict(double rs, int j, const double *th, double th0, const double *prev, int k,
+                                     int p, double tol, int itc, int subspace) {
+  ColumnVerdict v;
+  v.res = sqrt(rs);
+  double gap = INFINITY;
+  if (subspace && tol >= 0.0 && k < p) {
+    gap = fabs(th[j] - th[k]);
+  } else {
+    if (j > 0) gap = fmin(gap, fabs(th[j] - th[j - 1]));
+    if (j + 1 < p) gap = fmin(gap, fabs(th[j] - th[j + 1]));
+  }
+  v.floor = v.res <= 2e-14 * th0;
+  if (tol < 0.0) {
+    v.bnd = rs / (0.5 * gap);
+    v.ok = v.bnd <= -tol * fabs(th[j]) || v.floor;
+  } else {
+    const bool stagn = itc > 2 && v.res <= 1e-11 * th0 && v.res > 0.5 * prev[j];
+    v.bnd = 0.0;
+    v.ok = v.res <= tol * gap || v.floor || stagn;
+  }
+  return v;
+}
+// tol < 0: the summed bound (bsum, tsum: the wave's totals of bnd_j and
+// theta_j) moves the residual energy trace - sum_j theta_j, the numerator of
+// V(k) (src/criteria.jl:5), by at most -tol relative — the energy floored at
+// 1e-6 trace: below that the reference's own rounding of ||E||^2 already
+// exceeds -tol relative (exact-rank panels) — or every column is at the floor.
+// Called by one whole wave; floor_ok is this lane's columns' conjunction.
+DFM_DEV bool energy_converged(double bsum, double tsum, double trace, double tol, bool floor_ok) {
+  const double vnum = fmax(fabs(trace - tsum), 1e-6 * fabs(trace));
+  return bsum <= -tol * vnum || !__any(!floor_ok);
+}
+
 EigWork carve(char *base, int m, int nb, int P, int maxit);
 // Sum of the unconverged-replicate counts seen by the products of iterations
 // 0..last (shift = 1: the product of iteration it runs before that

@@ -66,45 +66,28 @@ DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, double t
                             int nrb, int k, int p, double tol, int it, int check_only) {
   const int lane = threadIdx.x & 63;
   if (!d && it > 0) {
-    // Converged when every wanted Ritz pair j < k satisfies
-    //   res_j <= tol * gap_j            (eigenvector error ~ res/gap <= tol)
-    // or sits at the rounding floor: res_j <= 2e-14 |theta_1|, or
-    //   res_j <= 1e-11 |theta_1| and stagnating (no 2x decrease).
+    // the rule is column_verdict / energy_converged (dfm_eig.h)
     const double *th = tail;
     const double *prev = tail + 2 * P + ((it - 1) & 1) * P;
     double *next = tail + 2 * P + (it & 1) * P;
     const double th0 = fabs(th[0]);
     bool ok = true;
     if (tol < 0.0) {
-      // Eigenvalue-only statistics (V, criteria, eigenvalues, trace): a Ritz
-      // value's error is quadratic in its residual, |theta_j - lambda_j| <=
-      // res_j^2 / gap_j (Kato-Temple; gap_j = distance to the neighbouring
-      // Ritz values, halved for safety).  Converged when every wanted
-      // eigenvalue is within -tol relative AND the summed bound moves the
-      // residual energy trace - sum_j theta_j (the numerator of V(k),
-      // src/criteria.jl:5) by at most -tol relative.
-      const double tv = -tol;
       double bsum = 0.0, tsum = 0.0;
       bool okall = true, floor_ok = true;
       for (int j = lane; j < k; j += 64) {
         double rs = 0.0;
         for (int r = 0; r < nrb; ++r) rs += rp[r * P + j];
-        double gap = INFINITY;
-        if (j > 0) gap = fmin(gap, fabs(th[j] - th[j - 1]));
-        if (j + 1 < p) gap = fmin(gap, fabs(th[j] - th[j + 1]));
-        const double bnd = rs / (0.5 * gap);
-        bsum += bnd;
+        const ColumnVerdict v = column_verdict(rs, j, th, th0, prev, k, p, tol, it, w.subspace);
+        bsum += v.bnd;
         tsum += th[j];
-        okall = okall && (bnd <= tv * fabs(th[j]) || sqrt(rs) <= 2e-14 * th0);
-        floor_ok = floor_ok && sqrt(rs) <= 2e-14 * th0;
-        if (rb == 0) next[j] = sqrt(rs);
+        okall = okall && v.ok;
+        floor_ok = floor_ok && v.floor;
+        if (rb == 0) next[j] = v.res;
       }
       bsum = wave_sum(bsum);
       tsum = wave_sum(tsum);
-      // residual energy floored at 1e-6 trace: below that the reference's own
-      // rounding of ||E||^2 already exceeds -tol relative (exact-rank panels)
-      const double vnum = fmax(fabs(tr - tsum), 1e-6 * fabs(tr));
-      ok = !__any(!okall) && (bsum <= tv * vnum || !__any(!floor_ok));
+      ok = !__any(!okall) && energy_converged(bsum, tsum, tr, tol, floor_ok);
     } else
     for (int j0 = 0; j0 < k; j0 += 64) {
       // lanes: j = j0 + lane / G, r = lane % G   with G = power of two >= nrb
@@ -122,17 +105,9 @@ DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, double t
         // lanes with r == 0 hold the column sums
         bool okj = true;
         if (j < k && r == 0) {
-          const double res = sqrt(v);
-          double gap = INFINITY;
-          if (w.subspace && k < p) {   // (k == p: no unwanted Ritz value, the neighbour rule)
-            gap = fabs(th[j] - th[k]);
-          } else {
-            if (j > 0) gap = fmin(gap, fabs(th[j] - th[j - 1]));
-            if (j + 1 < p) gap = fmin(gap, fabs(th[j] - th[j + 1]));
-          }
-          const bool stagn = it > 2 && res <= 1e-11 * th0 && res > 0.5 * prev[j];
-          okj = (res <= tol * gap || res <= 2e-14 * th0 || stagn);
-          if (rb == 0) next[j] = res;
+          const ColumnVerdict cv = column_verdict(v, j, th, th0, prev, k, p, tol, it, w.subspace);
+          okj = cv.ok;
+          if (rb == 0) next[j] = cv.res;
         }
         ok = ok && !__any(!okj);
       }

@@ -11,54 +11,30 @@
 // replicates.  H Z for a whole batch is ONE MFMA GEMM (dfm_gemm.hip) with H
 // resident in L2; everything else is O(T r p) per replicate.
 #include "dfm_eig.h"
+#include "dfm_fact_ws.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <vector>
+#include <type_traits>
 
 namespace dfm {
 
 // waves per replicate workgroup of the factored passes (prep, y2, ap2, Chebyshev)
-#ifndef DFM_BW
-#define DFM_BW 4
-#endif
-constexpr int BW = DFM_BW;   // dynamic LDS of ap2: 16 T + 4 bytes
+constexpr int BW = 4;
 
-// Z, the H.Z GEMM's B operand, replicate-major in 16-row chunks (round 6,
-// gemmh_zrm_kernel): replicate rep's element (s, c) at
-// rep zrs + (s >> 4) 16 pz + 16 c + (s & 15), zrs = round_up(T, 16) pz; the
-// chunk rows s >= T are zero (boot_prep_kernel writes them each call)
-DFM_DEV int64_t zrm_stride(int T, int pz) { return (int64_t)((T + 15) & ~15) * pz; }
-DFM_DEV int64_t zrm_ix(int rep, int s, int c, int pz, int64_t zrs) {
-  return (int64_t)rep * zrs + (int64_t)(s >> 4) * (16 * pz) + 16 * c + (s & 15);
-}
-// (the fp32 middle products' Z32 and HZ32 use the same indexing with float
-// elements, Z32 in the first half of Z's region, HZ32 in HZ's: round 8)
+// (Z's replicate-major chunk indexing, zrm_ix, is in dfm_internal.h; the fp32
+// middle products' Z32 and HZ32 use it with float elements, Z32 in the first
+// half of Z's region, HZ32 in HZ's)
 typedef float zf4 __attribute__((ext_vector_type(4)));
 
-// Per replicate: CSR of idx (bucket s lists t ascending — fixed summation
-// order, bit-reproducible), and trace(G*) = sum_t ||x*_t||^2 =
-// sum_t [F_t S F_t' + 2 eta_t F_t.(EL)_idx_t + eta_t^2 H_idx_t,idx_t].
-//
-// Round 6: the same kernel then forms the first H.Z product's operand
-// Z0 = P'D Q0 and the first step's ab = [a; cc] (a = F'Q0, cc = EL'Z0) —
-// the init pass of boot_ap2_kernel before, the same arithmetic in the same
-// order (its tile loop and zscatter_tail), without that pass's launch and
-// its reload of the CSR this kernel already holds in LDS.
-template <int P, bool STG>
-DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid, int wave, int lane,
-                           const double *set, const int *so, const int *sl, const double *Qn,
-                           double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab,
-                           const dv4 *aacc, double *sred, int ps, double *zst, const double *apre = nullptr,
-                           double *__restrict__ pvr = nullptr, bool z32 = false);
 // a = F'Q0 of the first product for the whole batch: F and the warm start Q0
-// are shared by every replicate, so boot_prep_kernel's per-workgroup tile
-// loop and fixed-order wave sums are run ONCE, in the same order (one
-// workgroup of the same shape: bit-identical), into apre in ab's layout
-// (round 6; before, every replicate's workgroup formed the same 16 x P block).
+// are shared by every replicate, so this one workgroup forms the 16 x P block
+// once, into apre in ab's layout; boot_prep_kernel copies it into every
+// replicate's ab.  Tiles per wave and the wave sums run in the order of the
+// per-replicate passes' a = F'Qn (boot_ap2_kernel, boot_cheb_kernel).
 template <int P>
-__global__ __launch_bounds__(256) void prep_a_kernel(FactBase fb, const double *__restrict__ Q0, int ps,
-                                                     double *__restrict__ apre) {
+__global__ __launch_bounds__(64 * BW) void prep_a_kernel(FactBase fb, const double *__restrict__ Q0, int ps,
+                                                         double *__restrict__ apre) {
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4, T = fb.T, r = fb.r;
@@ -83,6 +59,7 @@ __global__ __launch_bounds__(256) void prep_a_kernel(FactBase fb, const double *
 #pragma unroll
       for (int ct = 0; ct < NT; ++ct) aacc[ct] = mfma16(fa[g], qv[ct][g], aacc[ct]);
   }
+  // (the four-wave sum of wave_block_store, written out: see there)
   for (int wv = 0; wv < BW; ++wv) {
     if (wave == wv)
 #pragma unroll
@@ -100,17 +77,168 @@ __global__ __launch_bounds__(256) void prep_a_kernel(FactBase fb, const double *
   }
 }
 
+// Shared tail of prep, ap2 and the last Horner step: Z = P' D Qn by CSR gather
+// (bucket s lists t ascending), cc = EL' Z, and ab[rep] = [a (16 x P); cc
+// (16 x P)], a = F' Qn, with fixed-order wave sums.
+// From ap2 / the last Horner step (PREP = false) a is the caller's
+// accumulator aacc and Z is stored directly.  From prep (PREP = true) a is
+// copied from apre (prep_a_kernel), a tile's Z chunk (16 rows x pz,
+// contiguous in the replicate-major layout) leaves through this wave's LDS
+// stage zst (16 pz doubles) as 16-B pieces instead of one 128-B-strided
+// element per lane, as float if z32, and the same rows go to pvr (PV) if set.
+// The staged store measured -3 % in prep and +0.3 % in ap2 / the last Horner
+// step (profiles/r06_c3_ab.txt item 13), so those store directly.
+struct PrepTail {   // PREP = true
+  const double *apre;
+  double *zst, *pvr;
+  bool z32;
+};
+struct AccTail {   // PREP = false
+  const dv4 *aacc;
+};
+template <bool PREP> using TailSrc = std::conditional_t<PREP, PrepTail, AccTail>;
+template <int P, bool PREP>
+DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid, int wave, int lane,
+                           const double *set, const int *so, const int *sl, const double *Qn,
+                           double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab, double *sred, int ps,
+                           TailSrc<PREP> src) {
+  const int64_t zrs = zrm_stride(T, pz);
+  constexpr int NT = P / 16;
+  const int li = lane & 15, lk = lane >> 4;
+  dv4 cacc[NT];
+#pragma unroll
+  for (int ct = 0; ct < NT; ++ct) cacc[ct] = dv4{0.0, 0.0, 0.0, 0.0};
+  for (int tile = wave; tile < ntile; tile += BW) {
+    const int s0 = tile * 16;
+    // all four row groups' first GU bucket entries are fetched together
+    // (independent loads in flight); longer buckets finish serially
+    constexpr int GU = 3;
+    double z[4][NT];
+    int qn0[4], qn1[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int s = s0 + 4 * g + lk;
+      qn0[g] = s < T ? so[s] : 0;
+      qn1[g] = s < T ? so[s + 1] : 0;
+    }
+    double val[4][GU][NT], ev[4][GU];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int u = 0; u < GU; ++u) {
+        const int q = qn0[g] + u;
+        const bool ok = q < qn1[g];
+        const int t = sl[ok ? q : 0];
+        ev[g][u] = ok ? set[t] : 0.0;
+        // (lanes past their bucket issue no load: most second / third entries
+        // are empty, and these passes are bound by the texture-address unit)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+          val[g][u][ct] = (ok && 16 * ct + li < ps) ? Qn[(int64_t)t * ps + 16 * ct + li] : 0.0;
+      }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) {
+        double acc = 0.0;
+#pragma unroll
+        for (int u = 0; u < GU; ++u) acc = fma(ev[g][u], val[g][u][ct], acc);
+        z[g][ct] = acc;
+      }
+      for (int q = qn0[g] + GU; q < qn1[g]; ++q) {
+        const int t = sl[q];
+        const double e = set[t];
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+          z[g][ct] = fma(e, 16 * ct + li < ps ? Qn[(int64_t)t * ps + 16 * ct + li] : 0.0, z[g][ct]);
+      }
+    }
+    if constexpr (PREP) {
+      if (src.pvr) {   // the same rows as PV = P'D Qn in boot_cheb_mid_kernel's layout (compact rows, ps columns)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int s = s0 + 4 * g + lk;
+          if (s < T)
+#pragma unroll
+            for (int ct = 0; ct < NT; ++ct)
+              if (16 * ct + li < ps) src.pvr[(int64_t)s * ps + 16 * ct + li] = z[g][ct];
+        }
+      }
+      // (rows past T: 0, the chunk's pad-row value the H.Z GEMM's k-padding needs)
+      double *zst = src.zst;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the previous tile's staged reads are done
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+          if (16 * ct + li < pz) zst[16 * (16 * ct + li) + 4 * g + lk] = s0 + 4 * g + lk < T ? z[g][ct] : 0.0;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (src.z32) {   // the fp32 H.Z GEMM's operand: the same chunk indexing, float elements (round to nearest)
+        zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+        for (int e = lane; e < 4 * pz; e += 64)
+          zc4[e] = zf4{(float)zst[4 * e], (float)zst[4 * e + 1], (float)zst[4 * e + 2], (float)zst[4 * e + 3]};
+      } else {
+        double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+        for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{zst[2 * e], zst[2 * e + 1]};
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int s = s0 + 4 * g + lk;
+      const bool v = s < T;
+      const double ea = (v && li < r) ? fb.EL[(int64_t)s * r + li] : 0.0;
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) {
+        if (!PREP && v && 16 * ct + li < pz) Zc[zrm_ix(rep, s, 16 * ct + li, pz, zrs)] = z[g][ct];
+        cacc[ct] = mfma16(ea, z[g][ct], cacc[ct]);
+      }
+    }
+  }
+  double *abr = ab + (int64_t)rep * 32 * P;
+  if constexpr (PREP)
+    for (int e = tid; e < 16 * P; e += 64 * BW) abr[e] = src.apre[e];
+  // (the four-wave sum of wave_block_store, written out: see there)
+  for (int pass = PREP ? 1 : 0; pass < 2; ++pass) {
+    for (int wv = 0; wv < BW; ++wv) {
+      if (wave == wv)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int e = (ct * 4 + g) * 64 + lane;
+            double v = cacc[ct][g];
+            if constexpr (!PREP) v = pass ? v : src.aacc[ct][g];
+            sred[e] = (wv ? sred[e] : 0.0) + v;
+          }
+      __syncthreads();
+    }
+    for (int e = tid; e < NT * 256; e += 64 * BW) {
+      const int l = e & 63, g = (e >> 6) & 3, ct = e >> 8;
+      abr[pass * 16 * P + (4 * g + (l >> 4)) * P + 16 * ct + (l & 15)] = sred[e];
+    }
+    __syncthreads();
+  }
+}
+
+// Per replicate: CSR of idx (bucket s lists t ascending — fixed summation
+// order, bit-reproducible), PF = P'D F and e2 = P'D^2 1 for the middle Horner
+// steps, and trace(G*) = sum_t ||x*_t||^2 =
+// sum_t [F_t S F_t' + 2 eta_t F_t.(EL)_idx_t + eta_t^2 H_idx_t,idx_t];
+// then, from the CSR it still holds in LDS, the first H.Z product's operand
+// Z0 = P'D Q0 and the first step's ab = [a; cc] (a = F'Q0 from apre,
+// prep_a_kernel; cc = EL'Z0) through zscatter_tail.  Q0, Zc, ab and apre are
+// required; PF, E2, PV, FV are optional outputs.
 template <int P>
-__global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32_t *__restrict__ idx,
-                                                        const double *__restrict__ eta, int *__restrict__ off,
-                                                        int *__restrict__ lst, double *__restrict__ trace,
-                                                        double *__restrict__ PF, double *__restrict__ E2,
-                                                        const double *__restrict__ Q0, int ps,
-                                                        double *__restrict__ Zc, int64_t ldz, int pz,
-                                                        double *__restrict__ ab, const double *__restrict__ apre,
-                                                        double *__restrict__ PV, double *__restrict__ FV, int z32) {
+__global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const int32_t *__restrict__ idx,
+                                                            const double *__restrict__ eta, int *__restrict__ off,
+                                                            int *__restrict__ lst, double *__restrict__ trace,
+                                                            double *__restrict__ PF, double *__restrict__ E2,
+                                                            const double *__restrict__ Q0, int ps,
+                                                            double *__restrict__ Zc, int64_t ldz, int pz,
+                                                            double *__restrict__ ab, const double *__restrict__ apre,
+                                                            double *__restrict__ PV, double *__restrict__ FV, int z32) {
   // z32: Z0 leaves as float (the first product runs in fp32); PV, FV, a, cc stay fp64
-  static_assert(BW * 64 == 256, "prep runs the factored passes' wave layout");
+  static_assert(64 * BW == 256, "the scans and the tree sum below are written for 256 threads");
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
   __shared__ double zst[BW][16 * P];   // per-wave Z chunk staging (zscatter_tail)
@@ -215,30 +343,9 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
       }
       E2[(int64_t)rep * T + s] = a2;
     }
-  if (Zc) {
-    // a = F'Q0 in boot_ap2_kernel's init order (its tiles, its accumulator layout)
-    const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
+  {
+    const int lane = tid & 63, wave = tid >> 6;
     const int ntile = (T + 15) >> 4;
-    dv4 aacc[NT];
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) aacc[ct] = dv4{0.0, 0.0, 0.0, 0.0};
-    for (int tile = wave; tile < (apre ? 0 : ntile); tile += BW) {   // (apre: a = F'Q0 formed once per batch)
-      const int t0 = tile * 16;
-      double fa[4], qv[NT][4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int t = t0 + 4 * g + lk;
-        const int tc = min(t, T - 1);
-        fa[g] = (t < T && li < r) ? fb.F[(int64_t)tc * r + li] : 0.0;
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-          qv[ct][g] = (t < T && 16 * ct + li < ps) ? Q0[(int64_t)tc * ps + 16 * ct + li] : 0.0;
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) aacc[ct] = mfma16(fa[g], qv[ct][g], aacc[ct]);
-    }
     // the last chunk's rows past T (the H.Z GEMM's zero k-padding of B)
     {
       const int64_t zrs = zrm_stride(T, pz);
@@ -252,9 +359,9 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
     __syncthreads();   // so / set visible
     // (PV, FV: a warm solve without a first Rayleigh-Ritz step filters V0 = Q0 itself, so the middle Horner
     // steps' PV = P'D V0 is Z0 row by row and FV = F'V0 is a)
-    zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, aacc, sred, ps, zst[wave],
-                           apre, PV ? PV + (int64_t)rep * T * P : nullptr, z32 != 0);
-    if (FV && apre)
+    zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, sred, ps,
+                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, z32 != 0});
+    if (FV)
       for (int e = tid; e < 16 * P; e += 256) FV[(int64_t)rep * 16 * P + e] = apre[e];
   }
   double acc = 0.0;
@@ -283,21 +390,7 @@ __global__ __launch_bounds__(256) void boot_prep_kernel(FactBase fb, const int32
   if (tid == 0) trace[rep] = red[0];
 }
 
-// Z (the GEMM's B operand) has round_up(T, 16) rows, the pad rows zero, so
-// the H.Z GEMM streams it with running DMA pointers and no k-tail clamp
-static int64_t z_rows(int T) { return ((int64_t)T + 15) / 16 * 16; }
-// the middle Horner steps' per-replicate operands (boot_cheb_mid_kernel):
-// PF = P'D F (T x r, allocated T x 16), e2 = P'D^2 1 (T), FV = F'V0 (16 x P),
-// and F'F (16 x 16, shared)
-static size_t fact_mid_doubles(int T, int nb, int P) {
-  return (size_t)nb * T * 17 + (size_t)nb * 16 * P + 256;
-}
-size_t fact_workspace_bytes(int T, int nb, int P) {
-  const int64_t ldz = (int64_t)nb * P;
-  const int nrb = (T + EROWS - 1) / EROWS;
-  return (size_t)(z_rows(T) + T) * ldz * 8 + (size_t)nb * nrb * 2 * 32 * P * 8 + 4096 +
-         fact_mid_doubles(T, nb, P) * 8 + 4096;
-}
+size_t fact_workspace_bytes(int T, int nb, int P) { return fact_ws_layout(T, nb, P, P).total; }
 
 // ================================================= fused factored iteration
 // For T <= F2_T_MAX and r <= 16 (C3: T = 500, r = 8) one iteration of
@@ -317,8 +410,7 @@ size_t fact_workspace_bytes(int T, int nb, int P) {
 constexpr int F2_T_MAX = 4096;
 
 // Convergence verdict from per-column squared residuals res2[j] (j < k), on
-// one whole wave (same rules as check_converged: strict eigenvector-residual
-// test, or for tol < 0 the Kato-Temple eigenvalue bound).
+// one whole wave: the rule is column_verdict / energy_converged (dfm_eig.h).
 DFM_DEV bool decide_converged(const double *res2, const double *th, const double *prev, double *next,
                               int k, int p, double tol, double trace, int itc, int subspace) {
   const int lane = threadIdx.x & 63;
@@ -326,34 +418,20 @@ DFM_DEV bool decide_converged(const double *res2, const double *th, const double
   bool okall = true, floor_ok = true;
   double bsum = 0.0, tsum = 0.0;
   for (int j = lane; j < k; j += 64) {
-    const double rs = res2[j], res = sqrt(rs);
-    double gap = INFINITY;
-    if (subspace && tol >= 0.0 && k < p) {   // strict rule, subspace form (EigWork::subspace; k == p: neighbours)
-      gap = fabs(th[j] - th[k]);
-    } else {
-      if (j > 0) gap = fmin(gap, fabs(th[j] - th[j - 1]));
-      if (j + 1 < p) gap = fmin(gap, fabs(th[j] - th[j + 1]));
-    }
-    bool okj;
+    const ColumnVerdict v = column_verdict(res2[j], j, th, th0, prev, k, p, tol, itc, subspace);
     if (tol < 0.0) {
-      const double bnd = rs / (0.5 * gap);
-      bsum += bnd;
+      bsum += v.bnd;
       tsum += th[j];
-      okj = bnd <= -tol * fabs(th[j]) || res <= 2e-14 * th0;
-    } else {
-      const bool stagn = itc > 2 && res <= 1e-11 * th0 && res > 0.5 * prev[j];
-      okj = res <= tol * gap || res <= 2e-14 * th0 || stagn;
     }
-    floor_ok = floor_ok && res <= 2e-14 * th0;
-    okall = okall && okj;
-    next[j] = res;
+    floor_ok = floor_ok && v.floor;
+    okall = okall && v.ok;
+    next[j] = v.res;
   }
   bool ok = !__any(!okall);
   if (tol < 0.0) {
     bsum = wave_sum(bsum);
     tsum = wave_sum(tsum);
-    const double vnum = fmax(fabs(trace - tsum), 1e-6 * fabs(trace));
-    ok = ok && (bsum <= -tol * vnum || !__any(!floor_ok));
+    ok = ok && energy_converged(bsum, tsum, trace, tol, floor_ok);
   }
   return ok;
 }
@@ -400,7 +478,7 @@ struct Y2Tile {
 // and HZ[idx] row as r / 2 and pz / 2 pieces, the Q rows as one contiguous
 // range — and is transposed to its register layout there: half the load
 // requests of one-double-per-lane loads, for passes bound by the texture-
-// address unit (round 6).  Stage layout: F rows [0, 144) (kept for the
+// address unit.  Stage layout: F rows [0, 144) (kept for the
 // caller's accumulator-layout read of F, fa), EL rows [144, 288), then HZ
 // and Q rows over [144, 688) once the EL reads are done.
 constexpr int Y2_STG = 16 * 9 + 2 * 16 * 17;
@@ -489,6 +567,82 @@ DFM_DEV void y2_load(Y2Tile<P> &L, int tile, int T, int r, int KR, int lane, con
   }
 }
 
+// sa = a, sb = S a + cc (16 x P each, rows >= r of S a zero) from ab[rep] =
+// [a; cc]: the B operands of the tile products of y2 and the Horner steps.
+// Ends on a barrier.
+template <int P>
+DFM_DEV void load_ab(const FactBase &fb, const double *abr, double *sa, double *sb, int tid, int r) {
+  for (int e = tid; e < 16 * P; e += 64 * BW) sa[e] = abr[e];
+  __syncthreads();
+  for (int e = tid; e < 16 * P; e += 64 * BW) {
+    const int j = e / P, c = e % P;
+    double v = abr[16 * P + e];
+    if (j < r)
+      for (int i = 0; i < r; ++i) v = fma(fb.S[j * r + i], sa[i * P + c], v);
+    sb[e] = v;
+  }
+  __syncthreads();
+}
+
+// A replicate's image in dynamic LDS: eta (T doubles; 1 without eta), then
+// idx (T ints) if IDX, then the CSR — bucket starts (T + 1 ints) and the
+// sorted list (T ints) — if CSR; the pointers of an absent piece are passed
+// as null.  No barrier: the caller's next one publishes it.
+// (The pieces are template flags, not tests of the pointers: with the tests
+// at run time y2 and the last Horner step grew by 12 and 51 instructions,
+// profiles/r11_fact_refactor.txt section 1.)
+struct RepLds {
+  double *set;
+  int *six, *so, *sl;
+};
+template <bool IDX, bool CSR>
+DFM_DEV RepLds load_rep_lds(double *sdyn, int T, int tid, int rep, const int32_t *__restrict__ idx,
+                            const double *__restrict__ eta, const int *__restrict__ off,
+                            const int *__restrict__ lst) {
+  RepLds s;
+  s.set = sdyn;
+  s.six = (int *)(sdyn + T);
+  s.so = IDX ? s.six + T : s.six;
+  s.sl = s.so + T + 1;
+  const int32_t *ixg = IDX ? idx + (int64_t)rep * T : nullptr;
+  const double *etg = eta ? eta + (int64_t)rep * T : nullptr;
+  const int *o = CSR ? off + (int64_t)rep * (T + 1) : nullptr;
+  const int *L = CSR ? lst + (int64_t)rep * T : nullptr;
+  for (int e = tid; e < T; e += 64 * BW) {
+    if constexpr (IDX) s.six[e] = ixg[e];
+    s.set[e] = etg ? etg[e] : 1.0;
+    if constexpr (CSR) { s.so[e] = o[e]; s.sl[e] = L[e]; }
+  }
+  if (CSR && tid == 0) s.so[T] = o[T];
+  return s;
+}
+
+// One tile's yF = F bB and yE = EL[idx] a (16 x P each): A operands fA / eA of
+// the tile (Y2Tile), B operands sb / sa — from registers (bA, bB: the copies
+// y2 and the last Horner step hold) or, LDSB, re-read from LDS per tile.
+template <int P, bool LDSB>
+DFM_DEV void tile_yfe(const Y2Tile<P> &t, int KR, int li, int lk, const double *sa, const double *sb,
+                      const double (*bA)[P / 16], const double (*bB)[P / 16], dv4 *yF, dv4 *yE) {
+  constexpr int NT = P / 16;
+#pragma unroll
+  for (int ct = 0; ct < NT; ++ct) { yF[ct] = dv4{0.0, 0.0, 0.0, 0.0}; yE[ct] = yF[ct]; }
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    if (kk < KR) {
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) {
+        if constexpr (LDSB) {
+          yF[ct] = mfma16(t.fA[kk], sb[(4 * kk + lk) * P + 16 * ct + li], yF[ct]);
+          yE[ct] = mfma16(t.eA[kk], sa[(4 * kk + lk) * P + 16 * ct + li], yE[ct]);
+        } else {
+          yF[ct] = mfma16(t.fA[kk], bB[kk][ct], yF[ct]);
+          yE[ct] = mfma16(t.eA[kk], bA[kk][ct], yE[ct]);
+        }
+      }
+    }
+  }
+}
+
 // y2: one workgroup (4 waves) per replicate; wave w takes 16-row tiles w, w+4, ...
 template <int P, bool STG>
 // 4 workgroups per CU (~113 VGPRs, no spills; a tile is loaded at the top of
@@ -510,24 +664,10 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_y2_kernel(FactBase fb, EigWor
   __shared__ double red[3 * NT * NT * 256];
   extern __shared__ double sdyn[];                   // eta (T doubles), idx (T ints)
   __shared__ double stgy[STG ? BW : 1][STG ? Y2_STG : 1];   // per-wave operand staging (y2_load)
-  double *set = sdyn;
-  int *six = (int *)(sdyn + T);
-  {
-    const int32_t *ixg = idx + (int64_t)rep * T;
-    const double *etg = eta ? eta + (int64_t)rep * T : nullptr;
-    for (int e = tid; e < T; e += 64 * BW) { six[e] = ixg[e]; set[e] = etg ? etg[e] : 1.0; }
-  }
-  const double *abr = ab + (int64_t)rep * 32 * P;
-  for (int e = tid; e < 16 * P; e += 64 * BW) sa[e] = abr[e];
-  __syncthreads();
-  for (int e = tid; e < 16 * P; e += 64 * BW) {
-    const int j = e / P, c = e % P;
-    double v = abr[16 * P + e];
-    if (j < r)
-      for (int i = 0; i < r; ++i) v = fma(fb.S[j * r + i], sa[i * P + c], v);
-    sb[e] = v;
-  }
-  __syncthreads();
+  const RepLds rl = load_rep_lds<true, false>(sdyn, T, tid, rep, idx, eta, nullptr, nullptr);
+  const double *set = rl.set;
+  const int *six = rl.six;
+  load_ab<P>(fb, ab + (int64_t)rep * 32 * P, sa, sb, tid, r);
   const int KR = (r + 3) >> 2;
   double bA[4][NT], bB[4][NT];   // (STG: read from LDS per tile instead, to make room for the staged loader)
   if constexpr (!STG) {
@@ -555,23 +695,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_y2_kernel(FactBase fb, EigWor
     y2_load<P, STG>(cur, tile, T, r, KR, lane, six, fb, HZ, ldz, pz, rep, Qr, ps, stgy[STG ? wave : 0]);
     const int t0 = tile * 16;
     dv4 yF[NT], yE[NT];
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) { yF[ct] = dv4{0.0, 0.0, 0.0, 0.0}; yE[ct] = yF[ct]; }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      if (kk < KR) {
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          if constexpr (STG) {
-            yF[ct] = mfma16(cur.fA[kk], sb[(4 * kk + lk) * P + 16 * ct + li], yF[ct]);
-            yE[ct] = mfma16(cur.eA[kk], sa[(4 * kk + lk) * P + 16 * ct + li], yE[ct]);
-          } else {
-            yF[ct] = mfma16(cur.fA[kk], bB[kk][ct], yF[ct]);
-            yE[ct] = mfma16(cur.eA[kk], bA[kk][ct], yE[ct]);
-          }
-        }
-      }
-    }
+    tile_yfe<P, STG>(cur, KR, li, lk, sa, sb, bA, bB, yF, yE);
     double Yv[NT][4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -598,7 +722,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_y2_kernel(FactBase fb, EigWor
           acc[2][a][b] = mfma16(cur.q[a][g], cur.q[b][g], acc[2][a][b]);
         }
   }
-  // fixed-order sum over the four waves
+  // fixed-order sum over the four waves (wave_block_store's, over 3 NT^2 blocks)
   for (int wv = 0; wv < BW; ++wv) {
     if (wave == wv) {
 #pragma unroll
@@ -638,26 +762,25 @@ DFM_DEV double filter_end(const double *small, int k, int p, double bbeta) {
 }
 
 // One 16-row tile's operands for ap2 (ap2_load_lds): Q and Y rows in A-operand layout
-// (row t0 + (lane & 15), column 4kk + (lane >> 4)), F rows for a = F'Qn in
-// A-operand layout per row group g (row t0 + 4g + (lane >> 4), factor lane & 15),
-// and (init) Q in the accumulator layout.  Rows >= T read row T-1 (masked later).
+// (row t0 + (lane & 15), column 4kk + (lane >> 4)) and F rows for a = F'Qn in
+// A-operand layout per row group g (row t0 + 4g + (lane >> 4), factor lane & 15).
+// Rows >= T read row T-1 (masked later).
 template <int P>
 struct Ap2Tile {
-  double qa[P / 4], yo[P / 4], fa[4], q[P / 16][4];
+  double qa[P / 4], yo[P / 4], fa[4];
 };
 
-// ap2_load through a wave-private LDS transpose: the tile's Q and Y rows
-// (16 x P each) are read with coalesced 16-B loads (4 lanes per 128-B row)
-// and re-read from LDS in the MFMA A-operand layout (row lane & 15, column
+// The tile's Q and Y rows (16 x P each) through a wave-private LDS
+// transpose: read with coalesced 16-B loads (4 lanes per 128-B row) and
+// re-read from LDS in the MFMA A-operand layout (row lane & 15, column
 // 4 kk + (lane >> 4)), instead of 2 P/4 loads that each touch 16 rows.
-// Row stride P + 1: conflict-free A-layout reads.  F rows and the init
-// layout as ap2_load.
+// Row stride P + 1: conflict-free A-layout reads.
 template <int P>
-DFM_DEV void ap2_load_lds(Ap2Tile<P> &L, int tile, int T, int r, int lane, int init, const double *__restrict__ Qr,
+DFM_DEV void ap2_load_lds(Ap2Tile<P> &L, int tile, int T, int r, int lane, const double *__restrict__ Qr,
                           const double *Yr, const FactBase &fb, double *tq, double *ty, int ps, bool ldf = true) {
-  constexpr int NT = P / 16, KP = P / 4, PER = P / 4;   // doubles per lane per matrix
+  constexpr int KP = P / 4, PER = P / 4;   // doubles per lane per matrix
   const int li = lane & 15, lk = lane >> 4, t0 = tile * 16;
-  if (!init) {
+  {
     const int rr = lane >> 2, c0 = (lane & 3) * PER, t = t0 + rr;
     const bool ok = t < T;
     const int tc = ok ? t : T - 1;
@@ -682,9 +805,6 @@ DFM_DEV void ap2_load_lds(Ap2Tile<P> &L, int tile, int T, int r, int lane, int i
       L.qa[kk] = tq[li * (P + 1) + 4 * kk + lk];
       L.yo[kk] = ty[li * (P + 1) + 4 * kk + lk];
     }
-  } else {
-#pragma unroll
-    for (int kk = 0; kk < KP; ++kk) { L.qa[kk] = 0.0; L.yo[kk] = 0.0; }
   }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -694,148 +814,15 @@ DFM_DEV void ap2_load_lds(Ap2Tile<P> &L, int tile, int T, int r, int lane, int i
     // expanding windows' case without base factors, loads nothing)
     // (ldf = false, ap2's probe pass: no a = F'Qn there, no F rows)
     L.fa[g] = (ldf && t < T && li < r) ? fb.F[(int64_t)tc * r + li] : 0.0;
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) L.q[ct][g] = (init && 16 * ct + li < ps) ? Qr[(int64_t)tc * ps + 16 * ct + li] : 0.0;
   }
 }
 
-// Shared tail of ap2 and the Chebyshev step: Z = P' D Qn by CSR gather
-// (bucket s lists t ascending), cc = EL' Z, and the fixed-order wave sums of
-// a = F' Qn (aacc, accumulated by the caller) and cc into ab[rep].  STG (the
-// prep pass): zst is this wave's LDS staging (16 pz doubles) and a tile's Z
-// chunk (16 rows x pz, contiguous in the replicate-major layout) leaves as
-// 16-B pieces instead of one 128-B-strided element per lane — prep -3 %; in
-// ap2 / the last Horner step the same staging measured +0.3 % (round 6, item
-// 13 of profiles/r06_c3_ab.txt), so they store directly.
-template <int P, bool STG>
-DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid, int wave, int lane,
-                           const double *set, const int *so, const int *sl, const double *Qn,
-                           double *__restrict__ Zc, int pz, int rep, double *__restrict__ ab,
-                           const dv4 *aacc, double *sred, int ps, double *zst, const double *apre,
-                           double *__restrict__ pvr, bool z32) {
-  const int64_t zrs = zrm_stride(T, pz);
-  constexpr int NT = P / 16;
-  const int li = lane & 15, lk = lane >> 4;
-  dv4 cacc[NT];
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct) cacc[ct] = dv4{0.0, 0.0, 0.0, 0.0};
-  for (int tile = wave; tile < ntile; tile += BW) {
-    const int s0 = tile * 16;
-    // all four row groups' first GU bucket entries are fetched together
-    // (independent loads in flight); longer buckets finish serially
-    constexpr int GU = 3;
-    double z[4][NT];
-    int qn0[4], qn1[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int s = s0 + 4 * g + lk;
-      qn0[g] = s < T ? so[s] : 0;
-      qn1[g] = s < T ? so[s + 1] : 0;
-    }
-    double val[4][GU][NT], ev[4][GU];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int u = 0; u < GU; ++u) {
-        const int q = qn0[g] + u;
-        const bool ok = q < qn1[g];
-        const int t = sl[ok ? q : 0];
-        ev[g][u] = ok ? set[t] : 0.0;
-        // (lanes past their bucket issue no load: most second / third entries
-        // are empty, and these passes are bound by the texture-address unit)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-          val[g][u][ct] = (ok && 16 * ct + li < ps) ? Qn[(int64_t)t * ps + 16 * ct + li] : 0.0;
-      }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) {
-        double acc = 0.0;
-#pragma unroll
-        for (int u = 0; u < GU; ++u) acc = fma(ev[g][u], val[g][u][ct], acc);
-        z[g][ct] = acc;
-      }
-      for (int q = qn0[g] + GU; q < qn1[g]; ++q) {
-        const int t = sl[q];
-        const double e = set[t];
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-          z[g][ct] = fma(e, 16 * ct + li < ps ? Qn[(int64_t)t * ps + 16 * ct + li] : 0.0, z[g][ct]);
-      }
-    }
-    if (pvr) {   // the same rows as PV = P'D Qn in boot_cheb_mid_kernel's layout (compact rows, ps columns)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int s = s0 + 4 * g + lk;
-        if (s < T)
-#pragma unroll
-          for (int ct = 0; ct < NT; ++ct)
-            if (16 * ct + li < ps) pvr[(int64_t)s * ps + 16 * ct + li] = z[g][ct];
-      }
-    }
-    if constexpr (STG) {
-      // (rows past T: 0, the chunk's pad-row value the H.Z GEMM's k-padding needs)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the previous tile's staged reads are done
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-          if (16 * ct + li < pz) zst[16 * (16 * ct + li) + 4 * g + lk] = s0 + 4 * g + lk < T ? z[g][ct] : 0.0;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (z32) {   // the fp32 H.Z GEMM's operand: the same chunk indexing, float elements (round to nearest)
-        zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
-        for (int e = lane; e < 4 * pz; e += 64)
-          zc4[e] = zf4{(float)zst[4 * e], (float)zst[4 * e + 1], (float)zst[4 * e + 2], (float)zst[4 * e + 3]};
-      } else {
-        double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
-        for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{zst[2 * e], zst[2 * e + 1]};
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int s = s0 + 4 * g + lk;
-      const bool v = s < T;
-      const double ea = (v && li < r) ? fb.EL[(int64_t)s * r + li] : 0.0;
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) {
-        if (!STG && v && 16 * ct + li < pz) Zc[zrm_ix(rep, s, 16 * ct + li, pz, zrs)] = z[g][ct];
-        cacc[ct] = mfma16(ea, z[g][ct], cacc[ct]);
-      }
-    }
-  }
-  // a and cc: fixed-order sums over the waves -> ab[rep] = [a (16 x P); cc (16 x P)]
-  // (apre: a was formed once for the whole batch, prep_a_kernel — the same sums)
-  double *abr = ab + (int64_t)rep * 32 * P;
-  if (apre)
-    for (int e = tid; e < 16 * P; e += 64 * BW) abr[e] = apre[e];
-  for (int pass = apre ? 1 : 0; pass < 2; ++pass) {
-    for (int wv = 0; wv < BW; ++wv) {
-      if (wave == wv)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int e = (ct * 4 + g) * 64 + lane;
-            const double v = pass ? cacc[ct][g] : aacc[ct][g];
-            sred[e] = (wv ? sred[e] : 0.0) + v;
-          }
-      __syncthreads();
-    }
-    for (int e = tid; e < NT * 256; e += 64 * BW) {
-      const int l = e & 63, g = (e >> 6) & 3, ct = e >> 8;
-      abr[pass * 16 * P + (4 * g + (l >> 4)) * P + 16 * ct + (l & 15)] = sred[e];
-    }
-    __syncthreads();
-  }
-}
-
-// ap2: one workgroup per replicate.  init = 1: Qn := Q (the warm start), no
-// Ritz step.  Qn goes to global memory (over the Y rows this wave just read)
+// ap2: one workgroup per replicate, after the Rayleigh-Ritz step's eig_small.
+// Qn goes to global memory (over the Y rows this wave just read)
 // and is gathered back through the CSR after the barrier: same-CU L1, so the
 // workgroup-scope fence of __syncthreads makes it visible.  Dynamic LDS:
 // eta (T doubles), off (T+1 ints), lst (T ints) of this replicate.
-// probe (ignored with init): decide before writing.  A first pass over the
+// probe: decide before writing.  A first pass over the
 // tiles forms only u = Q A, Y A and the residuals (Q and Y tiles in, the sAm
 // MFMAs, no stores); the verdict follows as in the one-pass form.  A
 // replicate that retires (or a last launch) takes the exit without ever
@@ -848,7 +835,7 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
 template <int P>
 // 4 workgroups per CU (see boot_y2_kernel)
 __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWork w, int T, int k, int p, double tol,
-                                                       int it, int init, int last, int cheb, double fa1,
+                                                       int it, int last, double fa1,
                                                        double fa0, double bbeta, const double *__restrict__ eta,
                                                        const int *__restrict__ off, const int *__restrict__ lst,
                                                        const double *__restrict__ Qc, int64_t qs,
@@ -857,11 +844,8 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
                                                        int probe) {
   constexpr int NT = P / 16, KP = P / 4;
   const int rep = blockIdx.x;
-  if (!init && w.done[rep]) return;
-  const bool two = probe && !init;
+  if (w.done[rep]) return;
   extern __shared__ double sdyn[];
-  double *set = sdyn;                          // eta_t
-  int *so = (int *)(sdyn + T), *sl = so + T + 1;
   __shared__ double sred[NT * 256];
   __shared__ double sres[BW][P];
   __shared__ double stile[BW][2][16 * (P + 1)];   // per-wave Q / Y tile transposes (ap2_load_lds)
@@ -869,35 +853,31 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
   __shared__ double sAm[P * P], sBm[P * P];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = fb.r;
   const int li = lane & 15, lk = lane >> 4;
-  {
-    const double *et = eta ? eta + (int64_t)rep * T : nullptr;
-    const int *o = off + (int64_t)rep * (T + 1);
-    const int *L = lst + (int64_t)rep * T;
-    for (int e = tid; e < T; e += 64 * BW) { set[e] = et ? et[e] : 1.0; so[e] = o[e]; sl[e] = L[e]; }
-    if (tid == 0) so[T] = o[T];
-  }
+  const RepLds rl = load_rep_lds<false, true>(sdyn, T, tid, rep, nullptr, eta, off, lst);
+  const double *set = rl.set;
+  const int *so = rl.so, *sl = rl.sl;
   double *small = w.small + (int64_t)rep * small_stride<P>();
   // the Rayleigh-Ritz step's A and Bm (P x P each) in LDS: the MFMA B
-  // operands are read per tile instead of held in 2 KP NT registers (round 6:
-  // the kernel sat at 128 VGPRs with 32 B of scratch)
+  // operands are read per tile instead of held in 2 KP NT registers (held in
+  // registers the kernel sat at 128 VGPRs with 32 B of scratch)
   for (int e = tid; e < P * P; e += 64 * BW) {
-    sAm[e] = init ? 0.0 : small[e];
-    sBm[e] = init ? 0.0 : small[P * P + e];
+    sAm[e] = small[e];
+    sBm[e] = small[P * P + e];
   }
   double th[NT];
   bool dd[NT];
 #pragma unroll
   for (int ct = 0; ct < NT; ++ct) {
     const int c = 16 * ct + li;
-    th[ct] = init ? 0.0 : small[2 * P * P + c];
-    dd[ct] = init ? false : (small[2 * P * P + P + c] != 0.0);
+    th[ct] = small[2 * P * P + c];
+    dd[ct] = small[2 * P * P + P + c] != 0.0;
   }
   __syncthreads();
-  const double *Qr = Qc + (int64_t)rep * qs;   // qs = 0: the shared warm start (init / first step)
+  const double *Qr = Qc + (int64_t)rep * qs;   // (qs = 0: the warm start Q0, shared by every replicate)
   double *Yr = Yq + (int64_t)rep * T * P;
   // the filter's first Horner term (boot_cheb_kernel): S = (fa1 / b) Y Bm + fa0 Q Bm,
   // fa1 / fa0 = T*_d's y^d / y^(d-1) coefficients, b = filter_end
-  const double bch = init ? 0.0 : filter_end<P>(small, k, p, bbeta);
+  const double bch = filter_end<P>(small, k, p, bbeta);
   const double cf1 = bch > 0.0 ? fa1 / bch : 1.0, cf0 = bch > 0.0 ? fa0 : 0.0;
   double res2[NT];
   dv4 aacc[NT];
@@ -906,68 +886,82 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
   const int ntile = (T + 15) >> 4;
   // each tile's operands load at the top of its iteration (occupancy hides the latency)
   Ap2Tile<P> cur;
-  // the one-pass tile loop: u, Y A and the residuals, V0 and Qn out, a = F'Qn
+  // the loaded tile's residuals: u = Q A, Y A, res2 += (Y A - u diag(theta))^2 over the rows < T
+  auto tile_residuals = [&](int t0) {
+    dv4 u[NT], ya[NT];
+#pragma unroll
+    for (int ct = 0; ct < NT; ++ct) { u[ct] = dv4{0.0, 0.0, 0.0, 0.0}; ya[ct] = u[ct]; }
+#pragma unroll
+    for (int kk = 0; kk < KP; ++kk)
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) {
+        const double am = sAm[(4 * kk + lk) * P + 16 * ct + li];
+        u[ct] = mfma16(cur.qa[kk], am, u[ct]);
+        ya[ct] = mfma16(cur.yo[kk], am, ya[ct]);
+      }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const bool v = t0 + 4 * g + lk < T;
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) {
+        const double wr = ya[ct][g] - th[ct] * u[ct][g];
+        if (v && 16 * ct + li < k) res2[ct] = fma(wr, wr, res2[ct]);
+      }
+    }
+  };
+  // the one-pass tile loop: the residuals, then V0 and Qn out and a = F'Qn
+  // (the residuals' u and Y A are done with before V0 = Q Bm and Y Bm start:
+  // with all four products in one loop the kernel needs 128 VGPRs and 64 B of
+  // scratch, profiles/r11_fact_refactor.txt)
   auto tile_loop = [&]() {
     for (int tile = wave; tile < ntile; tile += BW) {
-      ap2_load_lds<P>(cur, tile, T, r, lane, init, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps);
+      ap2_load_lds<P>(cur, tile, T, r, lane, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps);
       const int t0 = tile * 16;
+      tile_residuals(t0);
       double qv[NT][4];
-      if (init) {
+      dv4 qn[NT], qb[NT];
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
+      for (int ct = 0; ct < NT; ++ct) { qn[ct] = dv4{0.0, 0.0, 0.0, 0.0}; qb[ct] = qn[ct]; }
 #pragma unroll
-          for (int ct = 0; ct < NT; ++ct) qv[ct][g] = (t0 + 4 * g + lk < T) ? cur.q[ct][g] : 0.0;
-      } else {
-        dv4 u[NT], ya[NT], qn[NT], qb[NT];
+      for (int kk = 0; kk < KP; ++kk)
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-          u[ct] = dv4{0.0, 0.0, 0.0, 0.0}; ya[ct] = u[ct]; qn[ct] = u[ct]; qb[ct] = u[ct];
+          const double bm = sBm[(4 * kk + lk) * P + 16 * ct + li];
+          qn[ct] = mfma16(cur.yo[kk], bm, qn[ct]);
+          qb[ct] = mfma16(cur.qa[kk], bm, qb[ct]);
         }
-#pragma unroll
-        for (int kk = 0; kk < KP; ++kk)
-#pragma unroll
-          for (int ct = 0; ct < NT; ++ct) {
-            const double am = sAm[(4 * kk + lk) * P + 16 * ct + li], bm = sBm[(4 * kk + lk) * P + 16 * ct + li];
-            u[ct] = mfma16(cur.qa[kk], am, u[ct]);
-            ya[ct] = mfma16(cur.yo[kk], am, ya[ct]);
-            qn[ct] = mfma16(cur.yo[kk], bm, qn[ct]);
-            if (cheb) qb[ct] = mfma16(cur.qa[kk], bm, qb[ct]);
-          }
-        if (cheb) {   // V0 = Q Bm for the filter's later steps (boot_cheb_kernel), kept in w.U
-          double *Xr = w.U + (int64_t)rep * T * P;
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int t = t0 + 4 * g + lk;
-            if (t < T)
-#pragma unroll
-              for (int ct = 0; ct < NT; ++ct) {
-                const int c = 16 * ct + li;
-                double x = qb[ct][g];
-                if (c < p && dd[ct]) x = hash_unit(seed, t, 1000003ull * (it + 1) + c);   // = S
-                if (c >= p) x = 0.0;
-                if (c < ps) Xr[(int64_t)t * ps + c] = x;
-              }
-          }
-        }
-        // every wave reads only its own tiles' Y rows, loaded (above) before
-        // these stores: Qn may overwrite this tile's Y rows
+      {   // V0 = Q Bm for the filter's later steps (boot_cheb_kernel), kept in w.U
+        double *Xr = w.U + (int64_t)rep * T * P;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int t = t0 + 4 * g + lk;
-          const bool v = t < T;
+          if (t < T)
 #pragma unroll
-          for (int ct = 0; ct < NT; ++ct) {
-            const int c = 16 * ct + li;
-            const double wr = ya[ct][g] - th[ct] * u[ct][g];
-            if (v && c < k) res2[ct] = fma(wr, wr, res2[ct]);
-            // the filter's first Horner term S_{d-1} = (a_d / b) K_1 + a_{d-1} V0
-            // (K_1 = Y Bm = G* V0), or the plain power step Y Bm
-            double q = cheb ? fma(cf1, qn[ct][g], cf0 * qb[ct][g]) : qn[ct][g];
-            if (c < p && dd[ct]) q = hash_unit(seed, t, 1000003ull * (it + 1) + c);
-            if (c >= p || !v) q = 0.0;
-            qv[ct][g] = q;
-            if (v && c < ps) Yr[(int64_t)t * ps + c] = q;
-          }
+            for (int ct = 0; ct < NT; ++ct) {
+              const int c = 16 * ct + li;
+              double x = qb[ct][g];
+              if (c < p && dd[ct]) x = hash_unit(seed, t, 1000003ull * (it + 1) + c);   // = S
+              if (c >= p) x = 0.0;
+              if (c < ps) Xr[(int64_t)t * ps + c] = x;
+            }
+        }
+      }
+      // every wave reads only its own tiles' Y rows, loaded (above) before
+      // these stores: Qn may overwrite this tile's Y rows
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int t = t0 + 4 * g + lk;
+        const bool v = t < T;
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) {
+          const int c = 16 * ct + li;
+          // the filter's first Horner term S_{d-1} = (a_d / b) K_1 + a_{d-1} V0
+          // (K_1 = Y Bm = G* V0; b <= 0, a degenerate block: the plain power step Y Bm)
+          double q = fma(cf1, qn[ct][g], cf0 * qb[ct][g]);
+          if (c < p && dd[ct]) q = hash_unit(seed, t, 1000003ull * (it + 1) + c);
+          if (c >= p || !v) q = 0.0;
+          qv[ct][g] = q;
+          if (v && c < ps) Yr[(int64_t)t * ps + c] = q;
         }
       }
 #pragma unroll
@@ -977,71 +971,47 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
     }
   };
   // probe: first only u, Y A and the residuals (no stores); the tile loop after the verdict, if the replicate goes on
-  if (two) {
+  if (probe) {
     for (int tile = wave; tile < ntile; tile += BW) {
-      ap2_load_lds<P>(cur, tile, T, r, lane, 0, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps, false);
-      const int t0 = tile * 16;
-      dv4 u[NT], ya[NT];
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) { u[ct] = dv4{0.0, 0.0, 0.0, 0.0}; ya[ct] = u[ct]; }
-#pragma unroll
-      for (int kk = 0; kk < KP; ++kk)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          const double am = sAm[(4 * kk + lk) * P + 16 * ct + li];
-          u[ct] = mfma16(cur.qa[kk], am, u[ct]);
-          ya[ct] = mfma16(cur.yo[kk], am, ya[ct]);
-        }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const bool v = t0 + 4 * g + lk < T;
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          const double wr = ya[ct][g] - th[ct] * u[ct][g];
-          if (v && 16 * ct + li < k) res2[ct] = fma(wr, wr, res2[ct]);
-        }
-      }
+      ap2_load_lds<P>(cur, tile, T, r, lane, Qr, Yr, fb, stile[wave][0], stile[wave][1], ps, false);
+      tile_residuals(tile * 16);
     }
   } else {
     tile_loop();
   }
   // residuals: sum over the 4 row-lanes of a column, then over waves (fixed order)
-  if (!init) {
 #pragma unroll
-    for (int ct = 0; ct < NT; ++ct) {
-      double v = res2[ct];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      if (lk == 0) sres[wave][16 * ct + li] = v;
-    }
+  for (int ct = 0; ct < NT; ++ct) {
+    double v = res2[ct];
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    if (lk == 0) sres[wave][16 * ct + li] = v;
   }
   __syncthreads();
   if (wave == 0) {
-    int conv = 0;
-    if (!init) {
-      if (lane < P) {
-        double v = sres[0][lane];
+    if (lane < P) {
+      double v = sres[0][lane];
 #pragma unroll
-        for (int wv = 1; wv < BW; ++wv) v += sres[wv][lane];
-        sres[0][lane] = v;
-      }
-      __builtin_amdgcn_wave_barrier();
-      const int itc = it + 1;
-      const double *prev = small + 2 * P * P + 2 * P + ((itc - 1) & 1) * P;
-      double *next = small + 2 * P * P + 2 * P + (itc & 1) * P;
-      conv = decide_converged(sres[0], small + 2 * P * P, prev, next, k, p, tol, w.trace[rep], itc, w.subspace) ? 1 : 0;
-#ifdef DFM_DIAG_X
-      diag_excess(sres[0], small + 2 * P * P, k, p, tol, w.trace[rep], rep, it);
-#endif
+      for (int wv = 1; wv < BW; ++wv) v += sres[wv][lane];
+      sres[0][lane] = v;
     }
+    __builtin_amdgcn_wave_barrier();
+    const int itc = it + 1;
+    const double *prev = small + 2 * P * P + 2 * P + ((itc - 1) & 1) * P;
+    double *next = small + 2 * P * P + 2 * P + (itc & 1) * P;
+    const int conv =
+        decide_converged(sres[0], small + 2 * P * P, prev, next, k, p, tol, w.trace[rep], itc, w.subspace) ? 1 : 0;
+#ifdef DFM_DIAG_X
+    diag_excess(sres[0], small + 2 * P * P, k, p, tol, w.trace[rep], rep, it);
+#endif
     if (lane == 0) {
       s_conv = conv;
       if (conv) { w.done[rep] = 1; w.iters[rep] = it + 1; }
-      else if (!init) atomicAdd(&w.active[it], 1);
+      else atomicAdd(&w.active[it], 1);
     }
   }
   __syncthreads();
-  if (!init && (s_conv || last)) {
+  if (s_conv || last) {
     if (w.no_vectors) return;   // eigenvalue-only statistics: eig_final reads theta only
     // Ritz vectors U = Q A for the final output (eig_final_kernel)
     double *Ur = w.U + (int64_t)rep * T * P;
@@ -1067,13 +1037,12 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_ap2_kernel(FactBase fb, EigWo
     }
     return;
   }
-  if (two) {
+  if (probe) {
     tile_loop();   // (its residuals are not read again)
     __syncthreads();   // every wave's Qn rows visible to the CSR gather (one pass: the verdict's barriers)
   }
   // Z = P' D Qn by CSR gather (bucket s lists t ascending), cc = EL' Z
-  const double *Qn = init ? Qr : Yr;
-  zscatter_tail<P, false>(fb, T, r, ntile, tid, wave, lane, set, so, sl, Qn, Zc, pz, rep, ab, aacc, sred, ps, nullptr);
+  zscatter_tail<P, false>(fb, T, r, ntile, tid, wave, lane, set, so, sl, Yr, Zc, pz, rep, ab, sred, ps, AccTail{aacc});
 }
 
 // One Horner step of the degree-d Chebyshev filter of the factored solver.
@@ -1113,29 +1082,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_kernel(FactBase fb, EigW
   __shared__ double sa[16 * P], sb[16 * P];
   __shared__ double sred[NT * 256];
   __shared__ double stg[STG ? BW : 1][STG ? Y2_STG : 1];   // per-wave operand staging (y2_load)
-  extern __shared__ double sdyn[];
-  double *set = sdyn;                          // eta_t
-  int *six = (int *)(sdyn + T);                // idx_t
-  int *so = six + T, *sl = so + T + 1;         // CSR of idx
-  {
-    const int32_t *ixg = idx + (int64_t)rep * T;
-    const double *etg = eta ? eta + (int64_t)rep * T : nullptr;
-    const int *o = off + (int64_t)rep * (T + 1);
-    const int *L = lst + (int64_t)rep * T;
-    for (int e = tid; e < T; e += 64 * BW) { six[e] = ixg[e]; set[e] = etg ? etg[e] : 1.0; so[e] = o[e]; sl[e] = L[e]; }
-    if (tid == 0) so[T] = o[T];
-  }
-  double *abr = ab + (int64_t)rep * 32 * P;
-  for (int e = tid; e < 16 * P; e += 64 * BW) sa[e] = abr[e];
-  __syncthreads();
-  for (int e = tid; e < 16 * P; e += 64 * BW) {
-    const int j = e / P, c = e % P;
-    double v = abr[16 * P + e];
-    if (j < r)
-      for (int i = 0; i < r; ++i) v = fma(fb.S[j * r + i], sa[i * P + c], v);
-    sb[e] = v;
-  }
-  __syncthreads();
+  extern __shared__ double sdyn[];             // eta, idx and the CSR of idx
+  const RepLds rl = load_rep_lds<true, true>(sdyn, T, tid, rep, idx, eta, off, lst);
+  const double *set = rl.set;
+  const int *six = rl.six, *so = rl.so, *sl = rl.sl;
+  load_ab<P>(fb, ab + (int64_t)rep * 32 * P, sa, sb, tid, r);
   const double *small = w.small + (int64_t)rep * small_stride<P>();
   const double b = bfix > 0.0 ? bfix : filter_end<P>(small, k, p, bbeta);
   // b <= 0 (a degenerate block): plain power steps
@@ -1163,18 +1114,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_kernel(FactBase fb, EigW
     y2_load<P, STG>(cur, tile, T, r, KR, lane, six, fb, HZ, ldz, pz, rep, Xr, ps, stg[STG ? wave : 0]);   // cur.q = V0 rows
     const int t0 = tile * 16;
     dv4 yF[NT], yE[NT];
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) { yF[ct] = dv4{0.0, 0.0, 0.0, 0.0}; yE[ct] = yF[ct]; }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      if (kk < KR) {
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          yF[ct] = mfma16(cur.fA[kk], bB[kk][ct], yF[ct]);
-          yE[ct] = mfma16(cur.eA[kk], bA[kk][ct], yE[ct]);
-        }
-      }
-    }
+    tile_yfe<P, false>(cur, KR, li, lk, sa, sb, bA, bB, yF, yE);
     double qv[NT][4], fa[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -1202,7 +1142,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_kernel(FactBase fb, EigW
       for (int ct = 0; ct < NT; ++ct) aacc[ct] = mfma16(fa[g], qv[ct][g], aacc[ct]);
   }
   __syncthreads();   // every wave's Qn rows visible to the CSR gather
-  zscatter_tail<P, false>(fb, T, r, ntile, tid, wave, lane, set, so, sl, Qr, Zc, pz, rep, ab, aacc, sred, ps, nullptr);
+  zscatter_tail<P, false>(fb, T, r, ntile, tid, wave, lane, set, so, sl, Qr, Zc, pz, rep, ab, sred, ps, AccTail{aacc});
 }
 
 // The middle Horner steps in row-local form.  With W = G* S_{i+1} = F bB +
@@ -1246,6 +1186,9 @@ hipError_t launch_fact_ftf(const FactBase &fb, double *FtF, hipStream_t st) {
 }
 
 // fixed-order sum over the waves of a 16 x P accumulator block -> dst (row-major, stride P)
+// (used by the middle Horner steps alone.  prep_a, zscatter_tail and y2 keep the same sum written out: those
+// kernels and the middle steps sit at 125-128 VGPRs, and with the helper shared the order in which the compiler
+// inlines it moves spills between boot_cheb_mid_kernel's instances, profiles/r11_fact_refactor.txt section 1)
 template <int P>
 DFM_DEV void wave_block_store(const dv4 *acc, double *sred, int wave, int lane, int tid, double *__restrict__ dst) {
   constexpr int NT = P / 16;
@@ -1349,7 +1292,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_pv_kernel(FactBase fb, EigWor
   }
 }
 
-// LP (round 8, the fp32 middle products of a warm eigenvalue-rule solve): 0 =
+// LP (the fp32 middle products of a warm eigenvalue-rule solve): 0 =
 // HZ and Z in fp64 as described; 1 = HZ arrives as float HZ32 = H32 Z32 in Z's
 // replicate-major chunk layout (this replicate's 16-row tile one contiguous
 // 64 pz-byte piece, fetched as 16-B pieces and transposed through the EL
@@ -1390,7 +1333,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   const int li = lane & 15, lk = lane >> 4;
   __shared__ double sa[16 * P], sb[16 * P];
   __shared__ double sred[NT * 256];
-  // per-wave staging (round 6: this pass is bound by the texture-address unit,
+  // per-wave staging (this pass is bound by the texture-address unit,
   // TA_TA_BUSY 0.95 of its cycles): the tile's PF and EL rows arrive as ONE
   // contiguous 16-row range each (16 r doubles) instead of two differently
   // shaped gathers of the same rows, and the tile's Z chunk (16 rows x pz,
@@ -1403,6 +1346,8 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   static_assert(!NOPF || MID_STG >= 16 * (P | 1), "... or 16 PV rows of ps <= P columns at an odd stride");
   __shared__ double stgP[BW][MID_STG], stgE[BW][16 * 17];
   double *abr = ab + (int64_t)rep * 32 * P;
+  // (load_ab, written out: through the helper <32, false, 0, true> spills 8 B more, profiles/r11_fact_refactor.txt)
+  // sa = a, sb = S a + cc
   for (int e = tid; e < 16 * P; e += 64 * BW) sa[e] = abr[e];
   __syncthreads();
   for (int e = tid; e < 16 * P; e += 64 * BW) {
@@ -1724,8 +1669,8 @@ static bool warm_keep_step0() {   // (read at every solve: one process can run b
   return e && atoi(e) != 0;
 }
 // Under the eigenvalue rule (tol < 0) the middle products of that filter-only
-// step — products 1 .. d0 - 1 of its d0 — run in fp32 (gemmh_zrm_f32_kernel,
-// round 8).  The filter only has to deliver a good subspace: the Rayleigh-Ritz
+// step — products 1 .. d0 - 1 of its d0 — run in fp32
+// (gemmh_zrm_f32_kernel).  The filter only has to deliver a good subspace: the Rayleigh-Ritz
 // step behind it and the Kato-Temple stopping rule stay fp64 and measure the
 // true residual, the eigenvalue error is quadratic in the subspace error, and
 // the rounding noise (relative to the idiosyncratic part H Z alone: PF bB,
@@ -1852,6 +1797,26 @@ __global__ __launch_bounds__(1024) void q0_guards_kernel(double *__restrict__ Q0
   }
 }
 
+// The kernel instances eig_run_fact2_t launches.  stg: the loaders staged
+// through LDS (y2_load's STG, the middle steps' FAST), which exist for P = 16
+// only.  lp, nopf: boot_cheb_mid_kernel's LP and NOPF.
+template <int P>
+static auto y2_instance(bool stg) { return stg ? boot_y2_kernel<P, P == 16> : boot_y2_kernel<P, false>; }
+template <int P>
+static auto cheb_instance(bool stg) { return stg ? boot_cheb_kernel<P, P == 16> : boot_cheb_kernel<P, false>; }
+template <int P>
+static auto cheb_mid_instance(bool stg, int lp, bool nopf) {
+  constexpr bool F = P == 16;
+  static constexpr decltype(&boot_cheb_mid_kernel<P, false, 0, false>) tab[2][2][3] = {
+      {{boot_cheb_mid_kernel<P, false, 0, false>, boot_cheb_mid_kernel<P, false, 1, false>,
+        boot_cheb_mid_kernel<P, false, 2, false>},
+       {boot_cheb_mid_kernel<P, F, 0, false>, boot_cheb_mid_kernel<P, F, 1, false>, boot_cheb_mid_kernel<P, F, 2, false>}},
+      {{boot_cheb_mid_kernel<P, false, 0, true>, boot_cheb_mid_kernel<P, false, 1, true>,
+        boot_cheb_mid_kernel<P, false, 2, true>},
+       {boot_cheb_mid_kernel<P, F, 0, true>, boot_cheb_mid_kernel<P, F, 1, true>, boot_cheb_mid_kernel<P, F, 2, true>}}};
+  return tab[nopf][stg][lp];
+}
+
 static int first_filter_degree(double spread) {
   const double ratio = std::max(1.0001, 1.1 * spread);
   const int d = (int)std::floor(std::log(1e6) / std::log(ratio));
@@ -1872,7 +1837,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // Z / HZ hold pz = p rounded up to even columns per replicate (the GEMM's
   // 16-byte DMA pairs): the H.Z GEMM's work scales with the block p, not P
   const int pz = (p + 1) & ~1;
-  // (round 6, measured and rejected: Z / HZ rows padded to 128-B lines cut the
+  // (measured and rejected: Z / HZ rows padded to 128-B lines cut the
   // H.Z GEMM's FETCH_SIZE 0.40 -> 0.32 GB per launch — unpadded, a 512-B tile
   // row straddles five lines, one shared with another XCD's column block — but
   // left the GEMM's time unchanged and slowed the gathering passes 2-4 % with
@@ -1888,16 +1853,15 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // replicate's final Ritz vectors (U, row stride P, eig_final_kernel) never
   // overlap another replicate's compact rows.
   const int ps = pz;
-  double *Zc = (double *)f.fws;
-  double *HZ = Zc + (size_t)z_rows(m) * ldz;
-  double *ab = HZ + (size_t)m * ldz;
-  // middle Horner steps' operands (fact_mid_doubles), after ab's region
-  double *PFb = ab + (size_t)nb * ((m + EROWS - 1) / EROWS) * 2 * 32 * P + 512;
-  double *E2b = PFb + (size_t)nb * m * 16, *FVb = E2b + (size_t)nb * m, *FtF = FVb + (size_t)nb * 16 * P;
+  const FactWsLayout wl = fact_ws_layout(m, nb, P, pz);
+  auto ws_at = [&](size_t o) { return (double *)(f.fws + o); };
+  double *Zc = ws_at(wl.Z), *HZ = ws_at(wl.HZ), *ab = ws_at(wl.ab);
+  // the middle Horner steps' operands
+  double *PFb = ws_at(wl.PF), *E2b = ws_at(wl.e2), *FVb = ws_at(wl.FV), *FtF = ws_at(wl.FtF);
   // dynamic LDS of ap2 and of the last Horner step (eta, idx, CSR: 20 T bytes)
   const size_t ap2_lds = (size_t)m * 8 + (size_t)(2 * m + 1) * 4;
   const size_t cheb_lds = (size_t)m * 8 + (size_t)(3 * m + 1) * 4;
-  {   // counters, flags and Z's zero k-padding rows: one launch
+  {   // counters and flags: one launch
     ZeroSpans zs{};
     zs.p[0] = w.active; zs.n[0] = maxit + 2;
     zs.p[1] = w.iters; zs.n[1] = nb;
@@ -1906,20 +1870,28 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   }
   const uint64_t seed = 0x5eed0000ull + (uint64_t)m * 131 + k;
   double *cur = w.Q, *alt = w.Y;
-  const int cheb = 1;   // degree-2 Chebyshev filter between Rayleigh-Ritz steps
-  // the warm start is the same for every replicate: ONE m x P block (Q0),
-  // read with replicate stride 0 by the init pass and the first step's y2 /
-  // ap2 (L2-resident) instead of nb materialised copies
-  double *Q0 = nullptr;
-  if (stream_malloc((void **)&Q0, (size_t)m * P * 8 + (size_t)16 * P * 8 + (size_t)(nb + 4) * 4, st) != hipSuccess)
-    return 1002;
-  double *apre = Q0 + (size_t)m * P;   // a = F'Q0, the same for every replicate (prep_a_kernel)
-  // straggler phase (< 1/8 of the batch active at a poll): the GEMMs tile only
-  // the listed replicates' column groups (list built once, a superset of the
-  // later active sets; replicates retired since are computed and ignored)
-  int *alist = (int *)(apre + 16 * P), *acount = alist + nb;
+  // One stream-ordered block of the solve's own:
+  //   Q0      the warm start, the same for every replicate: ONE m x P block,
+  //           read with replicate stride 0 by prep and the first step's y2 /
+  //           ap2 (L2-resident) instead of nb materialised copies
+  //   apre    a = F'Q0 (16 x P), the same for every replicate (prep_a_kernel)
+  //   alist   straggler phase (< 1/8 of the batch active at a poll): the GEMMs
+  //           tile only the listed replicates' column groups (nb ints; list
+  //           built once, a superset of the later active sets; replicates
+  //           retired since are computed and ignored)
+  //   acount  its length (4 ints)
+  struct { size_t Q0, apre, alist, acount, total; } ql;
+  ql.Q0 = 0;
+  ql.apre = ql.Q0 + (size_t)m * P * 8;
+  ql.alist = ql.apre + (size_t)16 * P * 8;
+  ql.acount = ql.alist + (size_t)nb * 4;
+  ql.total = ql.acount + 4 * 4;
+  char *qblk = nullptr;
+  if (stream_malloc((void **)&qblk, ql.total, st) != hipSuccess) return 1002;
+  double *Q0 = (double *)(qblk + ql.Q0), *apre = (double *)(qblk + ql.apre);
+  int *alist = (int *)(qblk + ql.alist), *acount = (int *)(qblk + ql.acount);
   bool cl_on = false;
-  struct Q0Free { double *q; hipStream_t s; ~Q0Free() { hipFreeAsync(q, s); } } q0free{Q0, st};
+  struct Q0Free { char *q; hipStream_t s; ~Q0Free() { hipFreeAsync(q, s); } } q0free{qblk, st};
   const double *qin = Q0;
   int64_t qs = 0;
   const bool warm_started = a.warm && a.kw >= k && f.spread >= 1.0;
@@ -1929,10 +1901,10 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // ... and, from a warm start, no Rayleigh-Ritz step in front of it (warm_keep_step0)
   const double bfix = kWarmFixBeta * f.lamk;
   const bool skip0 = warm_started && mid && maxit >= 2 && bfix > 0.0 && p <= Q0G_PMAX && !warm_keep_step0();
-  // the last Horner step stages F / EL[idx] rows through LDS for r <= 8 (round 6)
+  // y2 and the Horner steps stage F / EL[idx] rows through LDS for even r <= 8 (y2_load's STG)
   const bool stg_ok = P == 16 && fb.r <= 8 && (fb.r & 1) == 0 && pz <= 16;
-  auto chk = stg_ok ? boot_cheb_kernel<P, P == 16> : boot_cheb_kernel<P, false>;
-  auto y2k = stg_ok ? boot_y2_kernel<P, P == 16> : boot_y2_kernel<P, false>;
+  auto chk = cheb_instance<P>(stg_ok);
+  auto y2k = y2_instance<P>(stg_ok);
   // ... whose middle products run in fp32 under the eigenvalue rule (fact_f32_off)
   const bool lowp = skip0 && a.tol < 0.0 && fb.H32 && std::isfinite(fb.hmax) && fb.hmax > 0.0 && m >= 16 && !fact_f32_off();
   // ... and may take PF = P'D F from PV's rows (boot_cheb_mid_kernel's NOPF; off by default, fact_pf_stored):
@@ -1940,25 +1912,17 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // The middle steps behind a first Rayleigh-Ritz step (warm_keep_step0; PV = P'D (Q Bm), boot_pv_kernel) have
   // no such identity and always read stored PF.
   const bool nopf = skip0 && f.fscale > 0.0 && a.kw >= fb.r && !fact_pf_stored();
-  // (lp 0: fp64 HZ in, fp64 Z out; 1: HZ32 in, Z32 out; 2: HZ32 in, fp64 Z out)
-  auto cmk = nopf ? (stg_ok ? boot_cheb_mid_kernel<P, true, 0, true> : boot_cheb_mid_kernel<P, false, 0, true>)
-                  : (stg_ok ? boot_cheb_mid_kernel<P, true, 0> : boot_cheb_mid_kernel<P, false, 0>);
-  auto cmk32 = nopf ? (stg_ok ? boot_cheb_mid_kernel<P, true, 1, true> : boot_cheb_mid_kernel<P, false, 1, true>)
-                    : (stg_ok ? boot_cheb_mid_kernel<P, true, 1> : boot_cheb_mid_kernel<P, false, 1>);
-  auto cmk32l = nopf ? (stg_ok ? boot_cheb_mid_kernel<P, true, 2, true> : boot_cheb_mid_kernel<P, false, 2, true>)
-                     : (stg_ok ? boot_cheb_mid_kernel<P, true, 2> : boot_cheb_mid_kernel<P, false, 2>);
   { TimerScope ts(a, DFM_KC_EIG_OTHER);
     const int64_t n = (int64_t)m * P;
     dim3 grid((unsigned)((n + 255) / 256), 1);
     hipLaunchKernelGGL(eig_init_kernel<P>, grid, dim3(256), 0, st, Q0, m, p, a.warm, a.kw, w.done, seed, (int64_t)0, ps);
     if (skip0) hipLaunchKernelGGL(q0_guards_kernel, dim3(1), dim3(1024), 0, st, Q0, m, ps, a.kw, p, w.active, nb);
-    // the CSR, trace, PF / e2 and the first product's Z0 and ab (the init
-    // pass boot_ap2_kernel<init = 1> ran separately before round 6)
+    // the CSR, trace, PF / e2 and the first product's Z0 and ab
     const size_t prep_lds = (size_t)((4 * m + 3) & ~1) * 4 + (size_t)m * 8;
     if (prep_lds > 65536)   // T > 2730 (up to F2_T_MAX: 96 KB): above the default dynamic-LDS cap
       hipFuncSetAttribute((const void *)boot_prep_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-    hipLaunchKernelGGL(prep_a_kernel<P>, dim3(1), dim3(256), 0, st, fb, Q0, ps, apre);
-    hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(256), prep_lds, st,
+    hipLaunchKernelGGL(prep_a_kernel<P>, dim3(1), dim3(64 * BW), 0, st, fb, Q0, ps, apre);
+    hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(64 * BW), prep_lds, st,
                        fb, idx, eta, off, lst, w.trace, mid && !nopf ? PFb : nullptr, mid ? E2b : nullptr, Q0, ps, Zc,
                        ldz, pz, ab, apre,
                        skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, lowp ? 1 : 0);
@@ -1990,8 +1954,8 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // (lp: 0 = fp64 HZ in, fp64 Z out; 1 = HZ32 in, Z32 out; 2 = HZ32 in, fp64 Z out)
   auto horner_mid = [&](double c, double bbeta, double bfx, double lead, int lp = 0) {
     TimerScope ts(a, DFM_KC_EIG_APPLY);
-    hipLaunchKernelGGL(lp == 0 ? cmk : lp == 1 ? cmk32 : cmk32l, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz,
-                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale);
+    hipLaunchKernelGGL(cheb_mid_instance<P>(stg_ok, lp, nopf), dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz, pz,
+                       ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale);
   };
   // ... and the last one, S_0: the new basis into cur, with its Z, a, cc
   auto horner_last = [&](double c, double bbeta, const double *V0, int64_t v0s, double bfx) {
@@ -2055,9 +2019,9 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
       if (mid && it == 0 && it < maxit - 1)   // before ap2 overwrites Z(Q) and a(Q)
         hipLaunchKernelGGL(boot_pv_kernel<P>, dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, it, eta, off, lst, Zc, ldz,
                            pz, ab, seed, w.S, FVb, ps);
-      hipLaunchKernelGGL(boot_ap2_kernel<P>, dim3(nb), dim3(64 * BW), ap2_lds, st, fb, w, m, k, p, a.tol, it, 0,
-                         it == maxit - 1 ? 1 : 0, cheb, ca[dg], ca[dg - 1], bb, eta, off, lst, qin, qs, alt, Zc, ldz,
-                         pz, ab, seed, ps, probe && it >= first_poll ? 1 : 0);
+      hipLaunchKernelGGL(boot_ap2_kernel<P>, dim3(nb), dim3(64 * BW), ap2_lds, st, fb, w, m, k, p, a.tol, it,
+                         it == maxit - 1 ? 1 : 0, ca[dg], ca[dg - 1], bb, eta, off, lst, qin, qs, alt, Zc, ldz, pz, ab,
+                         seed, ps, probe && it >= first_poll ? 1 : 0);
     }
     if (it >= first_poll) {
       if (ahead) {
@@ -2090,7 +2054,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
         next_poll = it + ((int64_t)act * 8 < nb ? 1 : poll);
       }
     }
-    if (cheb && it < maxit - 1) {
+    if (it < maxit - 1) {
       // Filter: d - 1 products G* S_{i+1} and Horner steps S_i, i = d-2 .. 0: the new
       // basis S_0 goes back into cur (Q), Y stays in alt
       for (int sp = 2; sp <= dg; ++sp) {
@@ -2128,69 +2092,11 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
 }
 
 int eig_run_factored(const FactBase &fb, const EigArgs &a, const FactArgs &f) {
-  if (a.p < a.k || a.p > 32 || a.p > fb.T || fb.r > 32) return -1;
-  if (fb.r > 16 || fb.T > F2_T_MAX) return -1;   // callers take the direct path
+  // (r > 16 or T > F2_T_MAX: callers take the direct path)
+  if (a.p < a.k || a.p > 32 || a.p > fb.T || fb.r > 16 || fb.T > F2_T_MAX) return -1;
   if (a.p <= 16) return eig_run_fact2_t<16>(fb, a, f);
   return eig_run_fact2_t<32>(fb, a, f);
 }
 int fact_t_max() { return F2_T_MAX; }
 
-// ---- dfm_debug_hz_f32 (tests/test_gpu_f32_filter.py): the fp32 H.Z GEMM on
-// operands packed as the solver packs them.
-__global__ void dbg_diag_kernel(const double *__restrict__ H, int64_t ldH, int T, double *__restrict__ hd) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < T) hd[t] = H[(int64_t)t * ldH + t];
-}
-// Z (T x nb pz, row-major, column block = replicate) -> Z32 chunks (zrm_ix, float, chunk rows past T zero)
-__global__ void dbg_pack_z32_kernel(const double *__restrict__ Z, int T, int nb, int pz, float *__restrict__ Z32) {
-  const int64_t zrs = zrm_stride(T, pz), n = (int64_t)nb * zrs;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int rep = (int)(i / zrs);
-  const int64_t o = i - (int64_t)rep * zrs;
-  const int ch = (int)(o / (16 * pz)), w = (int)(o - (int64_t)ch * 16 * pz), c = w >> 4, s = 16 * ch + (w & 15);
-  Z32[zrm_ix(rep, s, c, pz, zrs)] = s < T ? (float)Z[(int64_t)s * nb * pz + (int64_t)rep * pz + c] : 0.0f;
-}
-__global__ void dbg_unpack_hz32_kernel(const float *__restrict__ C32, int T, int nb, int pz, double *__restrict__ out) {
-  const int64_t n = (int64_t)T * nb * pz, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int s = (int)(i / ((int64_t)nb * pz));
-  const int x = (int)(i - (int64_t)s * nb * pz), rep = x / pz, c = x - rep * pz;
-  out[i] = (double)C32[zrm_ix(rep, s, c, pz, zrm_stride(T, pz))];
-}
 }  // namespace dfm
-
-// Debug entry, not part of include/dfm.h.  H: device, T x ldH fp64, ldH >=
-// round_up(T, 16) with zero padding columns; Z: device, T x nb pz fp64
-// (replicate rep's columns rep pz .. rep pz + pz - 1).  Builds H32 =
-// float(H / hmax) (fact_h32_kernel) and Z32, runs gemmh_zrm_f32_kernel and
-// writes out = double(H32 Z32) as T x nb pz — NOT rescaled by hmax, which is
-// returned in *hmax_out (may be null).
-extern "C" int dfm_debug_hz_f32(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
-                                double *out, double *hmax_out) {
-  using namespace dfm;
-  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || ldH < (T + 15) / 16 * 16 || (ldH & 3)) return -1;
-  hipStream_t st = ctx_stream(ctx);
-  const int64_t zrs = (int64_t)((T + 15) & ~15) * pz;
-  char *buf = nullptr;
-  const size_t b_hd = ((size_t)T * 8 + 255) & ~size_t(255), b_h32 = ((size_t)T * ldH * 4 + 255) & ~size_t(255),
-               b_z = ((size_t)nb * zrs * 4 + 255) & ~size_t(255);
-  if (hipMalloc((void **)&buf, b_hd + b_h32 + 2 * b_z) != hipSuccess) return 1002;
-  double *hd = (double *)buf;
-  float *H32 = (float *)(buf + b_hd), *Z32 = (float *)(buf + b_hd + b_h32), *C32 = (float *)(buf + b_hd + b_h32 + b_z);
-  hipLaunchKernelGGL(dbg_diag_kernel, dim3((T + 255) / 256), dim3(256), 0, st, H, ldH, T, hd);
-  hipError_t e = launch_fact_h32(H, ldH, T, hd, H32, st);
-  hipLaunchKernelGGL(dbg_pack_z32_kernel, dim3((unsigned)(((int64_t)nb * zrs + 255) / 256)), dim3(256), 0, st, Z, T, nb,
-                     pz, Z32);
-  if (e == hipSuccess) e = launch_gemm_zrm_f32(H32, ldH, Z32, pz, zrs, C32, T, nb * pz, T, st);
-  hipLaunchKernelGGL(dbg_unpack_hz32_kernel, dim3((unsigned)(((int64_t)T * nb * pz + 255) / 256)), dim3(256), 0, st, C32,
-                     T, nb, pz, out);
-  std::vector<double> hdh(T);
-  if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = hipGetLastError();
-  hipFree(buf);
-  if (e != hipSuccess) return 1000 + (int)e;
-  if (hmax_out) *hmax_out = fact_hmax(hdh.data(), T);
-  return 0;
-}

@@ -46,6 +46,15 @@ hipError_t launch_gram_wk(const double *Ep, int64_t ld, int T, int N, int r, con
                           int nb, double *work, double *G, hipStream_t st);
 
 // ---- dfm_gemm.hip
+// Z, the B operand of launch_gemm_zrm / launch_gemm_zrm_f32, replicate-major
+// in 16-row chunks: replicate rep's element (s, c) at
+// rep zrs + (s >> 4) 16 pz + 16 c + (s & 15), zrs = round_up(T, 16) pz; the
+// chunk rows s >= T are zero (the factored solver's boot_prep_kernel writes
+// them each call).  The fp32 product's C has the same indexing.
+DFM_DEV int64_t zrm_stride(int T, int pz) { return (int64_t)((T + 15) & ~15) * pz; }
+DFM_DEV int64_t zrm_ix(int rep, int s, int c, int pz, int64_t zrs) {
+  return (int64_t)rep * zrs + (int64_t)(s >> 4) * (16 * pz) + 16 * c + (s & 15);
+}
 hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz, int64_t zrs, double *C,
                            int64_t ldc, int M, int Nc, int K, hipStream_t st, const int *col_done, const int *clist,
                            const int *ccount);
