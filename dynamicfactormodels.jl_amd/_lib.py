@@ -46,6 +46,22 @@ class dfm_em_info(C.Structure):
                 ("err", C.c_double), ("n_missing", C.c_int64)]
 
 
+class dfm_ss_params(C.Structure):
+    _fields_ = [("r", C.c_int32), ("p", C.c_int32), ("lambda_", c_double_p), ("sigma2", c_double_p),
+                ("A", c_double_p), ("Q", c_double_p), ("a0", c_double_p), ("P0", c_double_p)]
+
+
+class dfm_ss_spec(C.Structure):
+    _fields_ = [("horizon", C.c_int32), ("dev", C.c_int32)]
+
+
+class dfm_ss_fit_out(C.Structure):
+    _fields_ = [(n, c_double_p) for n in
+                ("mu", "sd", "lambda_", "sigma2", "A", "Q", "P0", "filtered", "smoothed", "smoothed_cov", "loglik",
+                 "x_smoothed", "x_completed", "forecast", "em_standardized", "em_completed", "em_factors",
+                 "eigvals")]
+
+
 # (name, restype, argtypes) — one row per symbol of include/dfm.h
 SIGNATURES = [
     ("dfm_ctx_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -128,6 +144,14 @@ SIGNATURES = [
                                    C.c_int64, C.c_int64, C.POINTER(dfm_em_spec), C.POINTER(C.c_void_p),
                                    C.POINTER(dfm_em_info)]),
     ("dfm_model_em_read", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("dfm_ss_stationary_cov", C.c_int, [c_double_p, c_double_p, C.c_int, C.c_int, c_double_p]),
+    ("dfm_ss_smooth", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                C.POINTER(dfm_ss_params), C.POINTER(dfm_ss_spec), c_double_p, c_double_p,
+                                c_double_p, c_double_p, c_int64_p]),
+    ("dfm_ss_estimate", C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                  c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("dfm_ss_fit", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
+                             C.c_int, C.c_int, C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out)]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

@@ -1084,6 +1084,189 @@ def DynamicFactorModel_em(y, w, x, number_of_factors: Optional[int] = None, crit
     return res
 
 
+# ------------------------------------------- state-space factor model (dfm_ss)
+@dataclass
+class KalmanResult:
+    """One ``kalman_smoother`` call.  A single (T, N) panel gives ``filtered``
+    (T, r) = f_t|t, ``smoothed`` (T + h, r) = f_t|T, ``smoothed_cov``
+    (T + h, r, r) = the factor block of P_t|T, ``loglik`` and ``n_observed``
+    scalars; a batch of M panels gives each with a leading axis M."""
+    filtered: np.ndarray
+    smoothed: np.ndarray
+    smoothed_cov: np.ndarray
+    loglik: Union[float, np.ndarray]
+    n_observed: Union[int, np.ndarray]
+
+
+@dataclass
+class StateSpaceResult:
+    """The two-step fit (``dfm_ss_fit``): the EM's record ``em``, the
+    parameters (``loadings`` N x r, ``sigma2`` N, ``A`` r x rp, ``Q`` r x r,
+    ``P0`` s x s), the ``filtered`` (T, r) and ``smoothed`` (T + h, r) factors
+    with ``smoothed_cov`` (T + h, r, r), ``loglik``, and the three panels:
+    ``x_smoothed`` (standardised units, missing := Lambda f_t|T),
+    ``x_completed`` (original units; observed entries untouched) and the
+    ``forecast`` rows (h, N)."""
+    em: EMResult
+    mean: np.ndarray
+    std: np.ndarray
+    loadings: np.ndarray
+    sigma2: np.ndarray
+    A: np.ndarray
+    Q: np.ndarray
+    P0: np.ndarray
+    filtered: np.ndarray
+    smoothed: np.ndarray
+    smoothed_cov: np.ndarray
+    loglik: float
+    x_smoothed: np.ndarray
+    x_completed: np.ndarray
+    forecast: np.ndarray
+    number_of_factors: int
+    lags: int
+
+
+def _ss_check(rc: int, what: str):
+    if rc != 0:
+        raise DFMError(rc, {-7: f"{what}: the state-space pass serves 1 <= r <= 16, 1 <= p <= 8, r p <= 32",
+                            -12: f"{what}: NaN in A or Q",
+                            6: f"{what}: the VAR is not stationary (the doubling iteration did not converge)"}
+                       .get(rc, f"{what}: bad arguments"))
+
+
+def stationary_covariance(A, Q) -> np.ndarray:
+    """Stationary covariance of the state of f_t = A_1 f_{t-1} + ... + A_p f_{t-p}
+    + u_t, u_t ~ N(0, Q): the solution of P = Tm P Tm' + Qs by the doubling
+    iteration (``dfm_ss_stationary_cov``; host arithmetic).  ``A`` is r x rp."""
+    A = _f64(A, 2)
+    Q = _f64(Q, 2)
+    r = A.shape[0]
+    if r < 1 or A.shape[1] % r or Q.shape != (r, r):
+        raise ValueError("A must be r x rp and Q r x r")
+    p = A.shape[1] // r
+    s = r * p
+    P0 = np.zeros((s, s))
+    Ac, Qc = _colmajor(A), _colmajor(Q)   # beyond the limits the library answers before it writes
+    _ss_check(_lib.load().dfm_ss_stationary_cov(Ac.ctypes.data_as(_lib.c_double_p),
+                                                Qc.ctypes.data_as(_lib.c_double_p), r, p, _lib.ptr(P0)),
+              "stationary_covariance")
+    return P0
+
+
+def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0,
+                    ctx: Optional[Context] = None) -> KalmanResult:
+    """Kalman filter and Rauch-Tung-Striebel smoother over the observed entries
+    (NaN = missing) of one panel or of M panels of one shape that share the
+    parameters (``dfm_ss_smooth``; the model is stated in ``include/dfm.h``).
+    ``x``: (T, N), (M, T, N), a list of (T, N) arrays, or a float64 GPU tensor
+    as ``monte_carlo`` takes.  ``loadings`` N x r, ``sigma2`` N, ``A`` r x rp,
+    ``Q`` r x r; ``a0`` defaults to zero and ``P0`` to the stationary
+    covariance.  ``horizon`` appends that many forecast rows."""
+    ctx = ctx or default_context()
+    single = (not _is_device_tensor(x) and not isinstance(x, (list, tuple)) and np.ndim(x) == 2) or \
+        (_is_device_tensor(x) and x.dim() == 2)
+    if single and _is_device_tensor(x):
+        if x.stride(0) != 1 or x.stride(1) < x.shape[0]:
+            raise ValueError("x must be a column-major float64 GPU tensor (stride (1, ldx))")
+        x = x.as_strided((1, x.shape[0], x.shape[1]), (x.stride(1) * x.shape[1], 1, x.stride(1)))
+    elif single:
+        x = np.asarray(x, dtype=np.float64)[None]
+    buf, M, T, N, ldx, stride, dev = _mc_layout(x)
+    Lc = _colmajor(_f64(loadings, 2))
+    r = Lc.shape[1]
+    A = _f64(A, 2)
+    if Lc.shape[0] != N or A.shape[0] != r or r < 1 or A.shape[1] % r:
+        raise ValueError("loadings must be N x r and A r x rp")
+    p = A.shape[1] // r
+    s = r * p
+    sg = np.ascontiguousarray(_f64(sigma2).ravel())
+    Ac, Qc = _colmajor(A), _colmajor(_f64(Q, 2))
+    a0c = None if a0 is None else np.ascontiguousarray(_f64(a0).ravel())
+    P0c = None if P0 is None else _colmajor(_f64(P0, 2))
+    if len(sg) != N or Qc.shape != (r, r) or (a0c is not None and len(a0c) != s) or \
+            (P0c is not None and P0c.shape != (s, s)):
+        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have rp entries and P0 be rp x rp")
+    cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
+    params = _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c))
+    h = int(horizon)
+    spec = _lib.dfm_ss_spec(h, int(dev))
+    filt = np.zeros((M, T, r))
+    sm = np.zeros((M, T + max(h, 0), r))
+    cov = np.zeros((M, T + max(h, 0), r, r))
+    ll = np.zeros(M)
+    nobs = np.zeros(M, dtype=np.int64)
+    xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
+    ctx.check(ctx.lib.dfm_ss_smooth(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), C.byref(spec), _lib.ptr(filt),
+                                    _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll), nobs.ctypes.data_as(_lib.c_int64_p)))
+    del buf
+    if single:
+        return KalmanResult(filt[0], sm[0], cov[0], float(ll[0]), int(nobs[0]))
+    return KalmanResult(filt, sm, cov, ll, nobs)
+
+
+def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context] = None):
+    """Steps 2-4 of the two-step fit (``dfm_ss_estimate``) from the
+    standardised panel ``zm`` (NaN = missing), the T x r ``factors`` and N x r
+    ``loadings``: the idiosyncratic variances, the VAR(``lags``) of the factors
+    by OLS and the stationary covariance.  Returns (sigma2, A, Q, P0)."""
+    ctx = ctx or default_context()
+    Zc = _colmajor(_f64(zm, 2))
+    Fc = _colmajor(_f64(factors, 2))
+    Lc = _colmajor(_f64(loadings, 2))
+    T, N = Zc.shape
+    r, p = Fc.shape[1], int(lags)
+    if Fc.shape[0] != T or Lc.shape != (N, r):
+        raise ValueError("factors must be T x r and loadings N x r")
+    s = max(r * p, 1)
+    sg = np.zeros(N)
+    A = np.zeros((r, s), order="F")
+    Q = np.zeros((r, r), order="F")
+    P0 = np.zeros((s, s), order="F")
+    cp = lambda a: a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
+    ctx.check(ctx.lib.dfm_ss_estimate(ctx.h, cp(Zc), T, N, T, cp(Fc), cp(Lc), r, p, _lib.ptr(sg), cp(A), cp(Q),
+                                      cp(P0)))
+    return sg, np.ascontiguousarray(A), np.ascontiguousarray(Q), np.ascontiguousarray(P0)
+
+
+def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion: str = "ICp2", lags: int = 1,
+                          horizon: int = 0, *, kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50,
+                          standardize: bool = True, ctx: Optional[Context] = None) -> StateSpaceResult:
+    """The two-step estimator of Doz, Giannone & Reichlin (2011) of a panel
+    with missing entries (``dfm_ss_fit``): ``em_factors``, a VAR(``lags``) on
+    its factors, then the Kalman smoother over the observed entries with
+    ``horizon`` forecast rows — ``em_factors`` -> ``ss_parameters`` ->
+    ``kalman_smoother`` in one call, bit for bit."""
+    ctx = ctx or default_context()
+    xp, T, N, ldx, dev, keep = _em_panel(x)
+    spec = _em_spec(T, N, number_of_factors, criterion, kmax, tol, max_iter, standardize, dev)
+    p, h = int(lags), int(horizon)
+    if h < 0:
+        raise ValueError("horizon must be >= 0")
+    cap = min(int(number_of_factors), 32) if number_of_factors is not None else 32
+    sc = max(cap * max(p, 1), 1)
+    col = lambda m, n: np.zeros((m, n), order="F")   # noqa: E731
+    Z, X2, xs, xc, fc = col(T, N), col(T, N), col(T, N), col(T, N), col(h, N)
+    mu, sd, sg, ev, ll = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(cap), np.zeros(1)
+    L, F, A, Q, P0 = np.zeros(N * cap), np.zeros(T * cap), np.zeros(cap * sc), np.zeros(cap * cap), np.zeros(sc * sc)
+    filt, sm, cov = np.zeros(T * cap), np.zeros((T + h) * cap), np.zeros((T + h) * cap * cap)
+    cp = lambda a: a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
+    out = _lib.dfm_ss_fit_out(cp(mu), cp(sd), cp(L), cp(sg), cp(A), cp(Q), cp(P0), cp(filt), cp(sm), cp(cov), cp(ll),
+                              cp(xs), cp(xc), cp(fc), cp(Z), cp(X2), cp(F), cp(ev))
+    info = _lib.dfm_em_info()
+    ctx.check(ctx.lib.dfm_ss_fit(ctx.h, xp, T, N, ldx, C.byref(spec), p, h, C.byref(info), C.byref(out)))
+    del keep
+    r = int(info.r)
+    s = r * p
+    cm = lambda v, m, n: np.ascontiguousarray(v[:m * n].reshape(n, m).T)   # noqa: E731  (column-major m x n)
+    Lr, Fr = cm(L, N, r), cm(F, T, r)
+    em = EMResult(np.ascontiguousarray(Z), np.ascontiguousarray(X2), mu, sd, Fr, Lr, ev[:r].copy(), r,
+                  int(info.iterations), float(info.err), bool(info.converged), int(info.n_missing))
+    return StateSpaceResult(em, mu, sd, Lr, sg, cm(A, r, s), cm(Q, r, r), cm(P0, s, s),
+                            filt[:T * r].reshape(T, r).copy(), sm[:(T + h) * r].reshape(T + h, r).copy(),
+                            cov[:(T + h) * r * r].reshape(T + h, r, r).copy(), float(ll[0]),
+                            np.ascontiguousarray(xs), np.ascontiguousarray(xc), np.ascontiguousarray(fc), r, p)
+
+
 # ------------------------------------------------------- targeted predictors
 def targeted_predictors(y, w, x, thresholding: str = "hard", mode: str = "joint",
                         *, return_tstats: bool = False, folds=None,

@@ -44,6 +44,52 @@ DFM_DEV void block_spd_inverse(const double *A, double *Ai, double *Lw, double *
   __syncthreads();
 }
 
+// Inverse of a general matrix by Gauss-Jordan elimination with partial
+// pivoting (the first largest |entry| of the column).  W: the augmented
+// [A | I] (n x 2n, LDS, row stride S >= 2n); on return its right half holds
+// A^-1 and *logdet = log|det A|.  colj (n), rowj (2n), logdet, piv: LDS.
+// *bad |= 2 on a zero or non-finite pivot (the elimination then goes on with
+// a unit pivot: the flag, not the result, reports it).
+DFM_DEV void block_gj_inverse(double *W, int n, int S, double *colj, double *rowj, double *logdet, int *piv,
+                              int *bad) {
+  const int tid = threadIdx.x, nt = blockDim.x, n2 = 2 * n;
+  if (tid == 0) *logdet = 0.0;
+  for (int j = 0; j < n; ++j) {
+    if (tid == 0) {
+      int p = j;
+      double best = fabs(W[j * S + j]);
+      for (int i = j + 1; i < n; ++i) {
+        const double v = fabs(W[i * S + j]);
+        if (v > best) { best = v; p = i; }
+      }
+      *piv = p;
+      if (!(best > 0.0) || isinf(best)) *bad |= 2;
+      else *logdet += log(best);
+    }
+    __syncthreads();
+    const int p = *piv;
+    if (p != j)
+      for (int c = tid; c < n2; c += nt) {
+        const double a = W[j * S + c];
+        W[j * S + c] = W[p * S + c];
+        W[p * S + c] = a;
+      }
+    __syncthreads();
+    double pv = W[j * S + j];
+    if (!(fabs(pv) > 0.0) || isinf(pv)) pv = 1.0;
+    for (int c = tid; c < n2 + n; c += nt) {
+      if (c < n2) rowj[c] = W[j * S + c] / pv;
+      else colj[c - n2] = W[(c - n2) * S + j];
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n2; e += nt) {
+      const int i = e / n2, c = e % n2;
+      W[i * S + c] = (i == j) ? rowj[c] : W[i * S + c] - colj[i] * rowj[c];
+    }
+    __syncthreads();
+  }
+}
+
 // block_spd_inverse on ONE wave (lanes, no barriers: every LDS write is
 // waited for before the lanes that read it issue their reads) — the same
 // operations in the same order, so several small inverses run side by side

@@ -1,0 +1,228 @@
+// dfm_ss_host.h — the host arithmetic of the state-space pass (dfm_ss.hip):
+// the limits, the companion form of a VAR(p), the stationary covariance by the
+// doubling iteration, the argument checks of the smoother's parameters and
+// steps 2-3 of the two-step fit (idiosyncratic variances, VAR(p) by OLS).
+// No HIP includes: a plain C++ compiler builds it alone (tests/c_harness).
+//
+// Layout: every matrix the caller passes is column-major (include/dfm.h);
+// the companion matrix, the state covariances and the r x r innovation
+// covariance used inside the library are row-major.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <vector>
+
+namespace dfm {
+
+constexpr int SS_RMAX = 16, SS_PMAX = 8, SS_SMAX = 32;
+
+// Return codes of the state-space entry points (beside the library's -2 / -7)
+constexpr int SS_E_LIMIT = -7;        // r, p or s = r p beyond the limits
+constexpr int SS_E_SIGMA = -10;       // a non-positive idiosyncratic variance
+constexpr int SS_E_VAR = -11;         // T - p <= r p, or a singular Xl'Xl
+constexpr int SS_E_NAN = -12;         // NaN in Lambda, sigma^2, A, Q, a0 or P0
+constexpr int SS_E_SINGULAR = 5;      // Q, a P_{t+1|t} or a G not invertible
+constexpr int SS_E_EXPLOSIVE = 6;     // the VAR is not stationary
+
+inline int ss_check_dims(int r, int p) {
+  if (r < 1 || p < 1) return -2;
+  if (r > SS_RMAX || p > SS_PMAX || r * p > SS_SMAX) return SS_E_LIMIT;
+  return 0;
+}
+
+// Companion matrix Tm (s x s row-major) of A = [A_1 ... A_p] (r x rp
+// column-major): A in the first r rows, the identity shift below.
+inline void ss_companion(const double *A, int r, int p, double *Tm) {
+  const int s = r * p;
+  for (int e = 0; e < s * s; ++e) Tm[e] = 0.0;
+  for (int i = 0; i < r; ++i)
+    for (int k = 0; k < s; ++k) Tm[i * s + k] = A[(size_t)k * r + i];
+  for (int i = r; i < s; ++i) Tm[i * s + (i - r)] = 1.0;
+}
+
+// One doubling step: P <- P + M P M', M <- M M (s x s row-major; W: 2 s^2 scratch).
+inline void ss_doubling_step(double *P, double *M, int s, double *W) {
+  double *MP = W, *MM = W + (size_t)s * s;
+  for (int i = 0; i < s; ++i)
+    for (int j = 0; j < s; ++j) {
+      double a = 0.0, b = 0.0;
+      for (int k = 0; k < s; ++k) {
+        a += M[i * s + k] * P[k * s + j];
+        b += M[i * s + k] * M[k * s + j];
+      }
+      MP[i * s + j] = a;
+      MM[i * s + j] = b;
+    }
+  for (int i = 0; i < s; ++i)
+    for (int j = 0; j < s; ++j) {
+      double a = 0.0;
+      for (int k = 0; k < s; ++k) a += MP[i * s + k] * M[j * s + k];
+      P[i * s + j] += a;
+    }
+  for (int e = 0; e < s * s; ++e) M[e] = MM[e];
+}
+
+// Solution of P = Tm P Tm' + Qs (Qs: Q in the top-left r x r block) by the
+// doubling iteration from P = Qs, M = Tm; stops when max|M| < 1e-40.
+// A, Q column-major; P0 s x s (symmetric).  SS_E_EXPLOSIVE after 60 doublings
+// or at the first non-finite entry.
+inline int ss_stationary_cov(const double *A, const double *Q, int r, int p, double *P0) {
+  const int rc = ss_check_dims(r, p);
+  if (rc) return rc;
+  if (!A || !Q || !P0) return -2;
+  const int s = r * p;
+  for (int e = 0; e < r * s; ++e)
+    if (isnan(A[e])) return SS_E_NAN;
+  for (int e = 0; e < r * r; ++e)
+    if (isnan(Q[e])) return SS_E_NAN;
+  std::vector<double> M((size_t)s * s), P((size_t)s * s, 0.0), W((size_t)2 * s * s);
+  ss_companion(A, r, p, M.data());
+  for (int i = 0; i < r; ++i)
+    for (int j = 0; j < r; ++j) P[i * s + j] = Q[(size_t)j * r + i];
+  for (int it = 0; it < 60; ++it) {
+    ss_doubling_step(P.data(), M.data(), s, W.data());
+    double big = 0.0;
+    for (int e = 0; e < s * s; ++e) {
+      if (!isfinite(M[e]) || !isfinite(P[e])) return SS_E_EXPLOSIVE;
+      big = fmax(big, fabs(M[e]));
+    }
+    if (big < 1e-40) {
+      for (int i = 0; i < s; ++i)
+        for (int j = 0; j < s; ++j) P0[i * s + j] = 0.5 * (P[i * s + j] + P[j * s + i]);
+      return 0;
+    }
+  }
+  return SS_E_EXPLOSIVE;
+}
+
+// Cholesky of the n x n row-major SPD matrix G in place (lower triangle);
+// false on a non-positive pivot.
+inline bool ss_cholesky(double *G, int n) {
+  for (int j = 0; j < n; ++j) {
+    double d = G[j * n + j];
+    for (int k = 0; k < j; ++k) d -= G[j * n + k] * G[j * n + k];
+    if (!(d > 0.0) || !isfinite(d)) return false;
+    d = sqrt(d);
+    G[j * n + j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double v = G[i * n + j];
+      for (int k = 0; k < j; ++k) v -= G[i * n + k] * G[j * n + k];
+      G[i * n + j] = v / d;
+    }
+  }
+  return true;
+}
+
+// The smoother's parameters: dims, NaN, non-positive variances.  *where: the
+// offending column of sigma^2 (SS_E_SIGMA).  a0, P0 may be null.
+inline int ss_check_params(int64_t N, int r, int p, const double *L, const double *sigma2, const double *A,
+                           const double *Q, const double *a0, const double *P0, int64_t *where) {
+  const int rc = ss_check_dims(r, p);
+  if (rc) return rc;
+  if (!L || !sigma2 || !A || !Q || N < 1) return -2;
+  const int s = r * p;
+  auto any_nan = [](const double *v, size_t n) {
+    for (size_t e = 0; e < n; ++e)
+      if (isnan(v[e])) return true;
+    return false;
+  };
+  if (any_nan(L, (size_t)N * r) || any_nan(sigma2, (size_t)N) || any_nan(A, (size_t)r * s) ||
+      any_nan(Q, (size_t)r * r) || (a0 && any_nan(a0, (size_t)s)) || (P0 && any_nan(P0, (size_t)s * s)))
+    return SS_E_NAN;
+  for (int64_t i = 0; i < N; ++i)
+    if (!(sigma2[i] > 0.0) || isinf(sigma2[i])) {
+      if (where) *where = i;
+      return SS_E_SIGMA;
+    }
+  return 0;
+}
+
+// Steps 2-4 of the two-step fit.  Zm: T x N column-major (ldz >= T), NaN =
+// missing; F: T x r column-major (ld T); L: N x r column-major (ld N).
+//   sigma2_i = sum_t m_ti (Z_ti - f_t' lambda_i)^2 / n_i
+//   VAR(p) by OLS without intercept: Y = F[p:], Xl = [F[p-1:T-1], ..., F[0:T-p]],
+//   A' = (Xl'Xl)^-1 Xl'Y, U = Y - Xl A', Q = U'U / (T - p)
+//   P0 = ss_stationary_cov(A, Q)
+// Outputs column-major: sigma2 (N), A (r x rp), Q (r x r), P0 (s x s); *where
+// names the column of a failed variance.
+inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                       int p, double *sigma2, double *A, double *Q, double *P0, int64_t *where) {
+  int rc = ss_check_dims(r, p);
+  if (rc) return rc;
+  if (!Zm || !F || !L || !sigma2 || !A || !Q || !P0 || T < 2 || N < 1 || ldz < T) return -2;
+  const int s = r * p;
+  for (size_t e = 0; e < (size_t)T * r; ++e)
+    if (isnan(F[e])) return SS_E_NAN;
+  for (size_t e = 0; e < (size_t)N * r; ++e)
+    if (isnan(L[e])) return SS_E_NAN;
+  for (int64_t i = 0; i < N; ++i) {
+    double ss = 0.0;
+    int64_t n = 0;
+    for (int64_t t = 0; t < T; ++t) {
+      const double z = Zm[(size_t)i * ldz + t];
+      if (isnan(z)) continue;
+      double c = 0.0;
+      for (int j = 0; j < r; ++j) c = fma(F[(size_t)j * T + t], L[(size_t)j * N + i], c);
+      ss += (z - c) * (z - c);
+      ++n;
+    }
+    const double v = n > 0 ? ss / (double)n : 0.0;
+    sigma2[i] = v;
+    if (!(v > 0.0) || isinf(v)) {
+      if (where) *where = i;
+      return SS_E_SIGMA;
+    }
+  }
+  const int64_t n = T - p;
+  if (n <= s) return SS_E_VAR;
+  // Xl[t][k r + j] = F[p - 1 - k + t][j]
+  auto xl = [&](int64_t t, int c) { return F[(size_t)(c % r) * T + (p - 1 - c / r + t)]; };
+  std::vector<double> G((size_t)s * s), B((size_t)s * r), U((size_t)n * r);
+  for (int a = 0; a < s; ++a)
+    for (int b = 0; b <= a; ++b) {
+      double v = 0.0;
+      for (int64_t t = 0; t < n; ++t) v += xl(t, a) * xl(t, b);
+      G[a * s + b] = G[b * s + a] = v;
+    }
+  for (int a = 0; a < s; ++a)
+    for (int j = 0; j < r; ++j) {
+      double v = 0.0;
+      for (int64_t t = 0; t < n; ++t) v += xl(t, a) * F[(size_t)j * T + p + t];
+      B[a * r + j] = v;
+    }
+  if (!ss_cholesky(G.data(), s)) return SS_E_VAR;
+  for (int j = 0; j < r; ++j) {   // G x = B[:, j] by the two triangular solves
+    for (int a = 0; a < s; ++a) {
+      double v = B[a * r + j];
+      for (int k = 0; k < a; ++k) v -= G[a * s + k] * B[k * r + j];
+      B[a * r + j] = v / G[a * s + a];
+    }
+    for (int a = s - 1; a >= 0; --a) {
+      double v = B[a * r + j];
+      for (int k = a + 1; k < s; ++k) v -= G[k * s + a] * B[k * r + j];
+      B[a * r + j] = v / G[a * s + a];
+    }
+  }
+  // B = A' (rp x r): A[i][c] = B[c][i], column-major r x rp
+  for (int c = 0; c < s; ++c)
+    for (int i = 0; i < r; ++i) A[(size_t)c * r + i] = B[c * r + i];
+  for (int64_t t = 0; t < n; ++t)
+    for (int j = 0; j < r; ++j) {
+      double v = F[(size_t)j * T + p + t];
+      for (int c = 0; c < s; ++c) v -= xl(t, c) * B[c * r + j];
+      U[(size_t)t * r + j] = v;
+    }
+  std::vector<double> Qc((size_t)r * r);
+  for (int i = 0; i < r; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double v = 0.0;
+      for (int64_t t = 0; t < n; ++t) v += U[(size_t)t * r + i] * U[(size_t)t * r + j];
+      v /= (double)n;
+      Q[(size_t)j * r + i] = Q[(size_t)i * r + j] = v;
+      Qc[i * r + j] = Qc[j * r + i] = v;
+    }
+  if (!ss_cholesky(Qc.data(), r)) return SS_E_SINGULAR;
+  return ss_stationary_cov(A, Q, r, p, P0);
+}
+
+}  // namespace dfm

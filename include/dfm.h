@@ -451,6 +451,104 @@ int dfm_model_fit_em(dfm_ctx *ctx, const double *y, const double *w, int q, int6
  * z-score's mu (N), sd (N) of a dfm_model_fit_em model; -1 for any other model. */
 int dfm_model_em_read(const dfm_model *m, double *X2, double *mu, double *sd);
 
+/* ------------------------------- state-space factor model (dfm_ss.hip)
+ * The factors as a VAR(p), smoothed over the observed entries of a panel
+ * (NaN = missing, m_ti = !isnan(x_ti)):
+ *   x_t = Lambda f_t + e_t,  e_t ~ N(0, diag(sigma^2)),  Lambda N x r
+ *   f_t = A_1 f_{t-1} + ... + A_p f_{t-p} + u_t,  u_t ~ N(0, Q)
+ *   state alpha_t = (f_t, ..., f_{t-p+1}), s = r p; companion matrix Tm: A =
+ *   [A_1 ... A_p] (r x rp) in its first r rows, the identity shift below;
+ *   Qs: Q in the top-left r x r block, zero elsewhere.
+ * Limits: 1 <= r <= 16, 1 <= p <= 8, s <= 32 (-7 beyond).
+ *
+ * Collapse (parallel over t, one read of the panel): for every row t
+ *   C_t = sum_i m_ti lambda_i lambda_i' / sigma^2_i      (r x r)
+ *   b_t = sum_i m_ti lambda_i x_ti / sigma^2_i           (r)
+ *   q_t = sum_i m_ti x_ti^2 / sigma^2_i,  n_t = sum_i m_ti,
+ *   l_t = sum_i m_ti log sigma^2_i.
+ * Recursion (sequential in t, one workgroup per panel), from a = a0, P = P0
+ * (the moments of alpha_1 before any data); Pff = P[:r,:r], Pf = P[:, :r],
+ * a_f = a[:r], G = I_r + C_t Pff.  For a row with n_t > 0:
+ *   K = Pf G^-1;  d = b_t - C_t a_f;  a <- a + K d
+ *   P <- P - K C_t Pf', then P <- (P + P') / 2
+ *   loglik -= 1/2 [ n_t log 2 pi + l_t + log det G + q_t - 2 b_t'a_f
+ *                   + a_f' C_t a_f - d' Pff G^-1 d ]   (a_f, Pff from before the update)
+ * a row with n_t = 0 leaves a and P as they are; then for every row
+ *   a <- Tm a;  P <- Tm P Tm' + Qs.
+ * Backwards (Rauch-Tung-Striebel):
+ *   J_t = P_t|t Tm' P_{t+1|t}^-1
+ *   a_t|T = a_t|t + J_t (a_{t+1|T} - a_{t+1|t})
+ *   P_t|T = P_t|t + J_t (P_{t+1|T} - P_{t+1|t}) J_t'.
+ * A forecast horizon h is h rows without an observed entry appended: outputs
+ * have T + h rows.  The batch is M panels of one shape sharing the parameters,
+ * each with its own NaN pattern (layout of dfm_mc); results are bit-identical
+ * run to run, and panel b of a batch is bit-identical to a call on panel b.
+ *
+ * Two-step fit (Doz, Giannone & Reichlin 2011), dfm_ss_fit:
+ *   1. dfm_em on the panel (spec passed through): Z, F, L, mu, sd
+ *   2. sigma^2_i = sum_t m_ti (Z_ti - f_t' lambda_i)^2 / n_i, n_i = column i's observed count
+ *   3. VAR(p) on F by OLS without intercept: Y = F[p:], Xl = [F[p-1:T-1], ...,
+ *      F[0:T-p]], A' = (Xl'Xl)^-1 Xl'Y, U = Y - Xl A', Q = U'U / (T - p)
+ *   4. a0 = 0; P0 solves P = Tm P Tm' + Qs by the doubling iteration
+ *      P <- P + M P M', M <- M M from P = Qs, M = Tm, until max|M| < 1e-40
+ *      (an error after 60 doublings or at the first non-finite entry)
+ *   5. the smoother with horizon h on Zm = m ? Z : NaN.
+ *
+ * Return codes beside -1 / -2: -7 r, p or s beyond the limits; -10 a
+ * non-positive sigma^2_i (the message names the column, 0-based); -11
+ * T - p <= r p, or a singular Xl'Xl; -12 NaN in Lambda, sigma^2, A, Q, a0 or
+ * P0; 5 Q, a P_{t+1|t} or a G not invertible; 6 the VAR is not stationary
+ * (the doubling iteration did not converge). */
+
+/* Stationary covariance of the state, step 4 above.  A: r x rp column-major,
+ * Q: r x r; P0_out: s x s (symmetric).  Pure host arithmetic; no context. */
+int dfm_ss_stationary_cov(const double *A, const double *Q, int r, int p, double *P0_out);
+
+typedef struct dfm_ss_params {
+  int32_t r, p;
+  const double *lambda;   /* N x r column-major (ld N) */
+  const double *sigma2;   /* N */
+  const double *A;        /* r x rp column-major */
+  const double *Q;        /* r x r */
+  const double *a0;       /* s; NULL: zero */
+  const double *P0;       /* s x s column-major; NULL: the stationary covariance */
+} dfm_ss_params;
+typedef struct dfm_ss_spec {
+  int32_t horizon;        /* h >= 0 forecast rows */
+  int32_t dev;            /* != 0: X is a device pointer on the context's device */
+} dfm_ss_spec;
+
+/* X: M panels, panel b column-major T x N at X + b*stride (ldx >= T, stride >=
+ * ldx*N), NaN = missing.  Outputs are host memory, row-major, any may be NULL:
+ * filtered M x T x r (f_t|t), smoothed M x (T+h) x r (f_t|T), smoothed_cov
+ * M x (T+h) x r x r (the factor block of P_t|T), loglik M, n_observed M. */
+int dfm_ss_smooth(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                  const dfm_ss_params *params, const dfm_ss_spec *spec, double *filtered, double *smoothed,
+                  double *smoothed_cov, double *loglik, int64_t *n_observed);
+
+/* Steps 2-4 of the two-step fit.  Zm: T x N column-major (ldx >= T), NaN =
+ * missing; F: T x r, L: N x r column-major.  Outputs column-major: sigma_out
+ * (N), A_out (r x rp), Q_out (r x r), P0_out (s x s).  Host arithmetic (the
+ * panel is read once, the rest is r p sized). */
+int dfm_ss_estimate(dfm_ctx *ctx, const double *Zm, int64_t T, int64_t N, int64_t ldx, const double *F,
+                    const double *L, int r, int p, double *sigma_out, double *A_out, double *Q_out, double *P0_out);
+
+/* What dfm_ss_fit returns: host memory, any may be NULL.  Panels are T x N
+ * column-major (ld T); size the r-dependent ones for em_spec->r, or for 32
+ * factors when r is selected (r = info->r on return). */
+typedef struct dfm_ss_fit_out {
+  double *mu, *sd;                 /* N: the EM's last z-score */
+  double *lambda;                  /* N x r column-major: the EM's loadings */
+  double *sigma2, *A, *Q, *P0;     /* as dfm_ss_estimate */
+  double *filtered, *smoothed, *smoothed_cov, *loglik;   /* as dfm_ss_smooth with M = 1 */
+  double *x_smoothed;              /* m ? Z : Lambda f_t|T */
+  double *x_completed;             /* m ? X : (Lambda f_t|T) sd + mu; observed entries bit-equal to X */
+  double *forecast;                /* h x N column-major (ld h): (Lambda f_{T+k|T}) sd + mu */
+  double *em_standardized, *em_completed, *em_factors, *eigvals;   /* dfm_em's Z, X2, F (T x r), eigvals (r) */
+} dfm_ss_fit_out;
+int dfm_ss_fit(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+               int horizon, dfm_em_info *info, const dfm_ss_fit_out *out);
+
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
  * JOINT: OLS of y on [w x], White HC0, |t_x| > crit_value (the reference's
