@@ -62,6 +62,21 @@ class dfm_ss_fit_out(C.Structure):
                  "eigvals")]
 
 
+class dfm_ss_em_spec(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("update_init", C.c_int32), ("horizon", C.c_int32), ("dev", C.c_int32),
+                ("tol", C.c_double)]
+
+
+class dfm_ss_em_info(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("loglik", C.c_double), ("crit", C.c_double)]
+
+
+class dfm_ss_em_out(C.Structure):
+    _fields_ = [(n, c_double_p) for n in ("lambda_", "sigma2", "A", "Q", "a0", "P0", "filtered", "smoothed",
+                                          "smoothed_cov")] + \
+               [("n_observed", c_int64_p), ("loglik_path", c_double_p)]
+
+
 # (name, restype, argtypes) — one row per symbol of include/dfm.h
 SIGNATURES = [
     ("dfm_ctx_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -152,6 +167,12 @@ SIGNATURES = [
                                   c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("dfm_ss_fit", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
                              C.c_int, C.c_int, C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out)]),
+    ("dfm_ss_em", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                            C.POINTER(dfm_ss_params), C.c_int64, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_em_out),
+                            C.POINTER(dfm_ss_em_info)]),
+    ("dfm_ss_fit_ml", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
+                                C.c_int, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_em_info),
+                                C.POINTER(dfm_ss_fit_out), c_double_p, c_double_p, C.POINTER(dfm_ss_em_info)]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

@@ -22,7 +22,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -1124,6 +1124,38 @@ class StateSpaceResult:
     forecast: np.ndarray
     number_of_factors: int
     lags: int
+    method: str = "two-step"
+    a0: Optional[np.ndarray] = None
+    loglik_path: Optional[np.ndarray] = None
+    ml_iterations: int = 0
+    ml_converged: bool = False
+    ml_criterion: float = float("nan")
+
+
+@dataclass
+class StateSpaceEMResult:
+    """One ``ss_em`` call: the parameters of the last E-step (``loadings``
+    N x r, ``sigma2`` N, ``A`` r x rp, ``Q`` r x r, ``a0`` rp, ``P0`` rp x rp),
+    that E-step's ``filtered``, ``smoothed``, ``smoothed_cov`` and
+    ``n_observed`` as ``kalman_smoother`` returns them, ``loglik``, the path
+    ``loglik_path`` (max_iter + 1, NaN beyond ``iterations``), ``iterations``,
+    ``converged`` and the last ``criterion``.  A batch of M panels gives each
+    with a leading axis M."""
+    loadings: np.ndarray
+    sigma2: np.ndarray
+    A: np.ndarray
+    Q: np.ndarray
+    a0: np.ndarray
+    P0: np.ndarray
+    filtered: np.ndarray
+    smoothed: np.ndarray
+    smoothed_cov: np.ndarray
+    loglik: Union[float, np.ndarray]
+    n_observed: Union[int, np.ndarray]
+    loglik_path: np.ndarray
+    iterations: Union[int, np.ndarray]
+    converged: Union[bool, np.ndarray]
+    criterion: Union[float, np.ndarray]
 
 
 def _ss_check(rc: int, what: str):
@@ -1153,6 +1185,20 @@ def stationary_covariance(A, Q) -> np.ndarray:
     return P0
 
 
+def _ss_panels(x):
+    """(single, ``_mc_layout`` of x): a single (T, N) panel, host or column-major
+    device tensor, becomes a batch of one."""
+    single = (not _is_device_tensor(x) and not isinstance(x, (list, tuple)) and np.ndim(x) == 2) or \
+        (_is_device_tensor(x) and x.dim() == 2)
+    if single and _is_device_tensor(x):
+        if x.stride(0) != 1 or x.stride(1) < x.shape[0]:
+            raise ValueError("x must be a column-major float64 GPU tensor (stride (1, ldx))")
+        x = x.as_strided((1, x.shape[0], x.shape[1]), (x.stride(1) * x.shape[1], 1, x.stride(1)))
+    elif single:
+        x = np.asarray(x, dtype=np.float64)[None]
+    return single, _mc_layout(x)
+
+
 def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0,
                     ctx: Optional[Context] = None) -> KalmanResult:
     """Kalman filter and Rauch-Tung-Striebel smoother over the observed entries
@@ -1163,15 +1209,7 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     ``Q`` r x r; ``a0`` defaults to zero and ``P0`` to the stationary
     covariance.  ``horizon`` appends that many forecast rows."""
     ctx = ctx or default_context()
-    single = (not _is_device_tensor(x) and not isinstance(x, (list, tuple)) and np.ndim(x) == 2) or \
-        (_is_device_tensor(x) and x.dim() == 2)
-    if single and _is_device_tensor(x):
-        if x.stride(0) != 1 or x.stride(1) < x.shape[0]:
-            raise ValueError("x must be a column-major float64 GPU tensor (stride (1, ldx))")
-        x = x.as_strided((1, x.shape[0], x.shape[1]), (x.stride(1) * x.shape[1], 1, x.stride(1)))
-    elif single:
-        x = np.asarray(x, dtype=np.float64)[None]
-    buf, M, T, N, ldx, stride, dev = _mc_layout(x)
+    single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
     Lc = _colmajor(_f64(loadings, 2))
     r = Lc.shape[1]
     A = _f64(A, 2)
@@ -1204,6 +1242,91 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     return KalmanResult(filt, sm, cov, ll, nobs)
 
 
+def _ss_start_axis(v, base_ndim, name):
+    """(array, has a leading panel axis) of one start parameter; a list of
+    per-panel arrays must be of one shape."""
+    if isinstance(v, (list, tuple)) and len(v) and np.ndim(v[0]) == base_ndim:
+        shapes = {np.shape(e) for e in v}
+        if len(shapes) != 1:
+            raise ValueError(f"{name}: the per-panel starts differ in shape {sorted(shapes)}")
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim not in (base_ndim, base_ndim + 1):
+        raise ValueError(f"{name} must have {base_ndim} dimensions, or a leading panel axis before them")
+    return a, a.ndim == base_ndim + 1
+
+
+def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max_iter: int = 100,
+          update_init: bool = True, horizon: int = 0, ctx: Optional[Context] = None) -> StateSpaceEMResult:
+    """Quasi-maximum likelihood of the state-space factor model by EM
+    (``dfm_ss_em``; the estimator is stated in ``include/dfm.h``), iterated on
+    the device over one panel or M panels of one shape, each with its own
+    parameters and its own stopping time.  ``x`` as ``kalman_smoother`` takes
+    it, in the units it is given.  The start: ``loadings`` N x r, ``sigma2`` N,
+    ``A`` r x rp, ``Q`` r x r, ``a0`` (zero) and ``P0`` (the stationary
+    covariance); a parameter with a leading axis M gives every panel its own,
+    one without it is shared.  Stops when the relative gain of the
+    log-likelihood falls below ``tol`` (0: never) or after ``max_iter``
+    M-steps; ``update_init`` re-estimates a0 and P0."""
+    ctx = ctx or default_context()
+    single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
+    given = [("loadings", loadings, 2), ("sigma2", sigma2, 1), ("A", A, 2), ("Q", Q, 2)]
+    if a0 is not None:
+        given.append(("a0", a0, 1))
+    if P0 is not None:
+        given.append(("P0", P0, 2))
+    arrs = {name: _ss_start_axis(v, nd, name) for name, v, nd in given}
+    per_panel = any(lead for _, lead in arrs.values())
+    n_start = M if per_panel else 1
+    for name, (a, lead) in arrs.items():
+        if lead and a.shape[0] != M:
+            raise ValueError(f"{name} has {a.shape[0]} per-panel starts for {M} panels")
+    get = lambda name, k: arrs[name][0][k] if arrs[name][1] else arrs[name][0]   # noqa: E731
+    r = arrs["loadings"][0].shape[-1]
+    Ash = arrs["A"][0].shape[-2:]
+    if r < 1 or Ash[0] != r or Ash[1] % r or arrs["loadings"][0].shape[-2] != N:
+        raise ValueError("loadings must be N x r and A r x rp")
+    p = Ash[1] // r
+    s = r * p
+    if arrs["sigma2"][0].shape[-1] != N or arrs["Q"][0].shape[-2:] != (r, r) or \
+            ("a0" in arrs and arrs["a0"][0].shape[-1] != s) or ("P0" in arrs and arrs["P0"][0].shape[-2:] != (s, s)):
+        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have rp entries and P0 be rp x rp")
+    cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
+    keep, starts = [], (_lib.dfm_ss_params * max(n_start, 1))()
+    for k in range(n_start):
+        Lc, Ac, Qc = _colmajor(get("loadings", k)), _colmajor(get("A", k)), _colmajor(get("Q", k))
+        sg = np.ascontiguousarray(get("sigma2", k).ravel())
+        a0c = np.ascontiguousarray(get("a0", k).ravel()) if "a0" in arrs else None
+        P0c = _colmajor(get("P0", k)) if "P0" in arrs else None
+        keep.append((Lc, Ac, Qc, sg, a0c, P0c))
+        starts[k] = _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c))
+    h, mi = int(horizon), int(max_iter)
+    if h < 0:
+        raise ValueError("horizon must be >= 0")
+    if mi < 0:
+        mi = 100
+    spec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, int(dev), float(tol))
+    Lo, so, Ao, Qo = np.zeros((M, r, N)), np.zeros((M, N)), np.zeros((M, s, r)), np.zeros((M, r, r))
+    a0o, P0o = np.zeros((M, s)), np.zeros((M, s, s))
+    filt, sm, cov = np.zeros((M, T, r)), np.zeros((M, T + h, r)), np.zeros((M, T + h, r, r))
+    nobs = np.zeros(M, dtype=np.int64)
+    path = np.full((M, mi + 1), np.nan)
+    out = _lib.dfm_ss_em_out(cp(Lo), cp(so), cp(Ao), cp(Qo), cp(a0o), cp(P0o), cp(filt), cp(sm), cp(cov),
+                             nobs.ctypes.data_as(_lib.c_int64_p), cp(path))
+    info = (_lib.dfm_ss_em_info * max(M, 1))()
+    xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
+    ctx.check(ctx.lib.dfm_ss_em(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(spec), C.byref(out), info))
+    del buf, keep
+    tr = lambda a: np.ascontiguousarray(np.swapaxes(a, 1, 2))   # noqa: E731  (column-major per panel)
+    its = np.array([info[k].iterations for k in range(M)], dtype=np.int64)
+    conv = np.array([bool(info[k].converged) for k in range(M)])
+    ll = np.array([info[k].loglik for k in range(M)])
+    crit = np.array([info[k].crit for k in range(M)])
+    res = StateSpaceEMResult(tr(Lo), so, tr(Ao), tr(Qo), a0o, tr(P0o), filt, sm, cov, ll, nobs, path, its, conv, crit)
+    if single:
+        return StateSpaceEMResult(*(getattr(res, f.name)[0] for f in fields(res)))
+    return res
+
+
 def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context] = None):
     """Steps 2-4 of the two-step fit (``dfm_ss_estimate``) from the
     standardised panel ``zm`` (NaN = missing), the T x r ``factors`` and N x r
@@ -1230,12 +1353,20 @@ def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context
 
 def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion: str = "ICp2", lags: int = 1,
                           horizon: int = 0, *, kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50,
-                          standardize: bool = True, ctx: Optional[Context] = None) -> StateSpaceResult:
+                          standardize: bool = True, method: str = "two-step", ml_tol: float = 1e-4,
+                          ml_max_iter: int = 100, update_init: bool = True,
+                          ctx: Optional[Context] = None) -> StateSpaceResult:
     """The two-step estimator of Doz, Giannone & Reichlin (2011) of a panel
     with missing entries (``dfm_ss_fit``): ``em_factors``, a VAR(``lags``) on
     its factors, then the Kalman smoother over the observed entries with
     ``horizon`` forecast rows — ``em_factors`` -> ``ss_parameters`` ->
-    ``kalman_smoother`` in one call, bit for bit."""
+    ``kalman_smoother`` in one call, bit for bit.  ``method="ml"`` iterates
+    that fit to the quasi-maximum likelihood (``dfm_ss_fit_ml``: ``ss_em`` on
+    the standardised panel from the two-step parameters, ``ml_tol``,
+    ``ml_max_iter``, ``update_init``); the parameters, factors and panels
+    returned are then the ML ones, ``mean`` and ``std`` stay the static EM's."""
+    if method not in ("two-step", "ml"):
+        raise ValueError('method must be "two-step" or "ml"')
     ctx = ctx or default_context()
     xp, T, N, ldx, dev, keep = _em_panel(x)
     spec = _em_spec(T, N, number_of_factors, criterion, kmax, tol, max_iter, standardize, dev)
@@ -1253,7 +1384,17 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     out = _lib.dfm_ss_fit_out(cp(mu), cp(sd), cp(L), cp(sg), cp(A), cp(Q), cp(P0), cp(filt), cp(sm), cp(cov), cp(ll),
                               cp(xs), cp(xc), cp(fc), cp(Z), cp(X2), cp(F), cp(ev))
     info = _lib.dfm_em_info()
-    ctx.check(ctx.lib.dfm_ss_fit(ctx.h, xp, T, N, ldx, C.byref(spec), p, h, C.byref(info), C.byref(out)))
+    ml = {}
+    if method == "ml":
+        mi = int(ml_max_iter) if int(ml_max_iter) >= 0 else 100
+        a0, path, minfo = np.zeros(sc), np.full(mi + 1, np.nan), _lib.dfm_ss_em_info()
+        mspec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, 0, float(ml_tol))
+        ctx.check(ctx.lib.dfm_ss_fit_ml(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(info),
+                                        C.byref(out), cp(a0), cp(path), C.byref(minfo)))
+        ml = dict(method="ml", a0=a0[:int(info.r) * p].copy(), loglik_path=path, ml_iterations=int(minfo.iterations),
+                  ml_converged=bool(minfo.converged), ml_criterion=float(minfo.crit))
+    else:
+        ctx.check(ctx.lib.dfm_ss_fit(ctx.h, xp, T, N, ldx, C.byref(spec), p, h, C.byref(info), C.byref(out)))
     del keep
     r = int(info.r)
     s = r * p
@@ -1264,7 +1405,7 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     return StateSpaceResult(em, mu, sd, Lr, sg, cm(A, r, s), cm(Q, r, r), cm(P0, s, s),
                             filt[:T * r].reshape(T, r).copy(), sm[:(T + h) * r].reshape(T + h, r).copy(),
                             cov[:(T + h) * r * r].reshape(T + h, r, r).copy(), float(ll[0]),
-                            np.ascontiguousarray(xs), np.ascontiguousarray(xc), np.ascontiguousarray(fc), r, p)
+                            np.ascontiguousarray(xs), np.ascontiguousarray(xc), np.ascontiguousarray(fc), r, p, **ml)
 
 
 # ------------------------------------------------------- targeted predictors

@@ -1,7 +1,8 @@
 // dfm_ss_host.h — the host arithmetic of the state-space pass (dfm_ss.hip):
 // the limits, the companion form of a VAR(p), the stationary covariance by the
 // doubling iteration, the argument checks of the smoother's parameters and
-// steps 2-3 of the two-step fit (idiosyncratic variances, VAR(p) by OLS).
+// steps 2-3 of the two-step fit (idiosyncratic variances, VAR(p) by OLS), and
+// of the quasi-ML EM the spec's defaults, the stopping rule and the checks.
 // No HIP includes: a plain C++ compiler builds it alone (tests/c_harness).
 //
 // Layout: every matrix the caller passes is column-major (include/dfm.h);
@@ -223,6 +224,68 @@ inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
     }
   if (!ss_cholesky(Qc.data(), r)) return SS_E_SINGULAR;
   return ss_stationary_cov(A, Q, r, p, P0);
+}
+
+// ------------------------------------------------ the quasi-ML EM (dfm_ss_em)
+constexpr int SS_EM_MAX_ITER = 100, SS_EM_ITER_CAP = 1 << 20;
+constexpr double SS_EM_TOL = 1e-4;
+
+// The spec's defaults: max_iter < 0 -> 100, tol < 0 -> 1e-4.  -2 for a NaN
+// tol, a negative horizon or an iteration count beyond the cap.
+inline int ss_em_defaults(int max_iter_in, double tol_in, int horizon, int *max_iter, double *tol) {
+  if (isnan(tol_in) || horizon < 0 || horizon > (1 << 20) || max_iter_in > SS_EM_ITER_CAP) return -2;
+  *max_iter = max_iter_in < 0 ? SS_EM_MAX_ITER : max_iter_in;
+  *tol = tol_in < 0.0 ? SS_EM_TOL : tol_in;
+  return 0;
+}
+
+// c_j = (ll_j - ll_{j-1}) / ((|ll_j| + |ll_{j-1}|) / 2); 0 when both are zero.
+inline double ss_em_criterion(double ll, double ll_prev) {
+  const double den = 0.5 * (fabs(ll) + fabs(ll_prev));
+  return den > 0.0 ? (ll - ll_prev) / den : 0.0;
+}
+
+// Banbura-Modugno's rule: converged when tol > 0 and c_j < tol (tol = 0 never stops).
+inline bool ss_em_converged(double c, double tol) { return tol > 0.0 && c < tol; }
+
+// The batch's layout and the starts' count; T < 2 is refused (the transition
+// sums need two rows).
+inline int ss_em_check_args(bool have_x, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                            bool have_starts, int64_t n_start) {
+  if (M < 0 || !have_starts || (n_start != 1 && n_start != M)) return -2;
+  if (M == 0) return 0;
+  if (!have_x || T < 2 || N < 1 || ldx < T || stride < ldx * N) return -2;
+  if (T > (1 << 24) || N > (1 << 24)) return -2;
+  return 0;
+}
+
+// One start: ss_check_params, then Q positive definite (SS_E_SINGULAR).
+inline int ss_em_check_start(int64_t N, int r, int p, const double *L, const double *sigma2, const double *A,
+                             const double *Q, const double *a0, const double *P0, int64_t *where) {
+  const int rc = ss_check_params(N, r, p, L, sigma2, A, Q, a0, P0, where);
+  if (rc) return rc;
+  std::vector<double> Qc((size_t)r * r);
+  for (int i = 0; i < r; ++i)
+    for (int j = 0; j < r; ++j) Qc[i * r + j] = 0.5 * (Q[(size_t)j * r + i] + Q[(size_t)i * r + j]);
+  return ss_cholesky(Qc.data(), r) ? 0 : SS_E_SINGULAR;
+}
+
+// First column without an observed entry of a host batch (layout of dfm_mc):
+// true, with its panel and column, when there is one.
+inline bool ss_em_empty_column(const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                               int64_t *panel, int64_t *col) {
+  for (int64_t b = 0; b < M; ++b)
+    for (int64_t i = 0; i < N; ++i) {
+      const double *x = X + b * stride + i * ldx;
+      int64_t t = 0;
+      while (t < T && isnan(x[t])) ++t;
+      if (t == T) {
+        *panel = b;
+        *col = i;
+        return true;
+      }
+    }
+  return false;
 }
 
 }  // namespace dfm

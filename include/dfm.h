@@ -549,6 +549,86 @@ typedef struct dfm_ss_fit_out {
 int dfm_ss_fit(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                int horizon, dfm_em_info *info, const dfm_ss_fit_out *out);
 
+/* Quasi-maximum likelihood by EM (Doz, Giannone & Reichlin 2012; Banbura &
+ * Modugno 2014 for arbitrary missing patterns), dfm_ss_em: M panels of one
+ * shape, each with its own parameters and its own stopping time; the whole
+ * iteration stays on the device.  The panel is in the units it is given.
+ *
+ * E-step at theta = (Lambda, sigma^2, A, Q, a0, P0): the collapse, filter and
+ * smoother above give loglik(theta), a_t|T, P_t|T and, for t = 2..T,
+ *   Cov(f_t, alpha_{t-1} | T) = the first r rows of P_t|T J_{t-1}'.
+ * With E_t = f_t|T f_t|T' + Pff_t|T, a_t = a_t|T, f_t = f_t|T:
+ *   S11 = sum_{t=2..T} E_t                                         (r x r)
+ *   S10 = sum_{t=2..T} [ f_t a_{t-1}' + Cov(f_t, alpha_{t-1}|T) ]  (r x s)
+ *   S00 = sum_{t=1..T-1} [ a_t a_t' + P_t|T ]                      (s x s)
+ *   per series i: S_i = sum_t m_ti E_t, g_i = sum_t m_ti x_ti f_t,
+ *   q_i = sum_t m_ti x_ti^2, n_i = sum_t m_ti.
+ * Forecast rows enter no sum; a row with n_t = 0 inside the sample enters the
+ * transition sums like any other.
+ * M-step (the latent variables are the states; missing entries are not data):
+ *   lambda_i = S_i^-1 g_i;  sigma^2_i = (q_i - lambda_i' g_i) / n_i
+ *   A = S10 S00^-1;  Q = (S11 - A S10') / (T - 1), then (Q + Q') / 2
+ *   update_init: a0 <- a_1|T, P0 <- P_1|T; otherwise a0, P0 stay the start's.
+ * Loop from the start theta_0, for j = 0, 1, ...:
+ *   1. E-step at theta_j: ll_j
+ *   2. j >= 1: c_j = (ll_j - ll_{j-1}) / ((|ll_j| + |ll_{j-1}|) / 2) (0 when
+ *      both are zero); converged if tol > 0 and c_j < tol
+ *   3. stop if j = max_iter
+ *   4. M-step: theta_{j+1}.
+ * The call returns theta_j of the last E-step with that E-step's outputs, the
+ * path ll_0..ll_j (NaN beyond) and iterations = j.  tol = 0 runs exactly
+ * max_iter M-steps; max_iter = 0 is one E-step.  A panel that has stopped is
+ * frozen: its kernels exit at once, its buffers are not touched again.  A
+ * panel's result does not depend on its neighbours: panel b of a batch is
+ * bit-identical to a call on panel b alone with its start.
+ *
+ * Return codes: -2 bad arguments, T < 2, or a column without an observed
+ * entry; -7 the limits; -12 NaN in a start; 5 a start's Q not positive
+ * definite, or an S_i, S00, P_{t+1|t} or G not invertible in a pass; 6 a NULL
+ * P0 with a non-stationary start; -10 a non-positive sigma^2_i in a start or
+ * after an M-step.  A column without an observed entry is found before the
+ * first pass, on the host for a host batch and by one small kernel for a
+ * device batch.  The messages of a pass name the panel, the column (-10) and
+ * the iteration j: "the E-step of iteration j" is the pass at theta_j, "the
+ * M-step giving iteration j" the one that produced theta_j. */
+typedef struct dfm_ss_em_spec {
+  int32_t max_iter;       /* M-steps at the most; < 0: 100 */
+  int32_t update_init;    /* != 0: a0, P0 are re-estimated */
+  int32_t horizon;        /* h >= 0 forecast rows of the outputs */
+  int32_t dev;            /* != 0: X is a device pointer on the context's device */
+  double tol;             /* < 0: 1e-4; 0: never stop early */
+} dfm_ss_em_spec;
+typedef struct dfm_ss_em_info {
+  int32_t iterations;     /* j of the last E-step */
+  int32_t converged;
+  double loglik;          /* ll_j */
+  double crit;            /* the last c_j (NaN when j = 0) */
+} dfm_ss_em_info;
+/* Host memory, any may be NULL; every field has a leading axis M.  The
+ * parameters in the layouts of dfm_ss_params; the smoother's outputs as
+ * dfm_ss_smooth; loglik_path M x (max_iter + 1) with the default resolved. */
+typedef struct dfm_ss_em_out {
+  double *lambda, *sigma2, *A, *Q, *a0, *P0;
+  double *filtered, *smoothed, *smoothed_cov;
+  int64_t *n_observed;
+  double *loglik_path;
+} dfm_ss_em_out;
+/* X as dfm_ss_smooth.  starts: n_start = 1 (shared by all panels) or M
+ * dfm_ss_params of one (r, p).  info: M entries, or NULL. */
+int dfm_ss_em(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+              const dfm_ss_params *starts, int64_t n_start, const dfm_ss_em_spec *spec, const dfm_ss_em_out *out,
+              dfm_ss_em_info *info);
+
+/* dfm_ss_fit, then dfm_ss_em (M = 1) on its Zm from its parameters (a0 = 0,
+ * P0 the stationary covariance of the two-step VAR).  `out` is filled as by
+ * dfm_ss_fit, from the ML parameters and their smoothed factors; mu and sd
+ * stay the static EM's.  ml_spec->horizon is the forecast horizon; ml_spec->dev
+ * is ignored (em_spec->dev says where X lives).  a0_out (s), loglik_path
+ * (max_iter + 1) and ml_info may be NULL. */
+int dfm_ss_fit_ml(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+                  const dfm_ss_em_spec *ml_spec, dfm_em_info *info, const dfm_ss_fit_out *out, double *a0_out,
+                  double *loglik_path, dfm_ss_em_info *ml_info);
+
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
  * JOINT: OLS of y on [w x], White HC0, |t_x| > crit_value (the reference's
