@@ -55,6 +55,10 @@ class dfm_ss_spec(C.Structure):
     _fields_ = [("horizon", C.c_int32), ("dev", C.c_int32)]
 
 
+class dfm_ss_mf(C.Structure):
+    _fields_ = [("n_w", C.c_int32), ("w", c_double_p), ("low", c_uint8_p)]
+
+
 class dfm_ss_fit_out(C.Structure):
     _fields_ = [(n, c_double_p) for n in
                 ("mu", "sd", "lambda_", "sigma2", "A", "Q", "P0", "filtered", "smoothed", "smoothed_cov", "loglik",
@@ -74,7 +78,7 @@ class dfm_ss_em_info(C.Structure):
 class dfm_ss_em_out(C.Structure):
     _fields_ = [(n, c_double_p) for n in ("lambda_", "sigma2", "A", "Q", "a0", "P0", "filtered", "smoothed",
                                           "smoothed_cov")] + \
-               [("n_observed", c_int64_p), ("loglik_path", c_double_p)]
+               [("n_observed", c_int64_p), ("loglik_path", c_double_p), ("smoothed_agg", c_double_p)]
 
 
 # (name, restype, argtypes) — one row per symbol of include/dfm.h
@@ -163,6 +167,9 @@ SIGNATURES = [
     ("dfm_ss_smooth", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                 C.POINTER(dfm_ss_params), C.POINTER(dfm_ss_spec), c_double_p, c_double_p,
                                 c_double_p, c_double_p, c_int64_p]),
+    ("dfm_ss_smooth_mf", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                   C.POINTER(dfm_ss_params), C.POINTER(dfm_ss_mf), C.POINTER(dfm_ss_spec),
+                                   c_double_p, c_double_p, c_double_p, c_double_p, c_int64_p, c_double_p]),
     ("dfm_ss_estimate", C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int64, c_double_p,
                                   c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("dfm_ss_fit", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
@@ -170,9 +177,16 @@ SIGNATURES = [
     ("dfm_ss_em", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                             C.POINTER(dfm_ss_params), C.c_int64, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_em_out),
                             C.POINTER(dfm_ss_em_info)]),
+    ("dfm_ss_em_mf", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                               C.POINTER(dfm_ss_params), C.c_int64, C.POINTER(dfm_ss_mf), C.POINTER(dfm_ss_em_spec),
+                               C.POINTER(dfm_ss_em_out), C.POINTER(dfm_ss_em_info)]),
     ("dfm_ss_fit_ml", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
                                 C.c_int, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_em_info),
                                 C.POINTER(dfm_ss_fit_out), c_double_p, c_double_p, C.POINTER(dfm_ss_em_info)]),
+    ("dfm_ss_fit_mf", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
+                                C.c_int, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_mf), C.c_int,
+                                C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out), c_double_p, c_double_p,
+                                C.POINTER(dfm_ss_em_info), c_double_p]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

@@ -1090,12 +1090,15 @@ class KalmanResult:
     """One ``kalman_smoother`` call.  A single (T, N) panel gives ``filtered``
     (T, r) = f_t|t, ``smoothed`` (T + h, r) = f_t|T, ``smoothed_cov``
     (T + h, r, r) = the factor block of P_t|T, ``loglik`` and ``n_observed``
-    scalars; a batch of M panels gives each with a leading axis M."""
+    scalars; a batch of M panels gives each with a leading axis M.  With
+    low-frequency series, ``smoothed_agg`` (T + h, r) is the smoothed
+    aggregate sum_k w_k f_{t-k}|T they load on (None otherwise)."""
     filtered: np.ndarray
     smoothed: np.ndarray
     smoothed_cov: np.ndarray
     loglik: Union[float, np.ndarray]
     n_observed: Union[int, np.ndarray]
+    smoothed_agg: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -1130,6 +1133,7 @@ class StateSpaceResult:
     ml_iterations: int = 0
     ml_converged: bool = False
     ml_criterion: float = float("nan")
+    smoothed_agg: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -1140,7 +1144,9 @@ class StateSpaceEMResult:
     ``n_observed`` as ``kalman_smoother`` returns them, ``loglik``, the path
     ``loglik_path`` (max_iter + 1, NaN beyond ``iterations``), ``iterations``,
     ``converged`` and the last ``criterion``.  A batch of M panels gives each
-    with a leading axis M."""
+    with a leading axis M.  With low-frequency series ``a0`` and ``P0`` are
+    those of the padded state and ``smoothed_agg`` (T + h, r) is the smoothed
+    aggregate they load on (None otherwise)."""
     loadings: np.ndarray
     sigma2: np.ndarray
     A: np.ndarray
@@ -1156,6 +1162,7 @@ class StateSpaceEMResult:
     iterations: Union[int, np.ndarray]
     converged: Union[bool, np.ndarray]
     criterion: Union[float, np.ndarray]
+    smoothed_agg: Optional[np.ndarray] = None
 
 
 def _ss_check(rc: int, what: str):
@@ -1199,15 +1206,46 @@ def _ss_panels(x):
     return single, _mc_layout(x)
 
 
-def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0,
-                    ctx: Optional[Context] = None) -> KalmanResult:
+# Aggregation weights of a quarterly series among monthly ones, observed in the
+# last month of its quarter: a flow in monthly growth rates (Mariano & Murasawa
+# 2003) and a quarterly mean.
+AGG_FLOW = (1.0, 2.0, 3.0, 2.0, 1.0)
+AGG_MEAN = (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0)
+
+
+def _ss_mixed(low_freq, agg_weights, N):
+    """The checked (mask, weights) of a mixed-frequency call; None when
+    ``low_freq`` is None (the plain model)."""
+    if low_freq is None:
+        if agg_weights is not None:
+            raise ValueError("agg_weights needs low_freq, the mask of the series it applies to")
+        return None
+    low = np.ascontiguousarray(np.asarray(low_freq).ravel().astype(bool).astype(np.uint8))
+    if len(low) != N:
+        raise DFMError(-2, f"low_freq must have one entry per series ({N}), not {len(low)}")
+    if agg_weights is None:
+        raise ValueError("low_freq needs agg_weights (AGG_FLOW and AGG_MEAN are the usual ones)")
+    w = np.ascontiguousarray(_f64(agg_weights).ravel())
+    return low, w
+
+
+def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0, low_freq=None,
+                    agg_weights=None, ctx: Optional[Context] = None) -> KalmanResult:
     """Kalman filter and Rauch-Tung-Striebel smoother over the observed entries
     (NaN = missing) of one panel or of M panels of one shape that share the
     parameters (``dfm_ss_smooth``; the model is stated in ``include/dfm.h``).
     ``x``: (T, N), (M, T, N), a list of (T, N) arrays, or a float64 GPU tensor
     as ``monte_carlo`` takes.  ``loadings`` N x r, ``sigma2`` N, ``A`` r x rp,
     ``Q`` r x r; ``a0`` defaults to zero and ``P0`` to the stationary
-    covariance.  ``horizon`` appends that many forecast rows."""
+    covariance.  ``horizon`` appends that many forecast rows.
+
+    Mixed frequency (``dfm_ss_smooth_mf``): ``low_freq``, a boolean mask of
+    length N, marks the series that load on sum_k w_k f_{t-k} with w =
+    ``agg_weights`` (a quarterly series among monthly ones has NaN in two
+    months of three).  The state then keeps max(p, len(w)) lags: ``a0`` and
+    ``P0`` are of that size, and the result carries ``smoothed_agg``.  A mask
+    without a marked series is the plain call, bit for bit."""
+    mixed = _ss_mixed(low_freq, agg_weights, np.shape(loadings)[0])   # before anything touches the device
     ctx = ctx or default_context()
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
     Lc = _colmajor(_f64(loadings, 2))
@@ -1216,14 +1254,16 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     if Lc.shape[0] != N or A.shape[0] != r or r < 1 or A.shape[1] % r:
         raise ValueError("loadings must be N x r and A r x rp")
     p = A.shape[1] // r
-    s = r * p
+    any_low = mixed is not None and bool(mixed[0].any())
+    s = r * (max(p, len(mixed[1])) if any_low else p)
     sg = np.ascontiguousarray(_f64(sigma2).ravel())
     Ac, Qc = _colmajor(A), _colmajor(_f64(Q, 2))
     a0c = None if a0 is None else np.ascontiguousarray(_f64(a0).ravel())
     P0c = None if P0 is None else _colmajor(_f64(P0, 2))
     if len(sg) != N or Qc.shape != (r, r) or (a0c is not None and len(a0c) != s) or \
             (P0c is not None and P0c.shape != (s, s)):
-        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have rp entries and P0 be rp x rp")
+        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have s entries and P0 be s x s "
+                         "(s = r p, or r max(p, len(agg_weights)) with low-frequency series)")
     cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
     params = _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c))
     h = int(horizon)
@@ -1234,12 +1274,22 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     ll = np.zeros(M)
     nobs = np.zeros(M, dtype=np.int64)
     xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
-    ctx.check(ctx.lib.dfm_ss_smooth(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), C.byref(spec), _lib.ptr(filt),
-                                    _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll), nobs.ctypes.data_as(_lib.c_int64_p)))
+    agg = None
+    if mixed is None:
+        ctx.check(ctx.lib.dfm_ss_smooth(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), C.byref(spec),
+                                        _lib.ptr(filt), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll),
+                                        nobs.ctypes.data_as(_lib.c_int64_p)))
+    else:
+        low, w = mixed
+        agg = np.zeros((M, T + max(h, 0), r)) if any_low else None
+        mf = _lib.dfm_ss_mf(len(w), cp(w), low.ctypes.data_as(_lib.c_uint8_p))
+        ctx.check(ctx.lib.dfm_ss_smooth_mf(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), C.byref(mf),
+                                           C.byref(spec), _lib.ptr(filt), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll),
+                                           nobs.ctypes.data_as(_lib.c_int64_p), _lib.ptr(agg)))
     del buf
     if single:
-        return KalmanResult(filt[0], sm[0], cov[0], float(ll[0]), int(nobs[0]))
-    return KalmanResult(filt, sm, cov, ll, nobs)
+        return KalmanResult(filt[0], sm[0], cov[0], float(ll[0]), int(nobs[0]), None if agg is None else agg[0])
+    return KalmanResult(filt, sm, cov, ll, nobs, agg)
 
 
 def _ss_start_axis(v, base_ndim, name):
@@ -1256,7 +1306,8 @@ def _ss_start_axis(v, base_ndim, name):
 
 
 def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max_iter: int = 100,
-          update_init: bool = True, horizon: int = 0, ctx: Optional[Context] = None) -> StateSpaceEMResult:
+          update_init: bool = True, horizon: int = 0, low_freq=None, agg_weights=None,
+          ctx: Optional[Context] = None) -> StateSpaceEMResult:
     """Quasi-maximum likelihood of the state-space factor model by EM
     (``dfm_ss_em``; the estimator is stated in ``include/dfm.h``), iterated on
     the device over one panel or M panels of one shape, each with its own
@@ -1266,7 +1317,13 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     covariance); a parameter with a leading axis M gives every panel its own,
     one without it is shared.  Stops when the relative gain of the
     log-likelihood falls below ``tol`` (0: never) or after ``max_iter``
-    M-steps; ``update_init`` re-estimates a0 and P0."""
+    M-steps; ``update_init`` re-estimates a0 and P0.
+
+    Mixed frequency (``dfm_ss_em_mf``): ``low_freq`` and ``agg_weights`` as
+    ``kalman_smoother`` takes them; a marked series' loading is then estimated
+    against the aggregate of the factors.  ``a0`` and ``P0``, given and
+    returned, are those of the padded state; ``A`` stays r x rp."""
+    mixed = _ss_mixed(low_freq, agg_weights, np.shape(loadings)[-2])   # before anything touches the device
     ctx = ctx or default_context()
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
     given = [("loadings", loadings, 2), ("sigma2", sigma2, 1), ("A", A, 2), ("Q", Q, 2)]
@@ -1286,10 +1343,12 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     if r < 1 or Ash[0] != r or Ash[1] % r or arrs["loadings"][0].shape[-2] != N:
         raise ValueError("loadings must be N x r and A r x rp")
     p = Ash[1] // r
-    s = r * p
+    any_low = mixed is not None and bool(mixed[0].any())
+    s = r * (max(p, len(mixed[1])) if any_low else p)
     if arrs["sigma2"][0].shape[-1] != N or arrs["Q"][0].shape[-2:] != (r, r) or \
             ("a0" in arrs and arrs["a0"][0].shape[-1] != s) or ("P0" in arrs and arrs["P0"][0].shape[-2:] != (s, s)):
-        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have rp entries and P0 be rp x rp")
+        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have s entries and P0 be s x s "
+                         "(s = r p, or r max(p, len(agg_weights)) with low-frequency series)")
     cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
     keep, starts = [], (_lib.dfm_ss_params * max(n_start, 1))()
     for k in range(n_start):
@@ -1305,25 +1364,35 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     if mi < 0:
         mi = 100
     spec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, int(dev), float(tol))
-    Lo, so, Ao, Qo = np.zeros((M, r, N)), np.zeros((M, N)), np.zeros((M, s, r)), np.zeros((M, r, r))
+    Lo, so, Ao, Qo = np.zeros((M, r, N)), np.zeros((M, N)), np.zeros((M, r * p, r)), np.zeros((M, r, r))
     a0o, P0o = np.zeros((M, s)), np.zeros((M, s, s))
     filt, sm, cov = np.zeros((M, T, r)), np.zeros((M, T + h, r)), np.zeros((M, T + h, r, r))
     nobs = np.zeros(M, dtype=np.int64)
     path = np.full((M, mi + 1), np.nan)
+    agg = np.zeros((M, T + h, r)) if any_low else None
     out = _lib.dfm_ss_em_out(cp(Lo), cp(so), cp(Ao), cp(Qo), cp(a0o), cp(P0o), cp(filt), cp(sm), cp(cov),
-                             nobs.ctypes.data_as(_lib.c_int64_p), cp(path))
+                             nobs.ctypes.data_as(_lib.c_int64_p), cp(path), cp(agg))
     info = (_lib.dfm_ss_em_info * max(M, 1))()
     xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
-    ctx.check(ctx.lib.dfm_ss_em(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(spec), C.byref(out), info))
+    if mixed is None:
+        ctx.check(ctx.lib.dfm_ss_em(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(spec), C.byref(out),
+                                    info))
+    else:
+        low, w = mixed
+        mf = _lib.dfm_ss_mf(len(w), cp(w), low.ctypes.data_as(_lib.c_uint8_p))
+        ctx.check(ctx.lib.dfm_ss_em_mf(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(mf), C.byref(spec),
+                                       C.byref(out), info))
     del buf, keep
     tr = lambda a: np.ascontiguousarray(np.swapaxes(a, 1, 2))   # noqa: E731  (column-major per panel)
     its = np.array([info[k].iterations for k in range(M)], dtype=np.int64)
     conv = np.array([bool(info[k].converged) for k in range(M)])
     ll = np.array([info[k].loglik for k in range(M)])
     crit = np.array([info[k].crit for k in range(M)])
-    res = StateSpaceEMResult(tr(Lo), so, tr(Ao), tr(Qo), a0o, tr(P0o), filt, sm, cov, ll, nobs, path, its, conv, crit)
+    res = StateSpaceEMResult(tr(Lo), so, tr(Ao), tr(Qo), a0o, tr(P0o), filt, sm, cov, ll, nobs, path, its, conv, crit,
+                             agg)
     if single:
-        return StateSpaceEMResult(*(getattr(res, f.name)[0] for f in fields(res)))
+        return StateSpaceEMResult(*(None if getattr(res, f.name) is None else getattr(res, f.name)[0]
+                                    for f in fields(res)))
     return res
 
 
@@ -1354,7 +1423,7 @@ def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context
 def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion: str = "ICp2", lags: int = 1,
                           horizon: int = 0, *, kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50,
                           standardize: bool = True, method: str = "two-step", ml_tol: float = 1e-4,
-                          ml_max_iter: int = 100, update_init: bool = True,
+                          ml_max_iter: int = 100, update_init: bool = True, low_freq=None, agg_weights=None,
                           ctx: Optional[Context] = None) -> StateSpaceResult:
     """The two-step estimator of Doz, Giannone & Reichlin (2011) of a panel
     with missing entries (``dfm_ss_fit``): ``em_factors``, a VAR(``lags``) on
@@ -1364,9 +1433,18 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     that fit to the quasi-maximum likelihood (``dfm_ss_fit_ml``: ``ss_em`` on
     the standardised panel from the two-step parameters, ``ml_tol``,
     ``ml_max_iter``, ``update_init``); the parameters, factors and panels
-    returned are then the ML ones, ``mean`` and ``std`` stay the static EM's."""
+    returned are then the ML ones, ``mean`` and ``std`` stay the static EM's.
+
+    Mixed frequency (``dfm_ss_fit_mf``): ``low_freq`` and ``agg_weights`` as
+    ``kalman_smoother`` takes them.  The marked series' loadings and variances
+    are re-estimated on the aggregate of the EM's factors before the smoother
+    (or the ML iteration) runs at the padded state; ``P0`` and ``a0`` are of
+    that size, the fill and the forecast of a marked column come from the
+    smoothed aggregate, and the result carries ``smoothed_agg``."""
     if method not in ("two-step", "ml"):
         raise ValueError('method must be "two-step" or "ml"')
+    mixed = None if low_freq is None and agg_weights is None else \
+        _ss_mixed(low_freq, agg_weights, np.shape(x)[-1])   # before anything touches the device
     ctx = ctx or default_context()
     xp, T, N, ldx, dev, keep = _em_panel(x)
     spec = _em_spec(T, N, number_of_factors, criterion, kmax, tol, max_iter, standardize, dev)
@@ -1374,7 +1452,9 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     if h < 0:
         raise ValueError("horizon must be >= 0")
     cap = min(int(number_of_factors), 32) if number_of_factors is not None else 32
-    sc = max(cap * max(p, 1), 1)
+    any_low = mixed is not None and bool(mixed[0].any())
+    lg = max(p, len(mixed[1])) if any_low else p   # lags of the state
+    sc = max(cap * max(lg, 1), 1)
     col = lambda m, n: np.zeros((m, n), order="F")   # noqa: E731
     Z, X2, xs, xc, fc = col(T, N), col(T, N), col(T, N), col(T, N), col(h, N)
     mu, sd, sg, ev, ll = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(cap), np.zeros(1)
@@ -1385,14 +1465,26 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
                               cp(xs), cp(xc), cp(fc), cp(Z), cp(X2), cp(F), cp(ev))
     info = _lib.dfm_em_info()
     ml = {}
-    if method == "ml":
+    if method == "ml" or mixed is not None:
         mi = int(ml_max_iter) if int(ml_max_iter) >= 0 else 100
         a0, path, minfo = np.zeros(sc), np.full(mi + 1, np.nan), _lib.dfm_ss_em_info()
         mspec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, 0, float(ml_tol))
-        ctx.check(ctx.lib.dfm_ss_fit_ml(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(info),
-                                        C.byref(out), cp(a0), cp(path), C.byref(minfo)))
-        ml = dict(method="ml", a0=a0[:int(info.r) * p].copy(), loglik_path=path, ml_iterations=int(minfo.iterations),
-                  ml_converged=bool(minfo.converged), ml_criterion=float(minfo.crit))
+        if mixed is None:
+            ctx.check(ctx.lib.dfm_ss_fit_ml(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(info),
+                                            C.byref(out), cp(a0), cp(path), C.byref(minfo)))
+        else:
+            low, w = mixed
+            agg = np.zeros((T + h) * cap)
+            mf = _lib.dfm_ss_mf(len(w), cp(w), low.ctypes.data_as(_lib.c_uint8_p))
+            ctx.check(ctx.lib.dfm_ss_fit_mf(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(mf),
+                                            int(method == "ml"), C.byref(info), C.byref(out), cp(a0), cp(path),
+                                            C.byref(minfo), cp(agg)))
+            if any_low:
+                ml["smoothed_agg"] = agg[:(T + h) * int(info.r)].reshape(T + h, int(info.r)).copy()
+        if method == "ml":
+            ml.update(method="ml", a0=a0[:int(info.r) * lg].copy(), loglik_path=path,
+                      ml_iterations=int(minfo.iterations), ml_converged=bool(minfo.converged),
+                      ml_criterion=float(minfo.crit))
     else:
         ctx.check(ctx.lib.dfm_ss_fit(ctx.h, xp, T, N, ldx, C.byref(spec), p, h, C.byref(info), C.byref(out)))
     del keep
@@ -1402,7 +1494,7 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     Lr, Fr = cm(L, N, r), cm(F, T, r)
     em = EMResult(np.ascontiguousarray(Z), np.ascontiguousarray(X2), mu, sd, Fr, Lr, ev[:r].copy(), r,
                   int(info.iterations), float(info.err), bool(info.converged), int(info.n_missing))
-    return StateSpaceResult(em, mu, sd, Lr, sg, cm(A, r, s), cm(Q, r, r), cm(P0, s, s),
+    return StateSpaceResult(em, mu, sd, Lr, sg, cm(A, r, s), cm(Q, r, r), cm(P0, r * lg, r * lg),
                             filt[:T * r].reshape(T, r).copy(), sm[:(T + h) * r].reshape(T + h, r).copy(),
                             cov[:(T + h) * r * r].reshape(T + h, r, r).copy(), float(ll[0]),
                             np.ascontiguousarray(xs), np.ascontiguousarray(xc), np.ascontiguousarray(fc), r, p, **ml)

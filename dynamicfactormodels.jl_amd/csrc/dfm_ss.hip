@@ -32,6 +32,13 @@
 //   ss_transition_kernel per panel A, Q, the companion matrix, a0 / P0
 // and ss_empty_column_kernel looks once, before the first pass, for a column
 // of a device-resident panel without an observed entry.
+// The mixed-frequency entry points (dfm_ss_smooth_mf, dfm_ss_em_mf,
+// dfm_ss_fit_mf) run the same launches at the padded state: the collapse on
+// wider operands (a tri(C) | b group per class), ss_filter_kernel<true>, which
+// updates once per class, ss_smoother_kernel<., true>, which also emits
+// Z_l a_t|T and the low class's moments, and the <true> instantiations of the
+// M-step kernels, which read and write a series' own class's columns and
+// regress the VAR on its own lags.
 // No kernel uses an atomic, and the K splits depend on N and T alone: results
 // are bit-identical run to run, and panel b of a batch is bit-identical to a
 // call on panel b alone.
@@ -141,6 +148,9 @@ struct SsArgs {
   double *filt, *smooth, *cov, *ll, *nobs;   // per panel T x r, Tt x r, Tt x r x r, 1, 1 (nullptr: not wanted)
   int *flag;                           // per panel: 1 a P_{t+1|t} not positive definite, 2 a G singular
   double *opnd, *mom;                  // the smoother's moments (ss_smoother_kernel<true>): [panel][T][NCP], [panel][SS_MOM]
+  int nw;                              // mixed frequency: the low class's weights w_0..w_{nw-1} (device memory)
+  const double *w;
+  double *agg;                         // per panel Tt x r, the smoothed aggregate Z_l a_t|T (nullptr: not wanted)
 };
 
 // Panel blockIdx.x.  Matrices live in LDS with row stride SS_LS; the rows
@@ -151,17 +161,24 @@ struct SsArgs {
 // entry (n_t = 0; every row t >= T) leaves a and P as they are.  Every
 // workspace element is read back by the thread index that wrote it, in the
 // filter and (a launch later) in the smoother.
+//
+// MF: the mixed-frequency model (include/dfm.h).  A collapsed row then holds
+// one tri(C) | b group per class (high, low), then q_t, n_t, l_t and the low
+// class's count; the update runs once per class with an observed entry.
+template <bool MF>
 __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
-  __shared__ double lds[7 * SS_MAT + 7 * 32 + 160 + 4];
+  __shared__ double lds[7 * SS_MAT + 7 * 32 + (MF ? 320 : 160) + 4 + (MF ? 24 : 0)];
   __shared__ int ibad, ipiv;
   double *Tm = lds, *P = Tm + SS_MAT, *W = P + SS_MAT, *GA = W + SS_MAT, *K = GA + SS_MAT, *KC = K + SS_MAT,
          *Qr = KC + SS_MAT;
   double *a = Qr + SS_MAT, *an = a + 32, *d = an + 32, *gv = d + 32, *colj = gv + 32, *rowj = colj + 32,
-         *crow = rowj + 64, *sc = crow + 160;   // sc: loglik, log det G, observed count
+         *crow = rowj + 64, *sc = crow + (MF ? 320 : 160);   // sc: loglik, log det G, observed count
+  double *zl = MF ? sc + 4 : nullptr, *wl = MF ? zl + 16 : nullptr;   // MF: Z_l a and the weights
+  double *PZl = K + 16, *Vl = KC + 16;  // MF: P Z_l' (s x r) and Z_l P Z_l' (r x r) in the columns K and KC leave free
   const int tid = threadIdx.x, b = blockIdx.x;
   if (g.active && !g.active[b]) return;
   const int T = g.T, Tt = g.Tt, r = g.r, s = g.s, ss = s * s;
-  const int cb = r * (r + 1) / 2, cq = cb + r, cn = cq + 1, cl = cq + 2;
+  const int nC = r * (r + 1) / 2, nG = nC + r, cq = MF ? 2 * nG : nG, cn = cq + 1, cl = cq + 2;
   const double *gTm = g.Tm + (int64_t)b * g.pstride, *gQ = g.Q + (int64_t)b * g.pstride,
                *ga0 = g.a0 + (int64_t)b * g.pstride, *gP0 = g.P0 + (int64_t)b * g.pstride;
   double *au = g.ws + (int64_t)b * Tt * (2 * s + 2 * ss), *ap = au + (int64_t)Tt * s, *Pu = ap + (int64_t)Tt * s,
@@ -176,9 +193,95 @@ __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
   for (int e = tid; e < r * r; e += 256) Qr[(e / r) * SS_LS + e % r] = gQ[e];
   if (tid < s) a[tid] = ga0[tid];
   if (tid < 3) sc[tid] = 0.0;
+  if (MF && tid < g.nw) wl[tid] = g.w[tid];
   if (tid == 0) ibad = 0;
   __syncthreads();
-  auto C = [&](int i, int j) { return crow[ss_tri(i, j)]; };
+  // One class's update against Z_c: PZ = P Z_c' (s x r), V = Z_c PZ, z = Z_c a,
+  // the class's moments at column co of the row.  n_t, l_t and q_t are sums
+  // over both classes: the row's first update brings them to the
+  // log-likelihood.  The high class reads P and a in place.
+  auto update = [&](const double *PZc, const double *Vc, const double *zc, int co, double nt, bool first) {
+    const double *PZ = MF ? PZc : P, *V = MF ? Vc : P, *z = MF ? zc : a, *cr = MF ? crow + co : crow;
+    auto C = [&](int i, int j) { return cr[ss_tri(i, j)]; };
+    for (int e = tid; e < r * r + r; e += 256) {
+      if (e < r * r) {   // G = I + C V beside the identity
+        const int i = e / r, j = e % r;
+        double v = i == j ? 1.0 : 0.0;
+        for (int k = 0; k < r; ++k) v = fma(C(i, k), V[k * SS_LS + j], v);
+        GA[i * SS_LS + j] = v;
+        GA[i * SS_LS + r + j] = i == j ? 1.0 : 0.0;
+      } else {           // d = b - C z
+        const int i = e - r * r;
+        double v = cr[nC + i];
+        for (int k = 0; k < r; ++k) v = fma(-C(i, k), z[k], v);
+        d[i] = v;
+      }
+    }
+    __syncthreads();
+    dfm::block_gj_inverse(GA, r, SS_LS, colj, rowj, sc + 1, &ipiv, &ibad);
+    for (int e = tid; e < s * r + r; e += 256) {
+      if (e < s * r) {   // K = PZ G^-1
+        const int i = e / r, j = e % r;
+        double v = 0.0;
+        for (int k = 0; k < r; ++k) v = fma(PZ[i * SS_LS + k], GA[k * SS_LS + r + j], v);
+        K[i * SS_LS + j] = v;
+      } else {           // G^-1 d
+        const int i = e - s * r;
+        double v = 0.0;
+        for (int k = 0; k < r; ++k) v = fma(GA[i * SS_LS + r + k], d[k], v);
+        gv[i] = v;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < s * r + s + 1; e += 256) {
+      if (e < s * r) {            // K C
+        const int i = e / r, j = e % r;
+        double v = 0.0;
+        for (int k = 0; k < r; ++k) v = fma(K[i * SS_LS + k], C(k, j), v);
+        KC[i * SS_LS + j] = v;
+      } else if (e < s * r + s) {   // a + K d
+        const int i = e - s * r;
+        double v = a[i];
+        for (int k = 0; k < r; ++k) v = fma(K[i * SS_LS + k], d[k], v);
+        an[i] = v;
+      } else {                    // the class's term of the log-likelihood, with z and V from before the update
+        double ba = 0.0, aCa = 0.0, dPg = 0.0;
+        for (int i = 0; i < r; ++i) {
+          double ca = 0.0, pg = 0.0;
+          for (int k = 0; k < r; ++k) {
+            ca = fma(C(i, k), z[k], ca);
+            pg = fma(V[i * SS_LS + k], gv[k], pg);
+          }
+          ba = fma(cr[nC + i], z[i], ba);
+          aCa = fma(z[i], ca, aCa);
+          dPg = fma(d[i], pg, dPg);
+        }
+        if (!MF || first) {
+          sc[0] -= 0.5 * (nt * 1.8378770664093453 + crow[cl] + sc[1] + crow[cq] - 2.0 * ba + aCa - dPg);
+          sc[2] += nt;
+        } else {
+          sc[0] -= 0.5 * (sc[1] - 2.0 * ba + aCa - dPg);
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < ss + s; e += 256) {
+      if (e < ss) {   // P - K C PZ'
+        const int i = e / s, j = e % s;
+        double v = P[i * SS_LS + j];
+        for (int k = 0; k < r; ++k) v = fma(-KC[i * SS_LS + k], PZ[j * SS_LS + k], v);
+        W[i * SS_LS + j] = v;
+      } else {
+        a[e - ss] = an[e - ss];
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < ss; e += 256) {
+      const int i = e / s, j = e % s;
+      P[i * SS_LS + j] = 0.5 * (W[i * SS_LS + j] + W[j * SS_LS + i]);
+    }
+    __syncthreads();
+  };
   // ------------------------------------------------------------ the filter
   for (int t = 0; t < Tt; ++t) {
     if (t < T)
@@ -189,81 +292,36 @@ __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
       }
     __syncthreads();
     const double nt = t < T ? crow[cn] : 0.0;
-    if (nt > 0.0) {
-      for (int e = tid; e < r * r + r; e += 256) {
-        if (e < r * r) {   // G = I + C Pff beside the identity
-          const int i = e / r, j = e % r;
-          double v = i == j ? 1.0 : 0.0;
-          for (int k = 0; k < r; ++k) v = fma(C(i, k), P[k * SS_LS + j], v);
-          GA[i * SS_LS + j] = v;
-          GA[i * SS_LS + r + j] = i == j ? 1.0 : 0.0;
-        } else {           // d = b - C a_f
-          const int i = e - r * r;
-          double v = crow[cb + i];
-          for (int k = 0; k < r; ++k) v = fma(-C(i, k), a[k], v);
-          d[i] = v;
-        }
-      }
-      __syncthreads();
-      dfm::block_gj_inverse(GA, r, SS_LS, colj, rowj, sc + 1, &ipiv, &ibad);
-      for (int e = tid; e < s * r + r; e += 256) {
-        if (e < s * r) {   // K = Pf G^-1
-          const int i = e / r, j = e % r;
-          double v = 0.0;
-          for (int k = 0; k < r; ++k) v = fma(P[i * SS_LS + k], GA[k * SS_LS + r + j], v);
-          K[i * SS_LS + j] = v;
-        } else {           // G^-1 d
-          const int i = e - s * r;
-          double v = 0.0;
-          for (int k = 0; k < r; ++k) v = fma(GA[i * SS_LS + r + k], d[k], v);
-          gv[i] = v;
-        }
-      }
-      __syncthreads();
-      for (int e = tid; e < s * r + s + 1; e += 256) {
-        if (e < s * r) {            // K C
-          const int i = e / r, j = e % r;
-          double v = 0.0;
-          for (int k = 0; k < r; ++k) v = fma(K[i * SS_LS + k], C(k, j), v);
-          KC[i * SS_LS + j] = v;
-        } else if (e < s * r + s) {   // a + K d
-          const int i = e - s * r;
-          double v = a[i];
-          for (int k = 0; k < r; ++k) v = fma(K[i * SS_LS + k], d[k], v);
-          an[i] = v;
-        } else {                    // the row's term of the log-likelihood, with a_f and Pff from before the update
-          double ba = 0.0, aCa = 0.0, dPg = 0.0;
-          for (int i = 0; i < r; ++i) {
-            double ca = 0.0, pg = 0.0;
-            for (int k = 0; k < r; ++k) {
-              ca = fma(C(i, k), a[k], ca);
-              pg = fma(P[i * SS_LS + k], gv[k], pg);
-            }
-            ba = fma(crow[cb + i], a[i], ba);
-            aCa = fma(a[i], ca, aCa);
-            dPg = fma(d[i], pg, dPg);
+    if (!MF) {
+      if (nt > 0.0) update(P, P, a, 0, nt, true);
+    } else if (nt > 0.0) {
+      const double nl = crow[cq + 3], nh = nt - nl;
+      if (nh > 0.0) update(P, P, a, 0, nt, true);
+      if (nl > 0.0) {
+        const int nw = g.nw;
+        for (int e = tid; e < s * r + r; e += 256) {
+          if (e < s * r) {   // P Z_l'
+            const int i = e / r, j = e % r;
+            double v = 0.0;
+            for (int k = 0; k < nw; ++k) v = fma(wl[k], P[i * SS_LS + k * r + j], v);
+            PZl[i * SS_LS + j] = v;
+          } else {           // Z_l a
+            const int i = e - s * r;
+            double v = 0.0;
+            for (int k = 0; k < nw; ++k) v = fma(wl[k], a[k * r + i], v);
+            zl[i] = v;
           }
-          sc[0] -= 0.5 * (nt * 1.8378770664093453 + crow[cl] + sc[1] + crow[cq] - 2.0 * ba + aCa - dPg);
-          sc[2] += nt;
         }
-      }
-      __syncthreads();
-      for (int e = tid; e < ss + s; e += 256) {
-        if (e < ss) {   // P - K C Pf'
-          const int i = e / s, j = e % s;
-          double v = P[i * SS_LS + j];
-          for (int k = 0; k < r; ++k) v = fma(-KC[i * SS_LS + k], P[j * SS_LS + k], v);
-          W[i * SS_LS + j] = v;
-        } else {
-          a[e - ss] = an[e - ss];
+        __syncthreads();
+        for (int e = tid; e < r * r; e += 256) {   // Z_l P Z_l'
+          const int i = e / r, j = e % r;
+          double v = 0.0;
+          for (int k = 0; k < nw; ++k) v = fma(wl[k], PZl[(k * r + i) * SS_LS + j], v);
+          Vl[i * SS_LS + j] = v;
         }
+        __syncthreads();
+        update(PZl, Vl, zl, nG, nt, !(nh > 0.0));
       }
-      __syncthreads();
-      for (int e = tid; e < ss; e += 256) {
-        const int i = e / s, j = e % s;
-        P[i * SS_LS + j] = 0.5 * (W[i * SS_LS + j] + W[j * SS_LS + i]);
-      }
-      __syncthreads();
     }
     for (int e = tid; e < ss; e += 256) Pu[(int64_t)t * ss + e] = P[(e / s) * SS_LS + e % s];
     if (tid < s) au[(int64_t)t * s + tid] = a[tid];
@@ -336,14 +394,18 @@ __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
 // from the host's memset).  mom: S11, S10, S00, a_1|T, P_1|T at SS_M*.
 constexpr int SS_M11 = 0, SS_M10 = 256, SS_M00 = 768, SS_MA1 = 1792, SS_MP1 = 1824, SS_MOM = 2848;
 
-template <bool MOM>
+// AGG: the mixed-frequency model: also the smoothed aggregate Z_l a_t|T, from
+// a while it holds row t, and with MOM the low class's group of the operand
+// row, tri(Z_l (a a' + P_t|T) Z_l') | Z_l a, after the high class's, then the 1.
+template <bool MOM, bool AGG>
 __global__ __launch_bounds__(256) void ss_smoother_kernel(SsArgs g) {
-  __shared__ double lds[7 * SS_MAT + 4 * 32 + (MOM ? 32 : 0)];
+  __shared__ double lds[7 * SS_MAT + 4 * 32 + (MOM ? 32 : 0) + (AGG ? SS_WMAX : 0)];
   __shared__ int ibad;
   double *Tm = lds, *P = Tm + SS_MAT, *B1 = P + SS_MAT, *Lw = B1 + SS_MAT, *Tw = Lw + SS_MAT, *J = Tw + SS_MAT,
          *Ps = J + SS_MAT;
   double *a = Ps + SS_MAT, *an = a + 32, *d = an + 32, *gv = d + 32;
   double *fp = gv + 32;   // MOM: f_{t+1|T}, kept while a moves on to row t
+  double *wl = AGG ? fp + (MOM ? 32 : 0) : nullptr;   // AGG: the weights
   const int tid = threadIdx.x, b = blockIdx.x;
   if (g.active && !g.active[b]) return;
   const int T = g.T, Tt = g.Tt, r = g.r, s = g.s, ss = s * s;
@@ -355,6 +417,11 @@ __global__ __launch_bounds__(256) void ss_smoother_kernel(SsArgs g) {
     if (g.smooth && tid < r) g.smooth[((int64_t)b * Tt + t) * r + tid] = a[tid];
     if (g.cov)
       for (int e = tid; e < r * r; e += 256) g.cov[((int64_t)b * Tt + t) * r * r + e] = Ps[(e / r) * SS_LS + e % r];
+    if (AGG && g.agg && tid < r) {
+      double v = 0.0;
+      for (int k = 0; k < g.nw; ++k) v = fma(wl[k], a[k * r + tid], v);
+      g.agg[((int64_t)b * Tt + t) * r + tid] = v;
+    }
     if (!MOM || t >= T) return;
     double *row = g.opnd + ((int64_t)b * T + t) * g.NCP;
     const int nC = r * (r + 1) / 2;
@@ -365,7 +432,20 @@ __global__ __launch_bounds__(256) void ss_smoother_kernel(SsArgs g) {
       if (t >= 1) s11 += v;
     }
     if (tid < r) row[nC + tid] = a[tid];
-    if (tid == 0) row[nC + r] = 1.0;
+    if (tid == 0) row[AGG ? 2 * (nC + r) : nC + r] = 1.0;
+    if (AGG && tid < r * r) {   // the low class's group
+      const int i = tid / r, j = tid % r, nw = g.nw;
+      double fi = 0.0, fj = 0.0, pv = 0.0;
+      for (int k = 0; k < nw; ++k) {
+        fi = fma(wl[k], a[k * r + i], fi);
+        fj = fma(wl[k], a[k * r + j], fj);
+        double pk = 0.0;
+        for (int k2 = 0; k2 < nw; ++k2) pk = fma(wl[k2], Ps[(k * r + i) * SS_LS + k2 * r + j], pk);
+        pv = fma(wl[k], pk, pv);
+      }
+      if (i >= j) row[nC + r + ss_tri(i, j)] = fma(fi, fj, pv);
+      if (j == 0) row[nC + r + nC + i] = fi;
+    }
     if (t + 1 < T) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -379,6 +459,7 @@ __global__ __launch_bounds__(256) void ss_smoother_kernel(SsArgs g) {
     Ps[(e / s) * SS_LS + e % s] = Pu[(int64_t)(Tt - 1) * ss + e];
   }
   if (tid < s) a[tid] = au[(int64_t)(Tt - 1) * s + tid];
+  if (AGG && tid < g.nw) wl[tid] = g.w[tid];
   if (tid == 0) ibad = 0;
   __syncthreads();
   emit(Tt - 1);
@@ -492,6 +573,9 @@ constexpr int SS_LB = 32;   // series per workgroup of ss_loadings_kernel
 // column-major panel: a thread stages four series at one t, sixteen
 // consecutive t side by side.  q_i = sum x^2 is summed beside the MFMA as q_t
 // is in the collapse.  pm: [panel][chunk][Nr][NCP], Nr = 64 gridDim.x.
+// MF: the operand row has a tri | f group per class: the value columns are two
+// ranges, and n_i, q_i follow the second group.
+template <bool MF>
 __global__ __launch_bounds__(256) void ss_mstep_kernel(const double *__restrict__ X, int64_t ldx, int64_t stride, int T,
                                                        int N, const double *__restrict__ opnd,
                                                        const int *__restrict__ active, int r, int NCP, int nct, int KS,
@@ -503,7 +587,7 @@ __global__ __launch_bounds__(256) void ss_mstep_kernel(const double *__restrict_
   const int rb = blockIdx.x, cb = blockIdx.y % nct, ks = blockIdx.y / nct, b = blockIdx.z;
   if (!active[b]) return;
   const int abase = rb * 64, bbase = cb * 64, Nr = 64 * gridDim.x;
-  const int nC = r * (r + 1) / 2, cn = nC + r, cq = cn + 1;
+  const int nC = r * (r + 1) / 2, nG = nC + r, cn = MF ? 2 * nG : nG, cq = cn + 1;
   const int Tpad = (T + 15) & ~15;
   const int k0 = ks * SS_KC, k1 = min(Tpad, k0 + SS_KC);
   const bool own_q = cq >= bbase && cq < bbase + 64;
@@ -530,7 +614,7 @@ __global__ __launch_bounds__(256) void ss_mstep_kernel(const double *__restrict_
       lv[ss_offA(ga + i, ka)] = v;
       if (own_q) qs[i] = fma(v, v, qs[i]);
       const int c = bbase + g4 + i;
-      const bool fcol = c >= nC && c < cn;
+      const bool fcol = (c >= nC && c < nG) || (MF && c >= nG + nC && c < 2 * nG);
       lbm[ss_offB(g4 + i, kk)] = fcol ? 0.0 : o[i];
       lbv[ss_offB(g4 + i, kk)] = fcol ? o[i] : 0.0;
     }
@@ -590,13 +674,18 @@ struct SsBlock {
 // pass's operands of the collapse.  status ([panel][N]): 0, or 1 S_i not
 // positive definite, 2 sigma^2_i not positive, 3 no observed entry — the
 // parameters of such a series are left as they were.
+// MF: low[i] names the series' class; it reads that class's group of its row
+// and writes the collapse operands at that class's columns.
+template <bool MF>
 __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__restrict__ pm, int N, int Nr, int r, int NCP,
                                                             int KS, const int *__restrict__ active, SsBlock L,
-                                                            double *__restrict__ par, int *__restrict__ status) {
+                                                            double *__restrict__ par, int *__restrict__ status,
+                                                            const uint8_t *__restrict__ low) {
   __shared__ double w[(SS_RMAX * (SS_RMAX + 1) / 2 + 2 * SS_RMAX) * SS_LB];
   const int tid = threadIdx.x, i = blockIdx.x * SS_LB + tid, b = blockIdx.y;
   if (!active[b] || i >= N) return;
-  const int nC = r * (r + 1) / 2, cn = nC + r, cq = cn + 1;
+  const int nC = r * (r + 1) / 2, cn = nC + r;
+  const int co = MF && low[i] ? cn : 0, ccn = MF ? 2 * cn : cn, cq = ccn + 1;   // the group, n_i and q_i in the row
   auto W = [&](int e) -> double & { return w[e * SS_LB + tid]; };
   const double *row = pm + ((int64_t)b * KS * Nr + i) * NCP;
   const int64_t kstep = (int64_t)Nr * NCP;
@@ -605,8 +694,8 @@ __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__rest
     for (int k = 0; k < KS; ++k) v += row[k * kstep + c];
     return v;
   };
-  for (int c = 0; c < cn; ++c) W(c) = chunks(c);
-  const double n = chunks(cn), q = chunks(cq);
+  for (int c = 0; c < cn; ++c) W(c) = chunks(co + c);
+  const double n = chunks(ccn), q = chunks(cq);
   bool bad = false;
   for (int j = 0; j < r; ++j) {
     double d = W(ss_tri(j, j));
@@ -644,11 +733,11 @@ __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__rest
   double *wm = P + L.oWm + (int64_t)i * NCP, *wv = P + L.oWv + (int64_t)i * NCP;
   for (int a = 0; a < r; ++a) {
     const double la = W(y + a);
-    for (int c = 0; c <= a; ++c) wm[ss_tri(a, c)] = la * W(y + c) / v;
-    wv[nC + a] = la / v;
+    for (int c = 0; c <= a; ++c) wm[co + ss_tri(a, c)] = la * W(y + c) / v;
+    wv[co + nC + a] = la / v;
     P[L.oL + (int64_t)a * N + i] = la;
   }
-  wm[cn + 2] = log(v);
+  wm[ccn + 2] = log(v);
   P[L.owi + i] = 1.0 / v;
   P[L.osig + i] = v;
 }
@@ -657,7 +746,10 @@ __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__rest
 // A into the companion matrix's first r rows, and (update_init) a0 <- a_1|T,
 // P0 <- P_1|T.  It also reduces the series' status to the panel's M-step flag
 // (1 an S_i, 2 a sigma^2_i, 4 an empty column, 8 S00) and the first such column.
-__global__ __launch_bounds__(256) void ss_transition_kernel(const double *__restrict__ mom, int T, int N, int r, int s,
+// MF: the regression runs on the leading rp block of S00 and S10 (the VAR's
+// own lags); the companion matrix's columns beyond stay zero.
+template <bool MF>
+__global__ __launch_bounds__(256) void ss_transition_kernel(const double *__restrict__ mom, int T, int N, int r, int s, int rp,
                                                             int update_init, const int *__restrict__ active, SsBlock L,
                                                             double *__restrict__ par, const int *__restrict__ status,
                                                             int *__restrict__ mflag, int *__restrict__ mcol) {
@@ -669,26 +761,27 @@ __global__ __launch_bounds__(256) void ss_transition_kernel(const double *__rest
   if (!active[b]) return;
   const double *m = mom + (int64_t)b * SS_MOM;
   double *P = par + (int64_t)b * L.stride;
-  for (int e = tid; e < ss; e += 256) S00[(e / s) * SS_LS + e % s] = m[SS_M00 + e];
-  for (int e = tid; e < r * s; e += 256) S10[(e / s) * SS_LS + e % s] = m[SS_M10 + e];
+  const int n = MF ? rp : s;
+  for (int e = tid; e < n * n; e += 256) S00[(e / n) * SS_LS + e % n] = m[SS_M00 + (e / n) * s + e % n];
+  for (int e = tid; e < r * n; e += 256) S10[(e / n) * SS_LS + e % n] = m[SS_M10 + (e / n) * s + e % n];
   int f = N;
   for (int i = tid; i < N; i += 256)
     if (status[(int64_t)b * N + i] && i < f) f = i;
   first[tid] = f;
   if (tid == 0) ibad = 0;
   __syncthreads();
-  dfm::block_spd_inverse(S00, Si, Lw, Tw, s, SS_LS, &ibad);
-  for (int e = tid; e < r * s; e += 256) {
-    const int i = e / s, j = e % s;
+  dfm::block_spd_inverse(S00, Si, Lw, Tw, n, SS_LS, &ibad);
+  for (int e = tid; e < r * n; e += 256) {
+    const int i = e / n, j = e % n;
     double v = 0.0;
-    for (int k = 0; k < s; ++k) v = fma(S10[i * SS_LS + k], Si[k * SS_LS + j], v);
+    for (int k = 0; k < n; ++k) v = fma(S10[i * SS_LS + k], Si[k * SS_LS + j], v);
     Am[i * SS_LS + j] = v;
   }
   __syncthreads();
   for (int e = tid; e < r * r; e += 256) {
     const int i = e / r, j = e % r;
     double v = m[SS_M11 + e];
-    for (int k = 0; k < s; ++k) v = fma(-Am[i * SS_LS + k], S10[j * SS_LS + k], v);
+    for (int k = 0; k < n; ++k) v = fma(-Am[i * SS_LS + k], S10[j * SS_LS + k], v);
     Lw[i * SS_LS + j] = v / (double)(T - 1);
   }
   __syncthreads();
@@ -697,7 +790,7 @@ __global__ __launch_bounds__(256) void ss_transition_kernel(const double *__rest
       const int i = e / r, j = e % r;
       P[L.oQ + e] = 0.5 * (Lw[i * SS_LS + j] + Lw[j * SS_LS + i]);
     }
-    for (int e = tid; e < r * s; e += 256) P[L.oTm + e] = Am[(e / s) * SS_LS + e % s];
+    for (int e = tid; e < r * n; e += 256) P[L.oTm + (e / n) * s + e % n] = Am[(e / n) * SS_LS + e % n];
     if (update_init) {
       for (int e = tid; e < ss; e += 256) P[L.oP0 + e] = m[SS_MP1 + e];
       if (tid < s) P[L.oa0 + tid] = m[SS_MA1 + tid];
@@ -770,19 +863,24 @@ SsBlock ss_block(int N, int r, int s, int NCP) {
 
 // The block of checked parameters; a null P0 is the stationary covariance
 // (SS_E_EXPLOSIVE when the doubling iteration does not converge).
-int ss_fill_block(const SsParams &pr, int N, int NCP, const SsBlock &B, double *hp) {
-  const int r = pr.r, p = pr.p, s = r * p, nC = r * (r + 1) / 2, cq = nC + r;
+// low (mixed frequency): a series' tri(C) | b columns are its class's group
+// (the low class's follows the high class's), and the column after l_t counts
+// the low class.
+int ss_fill_block(const SsParams &pr, int N, int NCP, const SsBlock &B, double *hp, const uint8_t *low = nullptr) {
+  const int r = pr.r, p = pr.p, s = r * p, nC = r * (r + 1) / 2, nG = nC + r, cq = low ? 2 * nG : nG;
   std::fill(hp, hp + B.stride, 0.0);
   for (int i = 0; i < N; ++i) {
     const double v = pr.sigma2[i];
+    const int co = low && low[i] ? nG : 0;
     double *wm = &hp[B.oWm + (size_t)i * NCP], *wv = &hp[B.oWv + (size_t)i * NCP];
     for (int a = 0; a < r; ++a) {
       const double la = pr.L[(size_t)a * N + i];
-      for (int c = 0; c <= a; ++c) wm[ss_tri(a, c)] = la * pr.L[(size_t)c * N + i] / v;
-      wv[nC + a] = la / v;
+      for (int c = 0; c <= a; ++c) wm[co + ss_tri(a, c)] = la * pr.L[(size_t)c * N + i] / v;
+      wv[co + nC + a] = la / v;
     }
     wm[cq + 1] = 1.0;
     wm[cq + 2] = log(v);
+    if (co) wm[cq + 3] = 1.0;
     hp[B.owi + i] = 1.0 / v;
   }
   ss_companion(pr.A, r, p, &hp[B.oTm]);
@@ -801,26 +899,31 @@ int ss_fill_block(const SsParams &pr, int N, int NCP, const SsBlock &B, double *
 }
 
 // The smoother over M panels (layout of dfm_mc).  Outputs host, any nullptr.
+// mf: the mixed-frequency model (checked; pr is then the padded state's: p =
+// max(p, n_w), A = [A 0]) with its smoothed aggregate agg; null: the plain model.
 int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx, int64_t stride,
                    bool dev, const SsParams &pr, int h, double *filt, double *smooth, double *cov, double *loglik,
-                   int64_t *nobs) {
-  if (M < 0 || h < 0 || h > (1 << 20)) return fail(ctx, -2, "dfm_ss_smooth: bad arguments");
+                   int64_t *nobs, const dfm_ss_mf *mf = nullptr, double *agg = nullptr) {
+  const char *who = mf ? "dfm_ss_smooth_mf" : "dfm_ss_smooth";
+  if (M < 0 || h < 0 || h > (1 << 20)) return fail(ctx, -2, "%s: bad arguments", who);
   int64_t where = -1;
   int rc = ss_check_params(N64, pr.r, pr.p, pr.L, pr.sigma2, pr.A, pr.Q, pr.a0, pr.P0, &where);
-  if (rc) return ss_param_error(ctx, "dfm_ss_smooth", rc, where);
+  if (rc) return ss_param_error(ctx, who, rc, where);
   if (M == 0) return 0;
-  if (!X || T64 < 1 || N64 < 1 || ldx < T64 || stride < ldx * N64) return fail(ctx, -2, "dfm_ss_smooth: bad panel layout");
+  if (!X || T64 < 1 || N64 < 1 || ldx < T64 || stride < ldx * N64) return fail(ctx, -2, "%s: bad panel layout", who);
   if (T64 + h > (1 << 24) || N64 > (1 << 24)) return fail(ctx, -2, "panel too large");
   const int T = (int)T64, N = (int)N64, r = pr.r, p = pr.p, s = r * p, ss = s * s, Tt = T + h;
-  const int ncols = ss_ncols(r), nct = (ncols + 63) / 64, NCP = nct * 64, Npad = (N + 15) & ~15;
+  const int cq = (mf ? 2 : 1) * (r * (r + 1) / 2 + r);
+  const int ncols = mf ? cq + 4 : ss_ncols(r), nct = (ncols + 63) / 64, NCP = nct * 64, Npad = (N + 15) & ~15;
   const int nrt = (T + 63) / 64, Tpad = nrt * 64, KS = (Npad + SS_KC - 1) / SS_KC;
-  const int cq = r * (r + 1) / 2 + r;
-  // ---- the shared parameters: operands of the collapse, companion form, Q, a0, P0
+  // ---- the shared parameters: operands of the collapse, companion form, Q, a0, P0, then the weights
   const SsBlock B = ss_block(N, r, s, NCP);
   const size_t oWm = B.oWm, oWv = B.oWv, owi = B.owi, oTm = B.oTm, oQ = B.oQ, oa0 = B.oa0, oP0 = B.oP0,
-               total = (size_t)B.stride;
+               ow = (size_t)B.stride, total = ow + (mf ? SS_WMAX : 0);
   std::vector<double> hp(total);
-  if ((rc = ss_fill_block(pr, N, NCP, B, hp.data()))) return ss_param_error(ctx, "dfm_ss_smooth", rc, -1);
+  if ((rc = ss_fill_block(pr, N, NCP, B, hp.data(), mf ? mf->low : nullptr)))
+    return ss_param_error(ctx, who, rc, -1);
+  if (mf) std::copy(mf->w, mf->w + mf->n_w, &hp[ow]);
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
   StreamBuf dpar;
@@ -829,7 +932,7 @@ int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_
   HIPCHK(ctx, hipMemcpyAsync(dp, hp.data(), total * 8, hipMemcpyHostToDevice, st));
   // ---- panels per pass: the collapsed rows and the recursion's workspace, about half a GB at the most
   const size_t per_part = (size_t)KS * Tpad * NCP, per_ws = (size_t)Tt * (2 * (size_t)s + 2 * (size_t)ss),
-               per_out = (size_t)T * r + (size_t)Tt * r + (size_t)Tt * r * r + 2;
+               per_out = (size_t)T * r + (size_t)Tt * r + (size_t)Tt * r * r + 2 + (agg ? (size_t)Tt * r : 0);
   const size_t per = (per_part + per_ws + per_out) * 8;
   const int64_t mb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, 65535), (int64_t)(((size_t)1 << 29) / per)));
   StreamBuf dwork, dx, dflag;
@@ -840,7 +943,7 @@ int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_
   double *w = (double *)dwork.p;
   double *part = w, *ws = part + (size_t)mb * per_part, *dfilt = ws + (size_t)mb * per_ws,
          *dsm = dfilt + (size_t)mb * T * r,
-         *dcov = dsm + (size_t)mb * Tt * r, *dll = dcov + (size_t)mb * Tt * r * r, *dn = dll + mb;
+         *dcov = dsm + (size_t)mb * Tt * r, *dll = dcov + (size_t)mb * Tt * r * r, *dn = dll + mb, *dagg = dn + mb;
   std::vector<int> hflag((size_t)mb);
   std::vector<double> hn((size_t)mb);
   for (int64_t c0 = 0; c0 < M; c0 += mb) {
@@ -861,9 +964,14 @@ int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_
       Scope sc(ctx, DFM_KC_MISC);
       SsArgs g{T, Tt, r, s, ncols, KS, Tpad, NCP, part, dp + oTm, dp + oQ, dp + oa0, dp + oP0, 0, nullptr, ws,
                filt ? dfilt : nullptr, smooth ? dsm : nullptr, cov ? dcov : nullptr, dll, dn, (int *)dflag.p,
-               nullptr, nullptr};
-      hipLaunchKernelGGL(ss_filter_kernel, dim3((unsigned)n), dim3(256), 0, st, g);
-      hipLaunchKernelGGL(ss_smoother_kernel<false>, dim3((unsigned)n), dim3(256), 0, st, g);
+               nullptr, nullptr, mf ? mf->n_w : 0, dp + ow, agg ? dagg : nullptr};
+      if (mf) {
+        hipLaunchKernelGGL(ss_filter_kernel<true>, dim3((unsigned)n), dim3(256), 0, st, g);
+        hipLaunchKernelGGL((ss_smoother_kernel<false, true>), dim3((unsigned)n), dim3(256), 0, st, g);
+      } else {
+        hipLaunchKernelGGL(ss_filter_kernel<false>, dim3((unsigned)n), dim3(256), 0, st, g);
+        hipLaunchKernelGGL((ss_smoother_kernel<false, false>), dim3((unsigned)n), dim3(256), 0, st, g);
+      }
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(hflag.data(), dflag.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -873,10 +981,11 @@ int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_
     if (cov)
       HIPCHK(ctx, hipMemcpyAsync(cov + c0 * Tt * r * r, dcov, (size_t)n * Tt * r * r * 8, hipMemcpyDeviceToHost, st));
     if (loglik) HIPCHK(ctx, hipMemcpyAsync(loglik + c0, dll, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (agg) HIPCHK(ctx, hipMemcpyAsync(agg + c0 * Tt * r, dagg, (size_t)n * Tt * r * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i) {
       if (hflag[i])
-        return fail(ctx, SS_E_SINGULAR, "dfm_ss_smooth: panel %lld: %s not invertible", (long long)(c0 + i),
+        return fail(ctx, SS_E_SINGULAR, "%s: panel %lld: %s not invertible", who, (long long)(c0 + i),
                     (hflag[i] & 2) ? "a G = I + C_t Pff is" : "a P_{t+1|t} is");
       if (nobs) nobs[c0 + i] = (int64_t)hn[i];
     }
@@ -889,7 +998,9 @@ int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_
 // and the `active` flags go back; the rest crosses the bus at the end.
 int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx,
                int64_t stride, bool dev, const dfm_ss_params *starts, int64_t n_start, int max_iter, double tol, bool update_init, int h,
-               const dfm_ss_em_out &out, dfm_ss_em_info *info) {
+               const dfm_ss_em_out &out, dfm_ss_em_info *info, const dfm_ss_mf *mf = nullptr, int p_var = 0) {
+  // mf: the mixed-frequency model (checked): the starts are then the padded state's (p = max(p_var, n_w), A = [A 0]),
+  // p_var the VAR's own lag count (out.A is r x r p_var); null: the plain model
   if (ss_em_check_args(X != nullptr, M, T64, N64, ldx, stride, starts != nullptr, n_start))
     return fail(ctx, -2, "%s: bad arguments (T >= 2, n_start 1 or M)", who);
   if (M == 0) return 0;
@@ -905,11 +1016,11 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
   if (!dev && ss_em_empty_column(X, M, T64, N64, ldx, stride, &ep, &ec))
     return fail(ctx, -2, "%s: panel %lld: column %lld (0-based) has no observed entry", who, (long long)ep, (long long)ec);
   if (T64 + h > (1 << 24) || M > (1 << 30)) return fail(ctx, -2, "panel too large");
-  const int T = (int)T64, N = (int)N64, s = r * p, ss = s * s, Tt = T + h;
-  const int ncols = ss_ncols(r), nct = (ncols + 63) / 64, NCP = nct * 64, Npad = (N + 15) & ~15;
+  const int T = (int)T64, N = (int)N64, s = r * p, ss = s * s, Tt = T + h, rp = mf ? r * p_var : s;
+  const int cq = (mf ? 2 : 1) * (r * (r + 1) / 2 + r);
+  const int ncols = mf ? cq + 4 : ss_ncols(r), nct = (ncols + 63) / 64, NCP = nct * 64, Npad = (N + 15) & ~15;
   const int nrt = (T + 63) / 64, Tpad = nrt * 64, KS = (Npad + SS_KC - 1) / SS_KC;
   const int nrn = (N + 63) / 64, Nr = nrn * 64, KT = (((T + 15) & ~15) + SS_KC - 1) / SS_KC;
-  const int cq = r * (r + 1) / 2 + r;
   const SsBlock B = ss_block(N, r, s, NCP);
   const size_t blk = (size_t)B.stride, tail = blk - (size_t)B.oTm;
   // ---- the starts' blocks
@@ -917,27 +1028,43 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
   for (int64_t k = 0; k < n_start; ++k) {
     const dfm_ss_params &q = starts[k];
     const SsParams pr{q.r, q.p, q.lambda, q.sigma2, q.A, q.Q, q.a0, q.P0};
-    if (int rc = ss_fill_block(pr, N, NCP, B, &hp[(size_t)k * blk])) return ss_param_error(ctx, who, rc, -1);
+    if (int rc = ss_fill_block(pr, N, NCP, B, &hp[(size_t)k * blk], mf ? mf->low : nullptr))
+      return ss_param_error(ctx, who, rc, -1);
   }
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
+  StreamBuf dmf;   // mixed frequency: the weights, then the mask
+  const double *dw = nullptr;
+  const uint8_t *dlow = nullptr;
+  if (mf) {
+    HIPCHK(ctx, dmf.alloc(SS_WMAX * 8 + (size_t)N, st));
+    double hw[SS_WMAX] = {0.0};
+    std::copy(mf->w, mf->w + mf->n_w, hw);
+    dw = (const double *)dmf.p;
+    dlow = (const uint8_t *)dmf.p + SS_WMAX * 8;
+    HIPCHK(ctx, hipMemcpyAsync(dmf.p, hw, sizeof hw, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync((void *)dlow, mf->low, (size_t)N, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // hw leaves scope
+  }
   // ---- panels per pass: the half-GB rule of the smoother over everything a panel keeps on the device
   const size_t per_part = (size_t)KS * Tpad * NCP, per_ws = (size_t)Tt * (2 * (size_t)s + 2 * (size_t)ss),
                per_pm = (size_t)KT * Nr * NCP, per_op = (size_t)T * NCP, per_filt = (size_t)T * r,
-               per_sm = (size_t)Tt * r, per_cov = (size_t)Tt * r * r;
-  const size_t per = (per_part + per_ws + per_pm + per_op + per_filt + per_sm + per_cov + SS_MOM + blk + 2) * 8 +
+               per_sm = (size_t)Tt * r, per_cov = (size_t)Tt * r * r, per_agg = mf ? per_sm : 0;
+  const size_t per = (per_part + per_ws + per_pm + per_op + per_filt + per_sm + per_cov + per_agg + SS_MOM + blk + 2) * 8 +
                      ((size_t)N + 4) * 4;
   const int64_t mb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, 65535), (int64_t)(((size_t)1 << 29) / per)));
   StreamBuf dpar, dwork, dx, dint;
   HIPCHK(ctx, dpar.alloc((size_t)mb * blk * 8, st));
-  HIPCHK(ctx, dwork.alloc((size_t)mb * (per_part + per_ws + per_pm + per_op + per_filt + per_sm + per_cov + SS_MOM + 2) * 8, st));
+  HIPCHK(ctx, dwork.alloc((size_t)mb * (per_part + per_ws + per_pm + per_op + per_filt + per_sm + per_cov + per_agg + SS_MOM + 2) * 8,
+                          st));
   HIPCHK(ctx, dint.alloc((size_t)mb * ((size_t)N + 4) * 4, st));
   const int64_t span_max = (mb - 1) * stride + ldx * (int64_t)(N - 1) + T;
   if (!dev) HIPCHK(ctx, dx.alloc((size_t)span_max * 8, st));
   double *dp = (double *)dpar.p, *part = (double *)dwork.p, *ws = part + (size_t)mb * per_part,
          *pm = ws + (size_t)mb * per_ws, *opnd = pm + (size_t)mb * per_pm, *dfilt = opnd + (size_t)mb * per_op,
          *dsm = dfilt + (size_t)mb * per_filt, *dcov = dsm + (size_t)mb * per_sm, *mom = dcov + (size_t)mb * per_cov,
-         *dll = mom + (size_t)mb * SS_MOM, *dn = dll + mb;   // dll, dn adjacent: one read-back
+         *dll = mom + (size_t)mb * SS_MOM, *dn = dll + mb,   // dll, dn adjacent: one read-back
+         *dagg = dn + mb;
   int *eflag = (int *)dint.p, *mflag = eflag + mb, *mcol = mflag + mb, *dact = mcol + mb, *status = dact + mb;
   const size_t path_ld = (size_t)max_iter + 1;
   std::vector<double> hll((size_t)2 * mb), prev((size_t)mb), htail;
@@ -986,9 +1113,14 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
       {
         Scope sc(ctx, DFM_KC_MISC);
         SsArgs g{T, Tt, r, s, ncols, KS, Tpad, NCP, part, dp + B.oTm, dp + B.oQ, dp + B.oa0, dp + B.oP0, B.stride, dact,
-                 ws, dfilt, dsm, dcov, dll, dn, eflag, opnd, mom};
-        hipLaunchKernelGGL(ss_filter_kernel, dim3((unsigned)n), dim3(256), 0, st, g);
-        hipLaunchKernelGGL(ss_smoother_kernel<true>, dim3((unsigned)n), dim3(256), 0, st, g);
+                 ws, dfilt, dsm, dcov, dll, dn, eflag, opnd, mom, mf ? mf->n_w : 0, dw, mf ? dagg : nullptr};
+        if (mf) {
+          hipLaunchKernelGGL(ss_filter_kernel<true>, dim3((unsigned)n), dim3(256), 0, st, g);
+          hipLaunchKernelGGL((ss_smoother_kernel<true, true>), dim3((unsigned)n), dim3(256), 0, st, g);
+        } else {
+          hipLaunchKernelGGL(ss_filter_kernel<false>, dim3((unsigned)n), dim3(256), 0, st, g);
+          hipLaunchKernelGGL((ss_smoother_kernel<true, false>), dim3((unsigned)n), dim3(256), 0, st, g);
+        }
       }
       HIPCHK(ctx, hipGetLastError());
       HIPCHK(ctx, hipMemcpyAsync(hll.data(), dll, (size_t)mb * 8, hipMemcpyDeviceToHost, st));
@@ -1024,16 +1156,18 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
       HIPCHK(ctx, hipMemcpyAsync(dact, act.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
       {
         Scope sc(ctx, DFM_KC_GEMM);
-        hipLaunchKernelGGL(ss_mstep_kernel, dim3(nrn, nct * KT, (unsigned)n), dim3(256), 0, st, src, ldx, stride, T, N,
-                           (const double *)opnd, (const int *)dact, r, NCP, nct, KT, pm);
+        hipLaunchKernelGGL(mf ? ss_mstep_kernel<true> : ss_mstep_kernel<false>, dim3(nrn, nct * KT, (unsigned)n), dim3(256), 0,
+                           st, src, ldx, stride, T, N, (const double *)opnd, (const int *)dact, r, NCP, nct, KT, pm);
       }
       HIPCHK(ctx, hipGetLastError());
       {
         Scope sc(ctx, DFM_KC_OLS);
-        hipLaunchKernelGGL(ss_loadings_kernel, dim3((N + SS_LB - 1) / SS_LB, (unsigned)n), dim3(SS_LB), 0, st,
-                           (const double *)pm, N, Nr, r, NCP, KT, (const int *)dact, B, dp, status);
-        hipLaunchKernelGGL(ss_transition_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double *)mom, T, N, r, s,
-                           update_init ? 1 : 0, (const int *)dact, B, dp, (const int *)status, mflag, mcol);
+        hipLaunchKernelGGL(mf ? ss_loadings_kernel<true> : ss_loadings_kernel<false>,
+                           dim3((N + SS_LB - 1) / SS_LB, (unsigned)n), dim3(SS_LB), 0, st, (const double *)pm, N, Nr, r, NCP,
+                           KT, (const int *)dact, B, dp, status, dlow);
+        hipLaunchKernelGGL(mf ? ss_transition_kernel<true> : ss_transition_kernel<false>, dim3((unsigned)n), dim3(256), 0,
+                           st, (const double *)mom, T, N, r, s, rp, update_init ? 1 : 0, (const int *)dact, B, dp,
+                           (const int *)status, mflag, mcol);
       }
       HIPCHK(ctx, hipGetLastError());
     }
@@ -1044,6 +1178,8 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
       HIPCHK(ctx, hipMemcpyAsync(out.smoothed + c0 * per_sm, dsm, (size_t)n * per_sm * 8, hipMemcpyDeviceToHost, st));
     if (out.smoothed_cov)
       HIPCHK(ctx, hipMemcpyAsync(out.smoothed_cov + c0 * per_cov, dcov, (size_t)n * per_cov * 8, hipMemcpyDeviceToHost, st));
+    if (mf && out.smoothed_agg)
+      HIPCHK(ctx, hipMemcpyAsync(out.smoothed_agg + c0 * per_sm, dagg, (size_t)n * per_sm * 8, hipMemcpyDeviceToHost, st));
     htail.resize((size_t)n * tail);
     HIPCHK(ctx, hipMemcpy2DAsync(htail.data(), tail * 8, dp + B.oTm, blk * 8, tail * 8, (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(hll.data(), dll, (size_t)2 * mb * 8, hipMemcpyDeviceToHost, st));
@@ -1053,8 +1189,8 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
       auto t = [&](int64_t off) { return tl + (off - B.oTm); };   // the block's offsets, over its tail
       const size_t g = (size_t)(c0 + i);
       if (out.A)
-        for (int k = 0; k < s; ++k)
-          for (int a = 0; a < r; ++a) out.A[g * r * s + (size_t)k * r + a] = t(B.oTm)[a * s + k];
+        for (int k = 0; k < rp; ++k)
+          for (int a = 0; a < r; ++a) out.A[g * r * rp + (size_t)k * r + a] = t(B.oTm)[a * s + k];
       if (out.Q)
         for (int a = 0; a < r; ++a)
           for (int c = 0; c < r; ++c) out.Q[g * r * r + (size_t)c * r + a] = t(B.oQ)[a * r + c];
@@ -1073,7 +1209,7 @@ int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_
 
 int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                 int horizon, dfm_em_info *info, const dfm_ss_fit_out *out, const dfm_ss_em_spec *ml, double *a0_out,
-                double *loglik_path, dfm_ss_em_info *ml_info);
+                double *loglik_path, dfm_ss_em_info *ml_info, const dfm_ss_mf *mf = nullptr, double *agg_out = nullptr);
 
 }  // namespace
 
@@ -1101,6 +1237,31 @@ int dfm_ss_smooth(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N
                         smoothed_cov, loglik, n_observed);
 }
 
+int dfm_ss_smooth_mf(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                     const dfm_ss_params *params, const dfm_ss_mf *mf, const dfm_ss_spec *spec, double *filtered,
+                     double *smoothed, double *smoothed_cov, double *loglik, int64_t *n_observed,
+                     double *smoothed_agg) {
+  if (!ctx) return -1;
+  if (!params || !spec || !mf || N < 1) return fail(ctx, -2, "dfm_ss_smooth_mf: bad arguments");
+  if (!mf->low) return fail(ctx, -2, "dfm_ss_smooth_mf: the mask of low-frequency series is missing");
+  if (!ss_mf_any_low(mf->low, N))
+    return dfm_ss_smooth(ctx, X, M, T, N, ldx, stride, params, spec, filtered, smoothed, smoothed_cov, loglik, n_observed);
+  const int r = params->r, p = params->p;
+  const int rc = ss_mf_check(r, p, mf->n_w, mf->w, mf->low);
+  if (rc == SS_E_LIMIT)
+    return fail(ctx, rc, "dfm_ss_smooth_mf: the mixed-frequency pass serves 1 <= r <= 16, 1 <= p <= 8, 1 <= n_w <= 8, "
+                "r max(p, n_w) <= 32");
+  if (rc) return fail(ctx, rc, "dfm_ss_smooth_mf: the weights must be finite with w_0 != 0, and r, p, n_w >= 1");
+  if (!params->A) return fail(ctx, -2, "dfm_ss_smooth_mf: bad arguments");
+  const int L = ss_mf_lags(p, mf->n_w);
+  std::vector<double> Apad((size_t)r * r * L);
+  ss_mf_pad_A(params->A, r, p, L, Apad.data());
+  DeviceShare gate(ctx->device);
+  const SsParams pr{r, L, params->lambda, params->sigma2, Apad.data(), params->Q, params->a0, params->P0};
+  return ss_smooth_core(ctx, X, M, T, N, ldx, stride, spec->dev != 0, pr, spec->horizon, filtered, smoothed,
+                        smoothed_cov, loglik, n_observed, mf, smoothed_agg);
+}
+
 int dfm_ss_estimate(dfm_ctx *ctx, const double *Zm, int64_t T, int64_t N, int64_t ldx, const double *F, const double *L,
                     int r, int p, double *sigma_out, double *A_out, double *Q_out, double *P0_out) {
   if (!ctx) return -1;
@@ -1122,6 +1283,38 @@ int dfm_ss_em(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, in
                     spec->horizon, *out, info);
 }
 
+int dfm_ss_em_mf(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                 const dfm_ss_params *starts, int64_t n_start, const dfm_ss_mf *mf, const dfm_ss_em_spec *spec,
+                 const dfm_ss_em_out *out, dfm_ss_em_info *info) {
+  if (!ctx) return -1;
+  if (!mf || N < 1) return fail(ctx, -2, "dfm_ss_em_mf: bad arguments");
+  if (!mf->low) return fail(ctx, -2, "dfm_ss_em_mf: the mask of low-frequency series is missing");
+  if (!ss_mf_any_low(mf->low, N)) return dfm_ss_em(ctx, X, M, T, N, ldx, stride, starts, n_start, spec, out, info);
+  int max_iter = 0;
+  double tol = 0.0;
+  if (!spec || !out || !starts || n_start < 1 || ss_em_defaults(spec->max_iter, spec->tol, spec->horizon, &max_iter, &tol))
+    return fail(ctx, -2, "dfm_ss_em_mf: bad arguments");
+  const int r = starts[0].r, p = starts[0].p;
+  const int rc = ss_mf_check(r, p, mf->n_w, mf->w, mf->low);
+  if (rc == SS_E_LIMIT)
+    return fail(ctx, rc, "dfm_ss_em_mf: the mixed-frequency pass serves 1 <= r <= 16, 1 <= p <= 8, 1 <= n_w <= 8, "
+                "r max(p, n_w) <= 32");
+  if (rc) return fail(ctx, rc, "dfm_ss_em_mf: the weights must be finite with w_0 != 0, and r, p, n_w >= 1");
+  const int L = ss_mf_lags(p, mf->n_w);
+  std::vector<dfm_ss_params> padded(starts, starts + n_start);
+  std::vector<double> Apad((size_t)n_start * r * r * L);
+  for (int64_t k = 0; k < n_start; ++k) {
+    if (starts[k].r != r || starts[k].p != p || !starts[k].A)
+      return fail(ctx, -2, "dfm_ss_em_mf: start %lld has another (r, p)", (long long)k);
+    ss_mf_pad_A(starts[k].A, r, p, L, &Apad[(size_t)k * r * r * L]);
+    padded[k].p = L;
+    padded[k].A = &Apad[(size_t)k * r * r * L];
+  }
+  DeviceShare gate(ctx->device);
+  return ss_em_core(ctx, "dfm_ss_em_mf", X, M, T, N, ldx, stride, spec->dev != 0, padded.data(), n_start, max_iter, tol,
+                    spec->update_init != 0, spec->horizon, *out, info, mf, p);
+}
+
 int dfm_ss_fit(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                int horizon, dfm_em_info *info, const dfm_ss_fit_out *out) {
   if (!ctx) return -1;
@@ -1136,15 +1329,37 @@ int dfm_ss_fit_ml(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t l
   return ss_fit_impl(ctx, "dfm_ss_fit_ml", X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out, ml_spec, a0_out, loglik_path, ml_info);
 }
 
+int dfm_ss_fit_mf(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+                  const dfm_ss_em_spec *ml_spec, const dfm_ss_mf *mf, int method, dfm_em_info *info,
+                  const dfm_ss_fit_out *out, double *a0_out, double *loglik_path, dfm_ss_em_info *ml_info,
+                  double *smoothed_agg) {
+  if (!ctx) return -1;
+  if (!ml_spec || !mf || N < 1 || (method != 0 && method != 1)) return fail(ctx, -2, "dfm_ss_fit_mf: bad arguments");
+  if (!mf->low) return fail(ctx, -2, "dfm_ss_fit_mf: the mask of low-frequency series is missing");
+  if (!ss_mf_any_low(mf->low, N))
+    return method ? dfm_ss_fit_ml(ctx, X, T, N, ldx, em_spec, p, ml_spec, info, out, a0_out, loglik_path, ml_info)
+                  : dfm_ss_fit(ctx, X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out);
+  // r may be selected by the fit: the limits are checked again once it is known
+  const int rc = ss_mf_check(em_spec && em_spec->r > 0 ? em_spec->r : 1, p, mf->n_w, mf->w, mf->low);
+  if (rc == SS_E_LIMIT)
+    return fail(ctx, rc, "dfm_ss_fit_mf: the mixed-frequency pass serves 1 <= r <= 16, 1 <= p <= 8, 1 <= n_w <= 8, "
+                "r max(p, n_w) <= 32");
+  if (rc) return fail(ctx, rc, "dfm_ss_fit_mf: the weights must be finite with w_0 != 0, and p, n_w >= 1");
+  return ss_fit_impl(ctx, "dfm_ss_fit_mf", X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out, method ? ml_spec : nullptr,
+                     a0_out, loglik_path, ml_info, mf, smoothed_agg);
+}
+
 }  // extern "C"
 
 namespace {
 
 // dfm_ss_fit, and with `ml` dfm_ss_fit_ml: the EM from the two-step parameters
 // takes the place of step 5's smoother.
+// mf (with a marked series): dfm_ss_fit_mf — the low series' start values by
+// ss_mf_start, the padded state, and Lambda ft_t|T for the low columns.
 int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                 int horizon, dfm_em_info *info, const dfm_ss_fit_out *out, const dfm_ss_em_spec *ml, double *a0_out,
-                double *loglik_path, dfm_ss_em_info *ml_info) {
+                double *loglik_path, dfm_ss_em_info *ml_info, const dfm_ss_mf *mf, double *agg_out) {
   if (!X || !em_spec || !out || T < 2 || N < 1 || ldx < T || horizon < 0)
     return fail(ctx, -2, "%s: bad arguments", who);
   int ml_iter = 0;
@@ -1152,7 +1367,8 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
   if (ml && ss_em_defaults(ml->max_iter, ml->tol, ml->horizon, &ml_iter, &ml_tol))
     return fail(ctx, -2, "%s: bad arguments", who);
   if (p < 1 || p > SS_PMAX) return ss_param_error(ctx, who, p < 1 ? -2 : SS_E_LIMIT, -1);
-  if (em_spec->r > SS_RMAX || (em_spec->r > 0 && em_spec->r * p > SS_SMAX))
+  const int Lg = mf ? ss_mf_lags(p, mf->n_w) : p;   // lags of the state
+  if (em_spec->r > SS_RMAX || (em_spec->r > 0 && em_spec->r * Lg > SS_SMAX))
     return ss_param_error(ctx, who, SS_E_LIMIT, -1);
   DeviceShare gate(ctx->device);
   const size_t tn = (size_t)T * N;
@@ -1162,8 +1378,8 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
   int rc = dfm_em(ctx, X, T, N, ldx, em_spec, Z.data(), out->em_completed, mu.data(), sd.data(), F.data(), L.data(),
                   ev.data(), &inf);
   if (rc) return rc;
-  const int r = inf.r, s = r * p, h = horizon;
-  if ((rc = ss_check_dims(r, p))) return ss_param_error(ctx, who, rc, -1);
+  const int r = inf.r, s = r * p, sp = r * Lg, h = horizon;   // s: the VAR's columns; sp: the state
+  if ((rc = ss_check_dims(r, Lg))) return ss_param_error(ctx, who, rc, -1);
   const double *Xs = X;   // the raw panel on the host: its NaN pattern is the mask
   int64_t lds = ldx;
   if (em_spec->dev) {
@@ -1184,21 +1400,34 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
   rc = ss_estimate(Zm.data(), T, N, T, F.data(), L.data(), r, p, sig.data(), A.data(), Q.data(), P0.data(), &where);
   if (rc) return ss_param_error(ctx, who, rc, where);
   const int64_t Tt = T + h;
-  std::vector<double> sm((size_t)Tt * r);
+  std::vector<double> sm((size_t)Tt * r), agg, Apad;
+  if (mf) {
+    rc = ss_mf_start(Zm.data(), T, N, T, F.data(), r, mf->w, mf->n_w, mf->low, L.data(), sig.data(), &where);
+    if (rc == SS_E_VAR)
+      return fail(ctx, rc, "%s: low-frequency column %lld (0-based) has fewer than r + 1 observed rows t >= n_w - 1", who,
+                  (long long)where);
+    if (rc) return ss_param_error(ctx, who, rc, where);
+    agg.resize((size_t)Tt * r);
+    Apad.resize((size_t)r * sp);
+    ss_mf_pad_A(A.data(), r, p, Lg, Apad.data());
+    P0.resize((size_t)sp * sp);
+    if ((rc = ss_stationary_cov(Apad.data(), Q.data(), r, Lg, P0.data()))) return ss_param_error(ctx, who, rc, -1);
+  }
+  const double *As = mf ? Apad.data() : A.data();   // the state's A
   if (!ml) {
-    const SsParams pr{r, p, L.data(), sig.data(), A.data(), Q.data(), nullptr, P0.data()};
+    const SsParams pr{r, Lg, L.data(), sig.data(), As, Q.data(), nullptr, P0.data()};
     rc = ss_smooth_core(ctx, Zm.data(), 1, T, N, T, (int64_t)tn, false, pr, h, out->filtered, sm.data(),
-                        out->smoothed_cov, out->loglik, nullptr);
+                        out->smoothed_cov, out->loglik, nullptr, mf, mf ? agg.data() : nullptr);
     if (rc) return rc;
   } else {
-    const dfm_ss_params start{r, p, L.data(), sig.data(), A.data(), Q.data(), nullptr, P0.data()};
-    std::vector<double> L2((size_t)N * r), sig2((size_t)N), A2((size_t)r * s), Q2((size_t)r * r), a02((size_t)s),
-        P02((size_t)s * s);
+    const dfm_ss_params start{r, Lg, L.data(), sig.data(), As, Q.data(), nullptr, P0.data()};
+    std::vector<double> L2((size_t)N * r), sig2((size_t)N), A2((size_t)r * s), Q2((size_t)r * r), a02((size_t)sp),
+        P02((size_t)sp * sp);
     const dfm_ss_em_out eo{L2.data(), sig2.data(), A2.data(), Q2.data(), a02.data(), P02.data(), out->filtered,
-                           sm.data(), out->smoothed_cov, nullptr, loglik_path};
+                           sm.data(), out->smoothed_cov, nullptr, loglik_path, mf ? agg.data() : nullptr};
     dfm_ss_em_info mi{};
     rc = ss_em_core(ctx, who, Zm.data(), 1, T, N, T, (int64_t)tn, false, &start, 1, ml_iter, ml_tol, ml->update_init != 0, h,
-                    eo, &mi);
+                    eo, &mi, mf, p);
     if (rc) return rc;
     L = L2, sig = sig2, A = A2, Q = Q2, P0 = P02;
     if (out->loglik) *out->loglik = mi.loglik;
@@ -1217,12 +1446,15 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
   put(out->sigma2, sig, (size_t)N);
   put(out->A, A, (size_t)r * s);
   put(out->Q, Q, (size_t)r * r);
-  put(out->P0, P0, (size_t)s * s);
+  put(out->P0, P0, (size_t)sp * sp);
   put(out->smoothed, sm, (size_t)Tt * r);
-  // the common component of the smoothed factors, Lambda f_t|T (the fma chain of the EM's)
+  if (mf && agg_out) std::copy(agg.begin(), agg.end(), agg_out);
+  // the common component of the smoothed factors, Lambda f_t|T (the fma chain of the EM's); a low-frequency
+  // column's is Lambda ft_t|T
   auto common = [&](int64_t t, int64_t i) {
+    const double *f = mf && mf->low[i] ? agg.data() : sm.data();
     double c = 0.0;
-    for (int j = 0; j < r; ++j) c = fma(sm[(size_t)t * r + j], L[(size_t)j * N + i], c);
+    for (int j = 0; j < r; ++j) c = fma(f[(size_t)t * r + j], L[(size_t)j * N + i], c);
     return c;
   };
   if (out->x_smoothed || out->x_completed)

@@ -2,7 +2,9 @@
 // the limits, the companion form of a VAR(p), the stationary covariance by the
 // doubling iteration, the argument checks of the smoother's parameters and
 // steps 2-3 of the two-step fit (idiosyncratic variances, VAR(p) by OLS), and
-// of the quasi-ML EM the spec's defaults, the stopping rule and the checks.
+// of the quasi-ML EM the spec's defaults, the stopping rule and the checks;
+// of the mixed-frequency model the limits, [A 0], Z_l and the fit's start
+// values of the low series.
 // No HIP includes: a plain C++ compiler builds it alone (tests/c_harness).
 //
 // Layout: every matrix the caller passes is column-major (include/dfm.h);
@@ -224,6 +226,104 @@ inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
     }
   if (!ss_cholesky(Qc.data(), r)) return SS_E_SINGULAR;
   return ss_stationary_cov(A, Q, r, p, P0);
+}
+
+// ------------------------------------------- mixed frequency (dfm_ss_smooth_mf)
+// A low-frequency series loads on sum_k w_k f_{t-k}, k < n_w: the state keeps
+// L = max(p, n_w) lags of the factors, s = r L.
+constexpr int SS_WMAX = 8;
+
+inline int ss_mf_lags(int p, int n_w) { return p > n_w ? p : n_w; }
+
+// The limits at the padded state, then the weights (finite, w_0 != 0) and the mask.
+inline int ss_mf_check(int r, int p, int n_w, const double *w, const uint8_t *low) {
+  if (n_w < 1 || p < 1) return -2;
+  if (n_w > SS_WMAX) return SS_E_LIMIT;
+  const int rc = ss_check_dims(r, ss_mf_lags(p, n_w));
+  if (rc) return rc;
+  if (!w || !low) return -2;
+  for (int k = 0; k < n_w; ++k)
+    if (!isfinite(w[k])) return -2;
+  return w[0] != 0.0 ? 0 : -2;
+}
+
+inline bool ss_mf_any_low(const uint8_t *low, int64_t N) {
+  for (int64_t i = 0; i < N; ++i)
+    if (low[i]) return true;
+  return false;
+}
+
+// [A 0]: A (r x rp column-major) followed by r (L - p) zero columns.  Its
+// companion matrix (ss_companion at p = L) is the padded one: [A 0] in the
+// first r rows, the identity shift below.
+inline void ss_mf_pad_A(const double *A, int r, int p, int L, double *Apad) {
+  for (int e = 0; e < r * r * L; ++e) Apad[e] = e < r * r * p ? A[e] : 0.0;
+}
+
+// Z_l = [w_0 I_r ... w_{n_w-1} I_r 0 ...], r x s row-major.
+inline void ss_mf_zl(const double *w, int n_w, int r, int s, double *Zl) {
+  for (int e = 0; e < r * s; ++e) Zl[e] = 0.0;
+  for (int k = 0; k < n_w; ++k)
+    for (int i = 0; i < r; ++i) Zl[i * s + k * r + i] = w[k];
+}
+
+// Start values of the low-frequency series for the fit: lambda_i, sigma^2_i by
+// OLS of Zm_ti on ft_t = sum_k w_k F[t-k] over the observed rows t >= n_w - 1,
+// sigma^2_i = the residual sum of squares over their count.  Zm: T x N
+// column-major (ldz), F: T x r, L: N x r column-major; L and sigma2 are
+// rewritten for the marked series only.  SS_E_VAR with fewer than r + 1 such
+// rows or a singular ft'ft, SS_E_SIGMA for a non-positive variance; *where
+// names the column.
+inline int ss_mf_start(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, int r, const double *w,
+                       int n_w, const uint8_t *low, double *L, double *sigma2, int64_t *where) {
+  if (!Zm || !F || !w || !low || !L || !sigma2 || r < 1 || r > SS_RMAX || n_w < 1 || n_w > SS_WMAX || T < 1 || ldz < T)
+    return -2;
+  std::vector<double> ft((size_t)T * r, 0.0), G((size_t)r * r), g((size_t)r);
+  for (int64_t t = n_w - 1; t < T; ++t)
+    for (int j = 0; j < r; ++j) {
+      double v = 0.0;
+      for (int k = 0; k < n_w; ++k) v = fma(w[k], F[(size_t)j * T + t - k], v);
+      ft[(size_t)t * r + j] = v;
+    }
+  for (int64_t i = 0; i < N; ++i) {
+    if (!low[i]) continue;
+    if (where) *where = i;
+    const double *z = Zm + (size_t)i * ldz;
+    std::fill(G.begin(), G.end(), 0.0);
+    std::fill(g.begin(), g.end(), 0.0);
+    int64_t n = 0;
+    for (int64_t t = n_w - 1; t < T; ++t) {
+      if (isnan(z[t])) continue;
+      ++n;
+      for (int a = 0; a < r; ++a) {
+        g[a] += ft[(size_t)t * r + a] * z[t];
+        for (int b = 0; b <= a; ++b) G[a * r + b] += ft[(size_t)t * r + a] * ft[(size_t)t * r + b];
+      }
+    }
+    if (n < r + 1 || !ss_cholesky(G.data(), r)) return SS_E_VAR;
+    for (int a = 0; a < r; ++a) {
+      double v = g[a];
+      for (int k = 0; k < a; ++k) v -= G[a * r + k] * g[k];
+      g[a] = v / G[a * r + a];
+    }
+    for (int a = r - 1; a >= 0; --a) {
+      double v = g[a];
+      for (int k = a + 1; k < r; ++k) v -= G[k * r + a] * g[k];
+      g[a] = v / G[a * r + a];
+    }
+    double rss = 0.0;
+    for (int64_t t = n_w - 1; t < T; ++t) {
+      if (isnan(z[t])) continue;
+      double c = 0.0;
+      for (int a = 0; a < r; ++a) c = fma(ft[(size_t)t * r + a], g[a], c);
+      rss += (z[t] - c) * (z[t] - c);
+    }
+    const double v = rss / (double)n;
+    if (!(v > 0.0) || isinf(v)) return SS_E_SIGMA;
+    for (int a = 0; a < r; ++a) L[(size_t)a * N + i] = g[a];
+    sigma2[i] = v;
+  }
+  return 0;
 }
 
 // ------------------------------------------------ the quasi-ML EM (dfm_ss_em)

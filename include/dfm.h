@@ -526,6 +526,49 @@ int dfm_ss_smooth(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N
                   const dfm_ss_params *params, const dfm_ss_spec *spec, double *filtered, double *smoothed,
                   double *smoothed_cov, double *loglik, int64_t *n_observed);
 
+/* Mixed frequency (Mariano & Murasawa 2003; Banbura & Modugno 2014): series
+ * sampled at a lower frequency than the state load on a within-period
+ * aggregate of the factors.
+ *   low_i in {0,1} per series; weights w_0..w_{n_w-1}, 1 <= n_w <= 8, finite, w_0 != 0
+ *   x_ti = lambda_i' f_t  + e_ti   (low_i = 0)
+ *   x_ti = lambda_i' ft_t + e_ti   (low_i = 1),  ft_t = sum_{k<n_w} w_k f_{t-k}
+ *   f_t as above: VAR(p), A r x rp, Q r x r
+ *   state alpha_t = (f_t, ..., f_{t-L+1}), L = max(p, n_w), s = r L; the
+ *   companion matrix holds [A 0] in its first r rows and the shift below; a0
+ *   has s entries and P0 is s x s; a NULL P0 is the stationary covariance of
+ *   this padded companion form (the same doubling iteration).
+ * Limits: 1 <= r <= 16, 1 <= p <= 8, 1 <= n_w <= 8, r max(p, n_w) <= 32 (-7
+ * beyond); a non-finite weight, w_0 = 0 or a NULL `low` is -2.
+ * A quarterly flow observed in the last month of its quarter (NaN in the
+ * other two) takes w = (1, 2, 3, 2, 1) for monthly growth rates, a quarterly
+ * mean w = (1/3, 1/3, 1/3).
+ *
+ * The errors are independent across series, so a row is two exact updates of
+ * the recursion above, one per class c in the order (high, low), each on the
+ * collapsed moments C^c_t, b^c_t of its own series only and skipped when
+ * n^c_t = 0.  With Z_h = [I_r 0 ...], Z_l = [w_0 I_r ... w_{n_w-1} I_r 0 ...]:
+ *   PZ = P Z_c',  V = Z_c PZ,  z = Z_c a,  G = I_r + C^c_t V
+ *   K = PZ G^-1;  d = b^c_t - C^c_t z;  a <- a + K d
+ *   P <- P - K C^c_t PZ', then P <- (P + P') / 2
+ *   loglik -= 1/2 [ n^c_t log 2 pi + l^c_t + log det G + q^c_t - 2 b^c_t'z
+ *                   + z' C^c_t z - d' V G^-1 d ]   (z, V from before the class's update)
+ * The prediction step and the backward pass are unchanged at the padded state. */
+typedef struct dfm_ss_mf {
+  int32_t n_w;
+  const double *w;        /* n_w aggregation weights */
+  const uint8_t *low;     /* N: != 0 marks a low-frequency series */
+} dfm_ss_mf;
+
+/* dfm_ss_smooth of the mixed-frequency model: params->A is r x rp, params->a0
+ * (s) and params->P0 (s x s) are those of the padded state.  smoothed_agg:
+ * M x (T+h) x r row-major, ft_t|T = Z_l a_t|T (NULL: not wanted).  When no
+ * series is marked low the call is dfm_ss_smooth bit for bit: w is ignored,
+ * the state is the plain one (s = r p) and smoothed_agg is not written. */
+int dfm_ss_smooth_mf(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                     const dfm_ss_params *params, const dfm_ss_mf *mf, const dfm_ss_spec *spec, double *filtered,
+                     double *smoothed, double *smoothed_cov, double *loglik, int64_t *n_observed,
+                     double *smoothed_agg);
+
 /* Steps 2-4 of the two-step fit.  Zm: T x N column-major (ldx >= T), NaN =
  * missing; F: T x r, L: N x r column-major.  Outputs column-major: sigma_out
  * (N), A_out (r x rp), Q_out (r x r), P0_out (s x s).  Host arithmetic (the
@@ -612,12 +655,30 @@ typedef struct dfm_ss_em_out {
   double *filtered, *smoothed, *smoothed_cov;
   int64_t *n_observed;
   double *loglik_path;
+  double *smoothed_agg;   /* dfm_ss_em_mf: M x (T+h) x r, Z_l a_t|T; dfm_ss_em does not read it */
 } dfm_ss_em_out;
 /* X as dfm_ss_smooth.  starts: n_start = 1 (shared by all panels) or M
  * dfm_ss_params of one (r, p).  info: M entries, or NULL. */
 int dfm_ss_em(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
               const dfm_ss_params *starts, int64_t n_start, const dfm_ss_em_spec *spec, const dfm_ss_em_out *out,
               dfm_ss_em_info *info);
+
+/* dfm_ss_em of the mixed-frequency model (dfm_ss_mf above; Banbura & Modugno
+ * 2014).  The starts' A is r x rp, their a0 (s) and P0 (s x s) those of the
+ * padded state, s = r max(p, n_w); the outputs likewise (A r x rp, a0, P0
+ * padded).  The E-step is dfm_ss_smooth_mf's.  The M-step differs in that the
+ * aggregation is built into each series' regressor:
+ *   S_i = sum_t m_ti Et^c(i)_t,  g_i = sum_t m_ti x_ti f^c(i)_t,
+ *   Et^c_t = Z_c (a_t|T a_t|T' + P_t|T) Z_c',  f^c_t = Z_c a_t|T  (c(i) the class of i)
+ *   lambda_i, sigma^2_i from them as above;
+ *   A = S10[:, :rp] (S00[:rp, :rp])^-1,  Q = (S11 - A S10[:, :rp]') / (T - 1),
+ *   symmetrised; the companion matrix's lags beyond p stay zero.
+ * The stopping rule, freezing, update_init, return codes and messages are
+ * dfm_ss_em's (-7 and -2 as dfm_ss_smooth_mf).  out->smoothed_agg is filled.
+ * When no series is marked low the call is dfm_ss_em bit for bit. */
+int dfm_ss_em_mf(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                 const dfm_ss_params *starts, int64_t n_start, const dfm_ss_mf *mf, const dfm_ss_em_spec *spec,
+                 const dfm_ss_em_out *out, dfm_ss_em_info *info);
 
 /* dfm_ss_fit, then dfm_ss_em (M = 1) on its Zm from its parameters (a0 = 0,
  * P0 the stationary covariance of the two-step VAR).  `out` is filled as by
@@ -628,6 +689,25 @@ int dfm_ss_em(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, in
 int dfm_ss_fit_ml(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                   const dfm_ss_em_spec *ml_spec, dfm_em_info *info, const dfm_ss_fit_out *out, double *a0_out,
                   double *loglik_path, dfm_ss_em_info *ml_info);
+
+/* dfm_ss_fit (method 0) or dfm_ss_fit_ml (method 1) of the mixed-frequency
+ * model.  dfm_em runs on the panel as given (a low series' empty months are
+ * ordinary NaN to it) and dfm_ss_estimate as in dfm_ss_fit; then for each low
+ * series lambda_i, sigma^2_i are re-estimated by OLS of Z_ti on ft_t = sum_k
+ * w_k F_{t-k} over its observed rows t >= n_w - 1 (sigma^2_i = the residual
+ * sum of squares over their count; -11 with fewer than r + 1 such rows, the
+ * message names the column), P0 is the stationary covariance of the padded
+ * companion form, and dfm_ss_smooth_mf / dfm_ss_em_mf take the place of the
+ * plain passes.  ml_spec is required: its horizon is the forecast horizon in
+ * both methods.  `out` as dfm_ss_fit_ml fills it, with P0 s x s at s = r
+ * max(p, n_w), and x_smoothed, x_completed and forecast from Lambda ft_t|T in
+ * the low columns; a0_out has s entries; smoothed_agg (T+h) x r row-major;
+ * each may be NULL.  When no series is marked low the call is dfm_ss_fit or
+ * dfm_ss_fit_ml bit for bit. */
+int dfm_ss_fit_mf(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+                  const dfm_ss_em_spec *ml_spec, const dfm_ss_mf *mf, int method, dfm_em_info *info,
+                  const dfm_ss_fit_out *out, double *a0_out, double *loglik_path, dfm_ss_em_info *ml_info,
+                  double *smoothed_agg);
 
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
