@@ -432,6 +432,9 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
     // rebuilds H: fact_ready is not copied)
     HIPCHK(ctx, hipMalloc((void **)&M->H32, (size_t)T * M->ldH * sizeof(float)));
     HIPCHK(ctx, launch_fact_h32(M->H, M->ldH, T, M->hd, M->H32, st));
+    // ... and its bf16 split for the same products as six bf16 terms (H32 stays for DFM_FACT_SPLIT=0)
+    HIPCHK(ctx, hipMalloc(&M->Hs, hsplit_bytes(T)));
+    HIPCHK(ctx, launch_fact_hsplit(M->H, M->ldH, T, M->hd, M->Hs, st));
     std::vector<double> hdh(T);
     HIPCHK(ctx, hipMemcpyAsync(hdh.data(), M->hd, (size_t)T * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -548,7 +551,7 @@ static int bootstrap_one(dfm_model *M, int kind, int64_t B, const int32_t *idx, 
     HIPCHK(ctx, dalloc(&pSig.p, (size_t)nb));
     if (spectrum_work(m, (int)nb) > 0) HIPCHK(ctx, dalloc(&pWk.p, (size_t)spectrum_work(m, (int)nb)));
   }
-  FactBase fb{T, r, M->ldH, M->F, M->EL, M->S, M->H, M->cF, M->hd, M->FtF, M->H32, M->hmax};
+  FactBase fb{T, r, M->ldH, M->F, M->EL, M->S, M->H, M->cF, M->hd, M->FtF, M->H32, M->hmax, M->Hs};
   for (int64_t b0 = 0; b0 < B; b0 += nb) {
     const int n = (int)std::min<int64_t>(nb, B - b0);
     PanelSrc src{M->Cp, M->Ep, idx + b0 * T, kind == DFM_BOOT_WILD ? eta + b0 * T : nullptr, M->ld, T};

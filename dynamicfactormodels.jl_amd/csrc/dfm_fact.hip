@@ -85,13 +85,14 @@ __global__ __launch_bounds__(64 * BW) void prep_a_kernel(FactBase fb, const doub
 // copied from apre (prep_a_kernel), a tile's Z chunk (16 rows x pz,
 // contiguous in the replicate-major layout) leaves through this wave's LDS
 // stage zst (16 pz doubles) as 16-B pieces instead of one 128-B-strided
-// element per lane, as float if z32, and the same rows go to pvr (PV) if set.
+// element per lane, as float if z32 == 1, as the three bf16 planes of
+// gemmh_zrm_split_kernel's Zs if z32 == 2, and the same rows go to pvr (PV) if set.
 // The staged store measured -3 % in prep and +0.3 % in ap2 / the last Horner
 // step (profiles/r06_c3_ab.txt item 13), so those store directly.
 struct PrepTail {   // PREP = true
   const double *apre;
   double *zst, *pvr;
-  bool z32;
+  int z32;
 };
 struct AccTail {   // PREP = false
   const dv4 *aacc;
@@ -173,7 +174,10 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
         for (int ct = 0; ct < NT; ++ct)
           if (16 * ct + li < pz) zst[16 * (16 * ct + li) + 4 * g + lk] = s0 + 4 * g + lk < T ? z[g][ct] : 0.0;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (src.z32) {   // the fp32 H.Z GEMM's operand: the same chunk indexing, float elements (round to nearest)
+      if (src.z32 == 2) {   // the bf16-split H.Z GEMM's operand: the chunk's 6 pz pieces (dfm_internal.h: Zs)
+        zsplit_store_chunk<P == 16>(zst, pz, lane, reinterpret_cast<char *>(Zc + (int64_t)rep * zrs) +
+                                                       (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz);
+      } else if (src.z32) {   // the fp32 H.Z GEMM's operand: the same chunk indexing, float elements (round to nearest)
         zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
         for (int e = lane; e < 4 * pz; e += 64)
           zc4[e] = zf4{(float)zst[4 * e], (float)zst[4 * e + 1], (float)zst[4 * e + 2], (float)zst[4 * e + 3]};
@@ -237,7 +241,8 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
                                                             double *__restrict__ Zc, int64_t ldz, int pz,
                                                             double *__restrict__ ab, const double *__restrict__ apre,
                                                             double *__restrict__ PV, double *__restrict__ FV, int z32) {
-  // z32: Z0 leaves as float (the first product runs in fp32); PV, FV, a, cc stay fp64
+  // z32: Z0 leaves as float (1: the first product runs in fp32) or as three bf16 planes (2: as six bf16 terms);
+  // PV, FV, a, cc stay fp64
   static_assert(64 * BW == 256, "the scans and the tree sum below are written for 256 threads");
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
@@ -350,7 +355,8 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
     {
       const int64_t zrs = zrm_stride(T, pz);
       const int npad = ((T + 15) & ~15) - T;
-      if (z32)
+      if (z32 == 2) {   // (the staged store writes the whole last chunk, its zero pad rows included)
+      } else if (z32)
         for (int e = tid; e < npad * pz; e += 256)
           reinterpret_cast<float *>(Zc)[zrm_ix(rep, T + e / pz, e % pz, pz, zrs)] = 0.0f;
       else
@@ -360,7 +366,7 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
     // (PV, FV: a warm solve without a first Rayleigh-Ritz step filters V0 = Q0 itself, so the middle Horner
     // steps' PV = P'D V0 is Z0 row by row and FV = F'V0 is a)
     zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, sred, ps,
-                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, z32 != 0});
+                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, z32});
     if (FV)
       for (int e = tid; e < 16 * P; e += 256) FV[(int64_t)rep * 16 * P + e] = apre[e];
   }
@@ -1298,7 +1304,9 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_pv_kernel(FactBase fb, EigWor
 // 64 pz-byte piece, fetched as 16-B pieces and transposed through the EL
 // stage) and is scaled by hscale = hmax on the way in, Z leaves as float Z32,
 // rounded to nearest; 2 = HZ32 in, fp64 Z out in the normal layout (the last
-// middle step, whose Z feeds the filter's fp64 product).  All arithmetic, a
+// middle step, whose Z feeds the filter's fp64 product); 3 = as 1 with Z
+// leaving as the three bf16 planes of gemmh_zrm_split_kernel's Zs (the
+// same doubles of the stage, split on the way out).  All arithmetic, a
 // and cc stay fp64 in every mode; cc is formed from the unrounded Z.
 //
 // NOPF (a warm solve that starts with the filter, eig_run_fact2_t; selected by
@@ -1375,6 +1383,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   double *sP = stgP[wave], *sE = stgE[wave];
   const int64_t zrs = zrm_stride(T, pz);
   for (int tile = wave; tile < ntile; tile += BW) {
+    // LP == 3: the lane number is re-read per tile, so the tile's lane-dependent addresses are formed here from one
+    // register and not carried through the loop as invariants (the split store below needs their registers: 128 VGPRs)
+    int lane_t = lane;
+    if constexpr (LP == 3) asm volatile("" : "+v"(lane_t));
+    const int lane = lane_t, li = lane & 15, lk = lane >> 4;
     const int t0 = tile * 16;
     const int nr = min(16, T - t0) * r;   // valid doubles of the tile's contiguous PF / EL range
     double hz[NT][4], pv[NT][4], e2v[4];
@@ -1531,7 +1544,8 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         if (c < pz) sP[16 * c + 4 * g + lk] = zv[ct][g];
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (LP == 1) {
+    if constexpr (LP == 3) {   // (split below, behind the tile's last MFMAs: their operands' registers are free there)
+    } else if constexpr (LP == 1) {
       zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
       for (int e = lane; e < 4 * pz; e += 64)
         zc4[e] = zf4{(float)sP[4 * e], (float)sP[4 * e + 1], (float)sP[4 * e + 2], (float)sP[4 * e + 3]};
@@ -1546,6 +1560,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         aacc[ct] = mfma16(pfa[g], uv[ct][g], aacc[ct]);
         cacc[ct] = mfma16(ea[g], zv[ct][g], cacc[ct]);
       }
+    if constexpr (LP == 3) {   // (the stage is this wave's until the next tile's PF rows, behind these reads in its LDS order)
+      asm volatile("" ::: "memory");
+      zsplit_store_chunk<P == 16>(sP, pz, lane, reinterpret_cast<char *>(Zc + (int64_t)rep * zrs) +
+                                                    (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz);
+    }
   }
   // a_i = (F'F bB + PF'u) / b + a_i FV  (dd columns: FV; columns >= p: 0)
   wave_block_store<P>(aacc, sred, wave, lane, tid, nullptr);
@@ -1695,6 +1714,14 @@ static bool fact_f32_off() {
 // on there and the second read of Q and Y would be pure cost.  The bits do
 // not depend on it.  DFM_AP2_PROBE=0 (A/B only, read at every solve) keeps
 // the one-pass form throughout.
+// By default those products run as six bf16 MFMA terms on operands split into
+// three bf16 planes (gemmh_zrm_split_kernel, round 15): as accurate as the
+// fp32 kernel, on the 16 times faster bf16 matrix path.  DFM_FACT_SPLIT=0 (A/B
+// only, read at every solve) restores the fp32 launches bit for bit.
+static bool fact_split_off() {
+  const char *e = getenv("DFM_FACT_SPLIT");
+  return e && atoi(e) == 0;
+}
 static bool ap2_probe_off() {
   const char *e = getenv("DFM_AP2_PROBE");
   return e && atoi(e) == 0;
@@ -1807,13 +1834,15 @@ static auto cheb_instance(bool stg) { return stg ? boot_cheb_kernel<P, P == 16> 
 template <int P>
 static auto cheb_mid_instance(bool stg, int lp, bool nopf) {
   constexpr bool F = P == 16;
-  static constexpr decltype(&boot_cheb_mid_kernel<P, false, 0, false>) tab[2][2][3] = {
+  static constexpr decltype(&boot_cheb_mid_kernel<P, false, 0, false>) tab[2][2][4] = {
       {{boot_cheb_mid_kernel<P, false, 0, false>, boot_cheb_mid_kernel<P, false, 1, false>,
-        boot_cheb_mid_kernel<P, false, 2, false>},
-       {boot_cheb_mid_kernel<P, F, 0, false>, boot_cheb_mid_kernel<P, F, 1, false>, boot_cheb_mid_kernel<P, F, 2, false>}},
+        boot_cheb_mid_kernel<P, false, 2, false>, boot_cheb_mid_kernel<P, false, 3, false>},
+       {boot_cheb_mid_kernel<P, F, 0, false>, boot_cheb_mid_kernel<P, F, 1, false>, boot_cheb_mid_kernel<P, F, 2, false>,
+        boot_cheb_mid_kernel<P, F, 3, false>}},
       {{boot_cheb_mid_kernel<P, false, 0, true>, boot_cheb_mid_kernel<P, false, 1, true>,
-        boot_cheb_mid_kernel<P, false, 2, true>},
-       {boot_cheb_mid_kernel<P, F, 0, true>, boot_cheb_mid_kernel<P, F, 1, true>, boot_cheb_mid_kernel<P, F, 2, true>}}};
+        boot_cheb_mid_kernel<P, false, 2, true>, boot_cheb_mid_kernel<P, false, 3, true>},
+       {boot_cheb_mid_kernel<P, F, 0, true>, boot_cheb_mid_kernel<P, F, 1, true>, boot_cheb_mid_kernel<P, F, 2, true>,
+        boot_cheb_mid_kernel<P, F, 3, true>}}};
   return tab[nopf][stg][lp];
 }
 
@@ -1911,6 +1940,8 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // that step filters V0 = Q0, whose first kw >= r columns are the warm vectors, and F = fscale * warm[:, :r].
   // The middle steps behind a first Rayleigh-Ritz step (warm_keep_step0; PV = P'D (Q Bm), boot_pv_kernel) have
   // no such identity and always read stored PF.
+  // ... as six bf16 terms on split operands where the model holds the split H (fact_split_off)
+  const bool split = lowp && fb.Hs && !fact_split_off();
   const bool nopf = skip0 && f.fscale > 0.0 && a.kw >= fb.r && !fact_pf_stored();
   { TimerScope ts(a, DFM_KC_EIG_OTHER);
     const int64_t n = (int64_t)m * P;
@@ -1925,7 +1956,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(64 * BW), prep_lds, st,
                        fb, idx, eta, off, lst, w.trace, mid && !nopf ? PFb : nullptr, mid ? E2b : nullptr, Q0, ps, Zc,
                        ldz, pz, ab, apre,
-                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, lowp ? 1 : 0);
+                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, split ? 2 : lowp ? 1 : 0);
     if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
     if (cheb_lds > 65536)   // T > 3276: above the default dynamic-LDS cap
       hipFuncSetAttribute((const void *)chk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cheb_lds);
@@ -1945,13 +1976,16 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   };
   // ... or, a middle product of a lowp step 0, HZ32 = H32 Z32 in fp32 (Z32 in the first half of Z's region, HZ32 in
   // HZ's, both in Z's chunk layout; every replicate is active there: no col_done, no list)
+  // (split: the same HZ32 from the bf16 planes of H and Z, Zs in Z's region at the fp64 replicate stride)
   auto hz32 = [&]() -> int {
     TimerScope ts(a, DFM_KC_GEMM);
-    const hipError_t e = launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
+    const hipError_t e =
+        split ? launch_gemm_zrm_split(fb.Hs, Zc, pz, zrs, (float *)HZ, m, ncz, m, st)
+              : launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
     return e == hipSuccess ? 0 : 1000 + (int)e;
   };
   // a middle Horner step S_i = G* S_{i+1} / b + c V0 in row-local form (Z, a, cc only) ...
-  // (lp: 0 = fp64 HZ in, fp64 Z out; 1 = HZ32 in, Z32 out; 2 = HZ32 in, fp64 Z out)
+  // (lp: 0 = fp64 HZ in, fp64 Z out; 1 = HZ32 in, Z32 out; 2 = HZ32 in, fp64 Z out; 3 = HZ32 in, split Z out)
   auto horner_mid = [&](double c, double bbeta, double bfx, double lead, int lp = 0) {
     TimerScope ts(a, DFM_KC_EIG_APPLY);
     hipLaunchKernelGGL(cheb_mid_instance<P>(stg_ok, lp, nopf), dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz, pz,
@@ -1989,10 +2023,10 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     // left the Z, a, cc, PV, FV of Q0; a_d goes into the first step's scale),
     // d0 products, the last step writes the new basis into cur with its Z, a, cc
     // (lowp: products 1 .. d0 - 1 in fp32 — prep left Z0 as float, each middle step hands the next a float Z, the
-    // last of them an fp64 Z for product d0)
+    // last of them an fp64 Z for product d0; split: bf16 planes where lowp has floats)
     for (int sp = 1; sp <= d0; ++sp) {
       if (int rc = (lowp && sp < d0) ? hz32() : hz(false)) return rc;
-      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, !lowp ? 0 : sp < d0 - 1 ? 1 : 2);
+      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, !lowp ? 0 : sp < d0 - 1 ? (split ? 3 : 1) : 2);
       else horner_last(ca0[0], 0.0, Q0, 0, bfix);
     }
     last_gemm = last_cheb = 0;

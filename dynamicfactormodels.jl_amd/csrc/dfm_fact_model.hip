@@ -261,6 +261,37 @@ hipError_t launch_fact_h32(const double *H, int64_t ldH, int T, const double *hd
   hipLaunchKernelGGL(fact_h32_kernel, dim3(T), dim3(256), 0, st, H, ldH, T, hd, H32);
   return hipGetLastError();
 }
+// Hs: the same H / hmax (the quotient in fp64) as three bf16 planes in
+// gemmh_zrm_split_kernel's piece order (dfm_internal.h), a constant of the
+// fit beside H32.  One workgroup per k-stage; thread (row a, k half kh) splits
+// its 8 doubles (H's zero k-padding gives zero pieces; rows past T are zero).
+__global__ __launch_bounds__(256) void fact_hsplit_kernel(const double *__restrict__ H, int64_t ldH, int T,
+                                                          const double *__restrict__ hd, uint4 *__restrict__ Hs,
+                                                          int mrows) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x, ks = blockIdx.x;
+  double mx = 0.0;
+  for (int s = tid; s < T; s += 256) mx = fmax(mx, hd[s]);
+  red[tid] = mx;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmax(red[tid], red[tid + o]); __syncthreads(); }
+  const double hmax = red[0] > 0.0 ? red[0] : 1.0;
+  for (int e = tid; e < 2 * mrows; e += 256) {
+    const int kh = e / mrows, a = e - kh * mrows;
+    double x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = a < T ? H[(int64_t)a * ldH + 16 * ks + 8 * kh + j] / hmax : 0.0;
+    uint4 ph, pm, pl;
+    bf16_split3_piece(x, ph, pm, pl);
+    uint4 *d = Hs + ((int64_t)ks * 6 + kh) * mrows + a;
+    d[0] = ph; d[2 * (int64_t)mrows] = pm; d[4 * (int64_t)mrows] = pl;
+  }
+}
+hipError_t launch_fact_hsplit(const double *H, int64_t ldH, int T, const double *hd, void *Hs, hipStream_t st) {
+  if (ldH < (T + 15) / 16 * 16) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fact_hsplit_kernel, dim3((T + 15) / 16), dim3(256), 0, st, H, ldH, T, hd, (uint4 *)Hs, hsplit_rows(T));
+  return hipGetLastError();
+}
 double fact_hmax(const double *hd_host, int T) {
   double mx = 0.0;
   for (int t = 0; t < T; ++t) mx = std::max(mx, hd_host[t]);   // (a NaN entry never wins, as fmax on the device)

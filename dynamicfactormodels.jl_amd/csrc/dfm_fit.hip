@@ -39,6 +39,7 @@ int dfm_model_destroy(dfm_model *m) {
                     m->cF, m->hd, m->FtF, m->FSF, m->Kwk, m->A0wk})
     hipFree(p);
   hipFree(m->H32);
+  hipFree(m->Hs);
   hipFree(m->emX2);
   for (size_t j = 1; j < m->Ubs.size(); ++j) hipFree(m->Ubs[j]);
   hipFree(m->ws);

@@ -17,8 +17,10 @@
 // tile out itself (on the shared k step it measured 3.6 % slower).
 // Grid order is XCD-aware: the row blocks of one column block are issued to
 // one XCD so a B tile is fetched from HBM once and re-read from that XCD's L2.
-// One kernel is fp32: gemmh_zrm_f32_kernel (v_mfma_f32_32x32x2_f32), the
-// middle products of a warm eigenvalue-rule solve's first filter.
+// Two kernels are not fp64, both for the middle products of a warm
+// eigenvalue-rule solve's first filter: gemmh_zrm_split_kernel (six bf16 terms
+// on v_mfma_f32_32x32x16_bf16, the default) and gemmh_zrm_f32_kernel
+// (v_mfma_f32_32x32x2_f32, DFM_FACT_SPLIT=0).
 #include "dfm_internal.h"
 #include "dfm_tile.h"
 
@@ -378,6 +380,147 @@ hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int 
   const int ncb8 = (ncb + 7) / 8 * 8;
   hipLaunchKernelGGL(gemmh_zrm_f32_kernel, dim3(nrb * ncb8), dim3(256), 0, st, A, lda, Z, pz, zrs, C, M, Nc, K, nrb,
                      ncb);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// gemmh_zrm_split_kernel: the same product, C32 ~ (H / hmax) Z, as six bf16
+// MFMA terms (round 15).  Both operands arrive split into three bf16 planes,
+// x ~ h + m + l (dfm_internal.h: Hs, Zs; the GEMM converts nothing), and
+// C32 = sum over the plane pairs of weight >= 2^-18 — (l,h) (h,l) (m,m) (m,h)
+// (h,m) (h,h), the small terms first — on v_mfma_f32_32x32x16_bf16 with fp32
+// accumulators: a product of two bf16 numbers is exact in fp32, and the
+// dropped pairs and split remainders are below 2^-25 |H| |Z|.
+// Tile, waves, XCD order and epilogue are gemmh_zrm_f32_kernel's.  One k = 16
+// stage is 24 KB: per operand six [128 rows] images of 16-B pieces, one per
+// (plane, k half) — piece (pi, kh, a) at (2 pi + kh) 128 + a, so a wave's
+// 1 KB DMA instruction fills 64 consecutive rows of one image from 64
+// consecutive pieces of Hs (or one image's pieces of consecutive Z columns),
+// and a ds_read_b128 fragment read (lane: row l & 31, k half l >> 5) touches
+// 16 distinct 16-B slots in each of its 16-lane groups with no swizzle.  The
+// six terms share one set of fragments per stage: 12 reads per 24 MFMAs.
+// 3-deep ring at 2 workgroups per CU (72 KB), six DMA instructions per wave
+// and stage.  Every output element adds its six terms in that order stage by
+// stage, whatever its tile, its place in the batch, nb or the lane.
+namespace {
+constexpr int SP_GT = 128, SP_KS = 16, SP_IMG = SP_GT * 16, SP_STAGE = 12 * SP_IMG;   // bytes
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+template <int NBUF>
+DFM_DEV void split_ring_wait(int s, int nst) {   // ring_wait at six DMA instructions per wave and stage
+  static_assert(NBUF == 3, "ring depth");
+  if (nst - 1 - s >= 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+}
+}  // namespace
+
+__global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__restrict__ Hs, int mrows,
+                                                                const char *__restrict__ Zs, int pz, int64_t zrs,
+                                                                float *__restrict__ C, int M, int Nc, int K, int nrb,
+                                                                int ncb) {
+  constexpr int NBUF = 3;
+  __shared__ __attribute__((aligned(16))) char lds[NBUF * SP_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
+  const int rb = j % nrb, cb = (j / nrb) * 8 + xcd;
+  if (cb >= ncb) return;
+  const int abase = rb * SP_GT, bbase = cb * SP_GT;
+  const int nst = (K + SP_KS - 1) / SP_KS;
+  // The stage's 24 DMA instructions, (operand, image q = 2 pi + kh, row half):
+  // wave w issues numbers 3 w .. 3 w + 2 of each operand.  Rows past M are
+  // zero in Hs (mrows = hsplit_rows(M) rows), columns past Nc read column
+  // Nc - 1 (finite data, discarded outputs).
+  const char *pa[3], *pb[3];
+  int lo[3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const int n = 3 * wave + u, q = n >> 1, half = n & 1;
+    lo[u] = (q * SP_GT + 64 * half) * 16;
+    pa[u] = Hs + ((int64_t)q * mrows + abase + 64 * half + lane) * 16;
+    const int xc = min(bbase + 64 * half + lane, Nc - 1);
+    const int rep = xc / pz, cc = xc - rep * pz;
+    pb[u] = Zs + (int64_t)rep * zrs * 8 + ((int64_t)q * pz + cc) * 16;
+  }
+  const int64_t astep = (int64_t)6 * mrows * 16, bstep = (int64_t)96 * pz;
+  auto issue = [&](int s) {
+    char *la = lds + (s % NBUF) * SP_STAGE, *lb = la + 6 * SP_IMG;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      __builtin_amdgcn_global_load_lds((gbl_void_t *)pa[u], (lds_void_t *)(la + lo[u]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_void_t *)pb[u], (lds_void_t *)(lb + lo[u]), 16, 0, 0);
+      pa[u] += astep; pb[u] += bstep;
+    }
+  };
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[ti][tj][v] = 0.0f;
+  // fragment offsets (bytes) inside plane 0's images: row r32 of tile t, k half hh
+  const int r32 = lane & 31, hh = lane >> 5;
+  int fa[2], fb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    fa[t] = (hh * SP_GT + wr * 64 + 32 * t + r32) * 16;
+    fb[t] = 6 * SP_IMG + (hh * SP_GT + wc * 64 + 32 * t + r32) * 16;
+  }
+  for (int s = 0; s < NBUF - 1 && s < nst; ++s) issue(s);
+  for (int s = 0; s < nst; ++s) {
+    split_ring_wait<NBUF>(s, nst);
+    if (s + NBUF - 1 < nst) issue(s + NBUF - 1);
+    const char *ls = lds + (s % NBUF) * SP_STAGE;
+    bf16x8 af[2][3], bf[2][3];   // [tile][plane]
+#pragma unroll
+    for (int pi = 2; pi >= 0; --pi)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        af[t][pi] = *reinterpret_cast<const bf16x8 *>(ls + fa[t] + 2 * pi * SP_IMG);
+        bf[t][pi] = *reinterpret_cast<const bf16x8 *>(ls + fb[t] + 2 * pi * SP_IMG);
+      }
+    constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};   // (H plane, Z plane), small terms first
+#pragma unroll
+    for (int e = 0; e < 6; ++e)
+#pragma unroll
+      for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+          acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti][TA[e]], bf[tj][TB[e]], acc[ti][tj], 0, 0, 0);
+  }
+  // accumulator register v of lane l: row 8 (v >> 2) + 4 (l >> 5) + (v & 3), column l & 31
+#pragma unroll
+  for (int tj = 0; tj < 2; ++tj) {
+    const int x = bbase + wc * 64 + 32 * tj + r32;
+    if (x >= Nc) continue;
+    const int rep = x / pz, cc = x - rep * pz;
+    float *cp = C + (int64_t)rep * zrs + 16 * cc;
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int row = abase + wr * 64 + 32 * ti + 8 * g + 4 * hh;
+        if (row < M)   // (rows row .. row + 3 stay inside the chunk: its pad rows take discarded values)
+          *reinterpret_cast<f32x4 *>(cp + (int64_t)(row >> 4) * (16 * pz) + (row & 15)) =
+              f32x4{acc[ti][tj][4 * g], acc[ti][tj][4 * g + 1], acc[ti][tj][4 * g + 2], acc[ti][tj][4 * g + 3]};
+      }
+  }
+}
+
+// Hs (hsplit_bytes(M), launch_fact_hsplit) times the split Z of nb = Nc / pz
+// replicates (dfm_internal.h: Zs; zrs = round_up(M, 16) pz, the fp64 Z's
+// replicate stride) -> C32 in launch_gemm_zrm_f32's layout (gemmh_zrm_split_kernel)
+hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
+                                 hipStream_t st) {
+  const int64_t kpad = (K + SP_KS - 1) / SP_KS * SP_KS;
+  if (!Hs || !Zs || M < 1 || pz < 1 || Nc < pz || Nc % pz || M != K || zrs < kpad * pz || (zrs & 3))
+    return hipErrorInvalidValue;
+  const int nrb = (M + SP_GT - 1) / SP_GT, ncb = (Nc + SP_GT - 1) / SP_GT;
+  const int ncb8 = (ncb + 7) / 8 * 8;
+  hipLaunchKernelGGL(gemmh_zrm_split_kernel, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs, hsplit_rows(M),
+                     (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb);
   return hipGetLastError();
 }
 

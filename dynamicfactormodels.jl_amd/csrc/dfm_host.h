@@ -149,6 +149,7 @@ struct dfm_model {
   int64_t ldH = 0;
   double *H = nullptr, *EL = nullptr, *S = nullptr, *cF = nullptr, *hd = nullptr;
   double *FtF = nullptr;   // F'F (16 x 16): the factored solver's middle Horner steps
+  void *Hs = nullptr;      // the same as three bf16 planes (hsplit_bytes): those products as six bf16 terms
   float *H32 = nullptr;    // float(H / hmax) (T x ldH): the fp32 middle products of warm eigenvalue-rule solves
   double hmax = 0.0;       // max_t H[t][t]
   double *FSF = nullptr;   // F S F' (T x ldH): the direct path's identity-based replicate Grams

@@ -22,6 +22,9 @@ struct FactBase {   // passed by value into the factored kernels
   // the fp32 middle products of a warm eigenvalue-rule solve (gemmh_zrm_f32_kernel); nullptr: those stay fp64
   const float *H32 = nullptr;
   double hmax = 0.0;
+  // H / hmax as three bf16 planes (hsplit_bytes; launch_fact_hsplit) for the same products as six bf16 terms
+  // (gemmh_zrm_split_kernel); nullptr: they run on H32
+  const void *Hs = nullptr;
 };
 
 // ---- dfm_ctx.hip
@@ -60,6 +63,73 @@ hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz
                            const int *ccount);
 hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int pz, int64_t zrs, float *C, int M,
                                int Nc, int K, hipStream_t st);
+// The bf16-split form of the same product (gemmh_zrm_split_kernel): x ~ h + m + l,
+// h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), the differences in fp64,
+// each bf16 the round-to-nearest-even of the fp32 rounding (24 significant
+// bits in all).  Plane pi = 0, 1, 2 is h, m, l; a 16-B piece holds 8
+// consecutive k of one row (H) or column (Z).
+//   Hs: piece (k-stage ks, plane pi, k-half kh, row a) at
+//       ((ks 3 + pi) 2 + kh) hsplit_rows(T) + a, rows a >= T and k >= T zero;
+//   Zs: replicate rep's block starts at byte 8 rep zrs (the fp64 Z's own
+//       block), its 16-row chunk ch at byte 96 pz ch, and there piece
+//       (pi, kh, column c) is number (2 pi + kh) pz + c; chunk rows >= T zero.
+// Two doubles -> one dword of each plane (element 0 in the low half).  The
+// fp32 rounding is kept a step of its own (the empty asm: the compiler would
+// fold double -> float -> bf16 into one rounding); v_cvt_pk_bf16_f32 rounds to
+// nearest even.
+DFM_DEV uint32_t bf16_pack2(float a, float b) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  asm volatile("" : "+v"(a), "+v"(b));
+  const bf16x2 v = {(__bf16)a, (__bf16)b};
+  return __builtin_bit_cast(uint32_t, v);
+}
+DFM_DEV void bf16_split3_pair(double x0, double x1, uint32_t &h, uint32_t &m, uint32_t &l) {
+  h = bf16_pack2((float)x0, (float)x1);
+  const double r0 = x0 - (double)__uint_as_float(h << 16), r1 = x1 - (double)__uint_as_float(h & 0xFFFF0000u);
+  m = bf16_pack2((float)r0, (float)r1);
+  const double s0 = r0 - (double)__uint_as_float(m << 16), s1 = r1 - (double)__uint_as_float(m & 0xFFFF0000u);
+  l = bf16_pack2((float)s0, (float)s1);
+}
+// eight consecutive doubles -> the three planes' 16-B pieces
+DFM_DEV void bf16_split3_piece(const double *x, uint4 &ph, uint4 &pm, uint4 &pl) {
+  bf16_split3_pair(x[0], x[1], ph.x, pm.x, pl.x);
+  bf16_split3_pair(x[2], x[3], ph.y, pm.y, pl.y);
+  bf16_split3_pair(x[4], x[5], ph.z, pm.z, pl.z);
+  bf16_split3_pair(x[6], x[7], ph.w, pm.w, pl.w);
+}
+// A wave stores one Z chunk (16 rows x pz columns, column-major doubles st[16 c
+// + row], in LDS) as its Zs pieces at dst, the chunk's first piece.  A lane
+// splits four doubles and stores each plane's half piece (8 B): twice the
+// lanes at half the registers of whole pieces per lane, which the middle
+// Horner steps (128 VGPRs) cannot spare.  ONE: 4 pz <= 64, a single round.
+// dst must be wave-uniform (the chunk number through readfirstlane): the
+// three stores then take a scalar base and one 32-bit lane offset, and no
+// 64-bit per-lane address is carried through the caller's tile loop.
+template <bool ONE>
+DFM_DEV void zsplit_store_chunk(const double *st, int pz, int lane, char *__restrict__ dst) {
+  auto part = [&](int e) {   // e = 4 c + 2 kh + half: doubles 4 e .. 4 e + 3
+    uint2 h, m, l;
+    bf16_split3_pair(st[4 * e], st[4 * e + 1], h.x, m.x, l.x);
+    bf16_split3_pair(st[4 * e + 2], st[4 * e + 3], h.y, m.y, l.y);
+    const uint32_t off = 8u * (uint32_t)(2 * (((e >> 1) & 1) * pz + (e >> 2)) + (e & 1));
+    *reinterpret_cast<uint2 *>(dst + off) = h;
+    *reinterpret_cast<uint2 *>(dst + 32 * pz + off) = m;
+    *reinterpret_cast<uint2 *>(dst + 64 * pz + off) = l;
+  };
+  if constexpr (ONE) {
+    // (the lane number is re-read here so that the addresses below are formed at the call, from one register: as
+    // loop invariants of the caller's tile loop they are carried in five, which the middle steps spill)
+    int e = lane;
+    asm volatile("" : "+v"(e));
+    if (e < 4 * pz) part(e);
+  } else {
+    for (int e = lane; e < 4 * pz; e += 64) part(e);
+  }
+}
+inline int hsplit_rows(int T) { return (T + 127) & ~127; }
+inline size_t hsplit_bytes(int T) { return (size_t)((T + 15) / 16) * 6 * hsplit_rows(T) * 16; }
+hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
+                                 hipStream_t st);
 hipError_t launch_gemm_loadings(const double *Eaug, int64_t lda, const double *ZF, int Kp, int rp, int N, int nrep,
                                 int K, int r, double invT, double *Lout, hipStream_t st);
 int gram_dma_slots(int m);
@@ -125,6 +195,7 @@ hipError_t launch_gram_fact(const FactBase &fb, const double *FSF, const int32_t
 int fact_precompute(const double *Ep, int64_t ld, int T, int N, int r, const double *Lb, const double *Fb,
                     const double *H, int64_t ldH, double *EL, double *S, double *cF, double *hd, hipStream_t st);
 hipError_t launch_fact_h32(const double *H, int64_t ldH, int T, const double *hd, float *H32, hipStream_t st);
+hipError_t launch_fact_hsplit(const double *H, int64_t ldH, int T, const double *hd, void *Hs, hipStream_t st);
 double fact_hmax(const double *hd_host, int T);
 
 // ---- dfm_model.hip

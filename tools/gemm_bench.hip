@@ -129,10 +129,18 @@ __global__ void fill32(float *p, size_t n, float s) {
   if (i < n) p[i] = ((i * 2654435761ull) % 1000) * 1e-3f * s - 0.5f * s;
 }
 
+// bf16 planes of random values in [-s/2, s/2) (the upper half of the float: timing only)
+__global__ void fillbf(uint16_t *p, size_t n, float s) {
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < n) p[i] = (uint16_t)(__float_as_uint(((i * 2654435761ull) % 1000) * 1e-3f * s - 0.5f * s) >> 16);
+}
+
 // Round 8: gemmh_zrm_f32_kernel (the fp32 middle products) in isolation, at
 // the C3 shape (T = 500, pz = 12, 9 999 replicates) and two smaller batches,
 // beside gemmh_zrm_kernel on the same shape in fp64.  Operands in the chunk
-// layout, every element set (pad rows included: timing only).
+// layout, every element set (pad rows included: timing only).  Round 15:
+// gemmh_zrm_split_kernel (the same products as six bf16 terms) beside them, on
+// random planes.
 static void bench_f32() {
   const int T = 500, pz = 12;
   const int64_t lda = (T + 15) / 16 * 16, zrs = lda * pz;
@@ -140,6 +148,10 @@ static void bench_f32() {
     const int Nc = nb * pz;
     float *A, *Z, *C;
     double *A64, *Z64, *C64;
+    uint16_t *Hs, *Zs;
+    hipMalloc(&Hs, hsplit_bytes(T)); hipMalloc(&Zs, (size_t)nb * zrs * 8);
+    fillbf<<<(hsplit_bytes(T) / 2 + 255) / 256, 256>>>(Hs, hsplit_bytes(T) / 2, 1.0f);
+    fillbf<<<((size_t)nb * zrs * 4 + 255) / 256, 256>>>(Zs, (size_t)nb * zrs * 4, 2.0f);
     hipMalloc(&A, (size_t)T * lda * 4); hipMalloc(&Z, (size_t)nb * zrs * 4); hipMalloc(&C, (size_t)nb * zrs * 4);
     hipMalloc(&A64, (size_t)T * lda * 8); hipMalloc(&Z64, (size_t)nb * zrs * 8); hipMalloc(&C64, (size_t)T * Nc * 8);
     fill32<<<((size_t)T * lda + 255) / 256, 256>>>(A, (size_t)T * lda, 1.0f);
@@ -147,9 +159,10 @@ static void bench_f32() {
     fill<<<((size_t)T * lda + 255) / 256, 256>>>(A64, (size_t)T * lda, 1.0, lda, T);
     fill<<<((size_t)nb * zrs + 255) / 256, 256>>>(Z64, (size_t)nb * zrs, 2.0, 1, 1);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int v = 0; v < 2; ++v) {
+    for (int v = 0; v < 3; ++v) {
       auto run = [&]() {
-        if (v == 0) launch_gemm_zrm_f32(A, lda, Z, pz, zrs, C, T, Nc, T, 0);
+        if (v == 2) launch_gemm_zrm_split(Hs, Zs, pz, zrs, C, T, Nc, T, 0);
+        else if (v == 0) launch_gemm_zrm_f32(A, lda, Z, pz, zrs, C, T, Nc, T, 0);
         else launch_gemm_zrm(A64, lda, Z64, pz, zrs, C64, Nc, T, Nc, T, 0, nullptr, nullptr, nullptr);
       };
       for (int w = 0; w < 3; ++w) run();
@@ -158,10 +171,13 @@ static void bench_f32() {
       for (int w = 0; w < reps; ++w) run();
       hipEventRecord(e1); hipEventSynchronize(e1);
       float ms; hipEventElapsedTime(&ms, e0, e1);
-      const double t = ms / reps * 1e-3, fl = 2.0 * T * (double)Nc * T, peak = v == 0 ? 157.3 : 78.6;
-      printf("%s M=K=%d pz=%d nb=%5d : %8.3f ms  %6.2f TF/s (%.1f%% of %.1f)  [%s]\n", v == 0 ? "zrm_f32" : "zrm_f64", T,
+      const double t = ms / reps * 1e-3, fl = 2.0 * T * (double)Nc * T, peak = v == 1 ? 78.6 : 157.3;
+      // (zrm_split: the fp32-equivalent rate, one product's flops; it issues six times as many on the bf16 path)
+      printf("%s M=K=%d pz=%d nb=%5d : %8.3f ms  %6.2f TF/s (%.1f%% of %.1f)  [%s]\n",
+             v == 0 ? "zrm_f32  " : v == 1 ? "zrm_f64  " : "zrm_split", T,
              pz, nb, t * 1e3, fl / t / 1e12, fl / t / 1e12 / peak * 100, peak, hipGetErrorString(hipGetLastError()));
     }
+    hipFree(Hs); hipFree(Zs);
     hipFree(A); hipFree(Z); hipFree(C); hipFree(A64); hipFree(Z64); hipFree(C64);
   }
 }
