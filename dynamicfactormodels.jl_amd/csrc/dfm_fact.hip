@@ -1943,23 +1943,31 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // ... as six bf16 terms on split operands where the model holds the split H (fact_split_off)
   const bool split = lowp && fb.Hs && !fact_split_off();
   const bool nopf = skip0 && f.fscale > 0.0 && a.kw >= fb.r && !fact_pf_stored();
+  // dynamic LDS above the default 64 KB cap: prep (24 T + 8 bytes) for T > 2730, the last Horner step (20 T + 4)
+  // for T > 3276, ap2 (16 T + 4) at T = F2_T_MAX.  A refused cap is this solve's error, not a later launch's.
+  const size_t prep_lds = (size_t)((4 * m + 3) & ~1) * 4 + (size_t)m * 8;
+  {
+    hipError_t e = hipSuccess;
+    if (prep_lds > 65536)
+      e = hipFuncSetAttribute((const void *)boot_prep_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
+    if (e == hipSuccess && cheb_lds > 65536)
+      e = hipFuncSetAttribute((const void *)chk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cheb_lds);
+    if (e == hipSuccess && ap2_lds > 65536)
+      e = hipFuncSetAttribute((const void *)boot_ap2_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap2_lds);
+    if (e != hipSuccess) return 1000 + (int)e;
+  }
   { TimerScope ts(a, DFM_KC_EIG_OTHER);
     const int64_t n = (int64_t)m * P;
     dim3 grid((unsigned)((n + 255) / 256), 1);
     hipLaunchKernelGGL(eig_init_kernel<P>, grid, dim3(256), 0, st, Q0, m, p, a.warm, a.kw, w.done, seed, (int64_t)0, ps);
     if (skip0) hipLaunchKernelGGL(q0_guards_kernel, dim3(1), dim3(1024), 0, st, Q0, m, ps, a.kw, p, w.active, nb);
     // the CSR, trace, PF / e2 and the first product's Z0 and ab
-    const size_t prep_lds = (size_t)((4 * m + 3) & ~1) * 4 + (size_t)m * 8;
-    if (prep_lds > 65536)   // T > 2730 (up to F2_T_MAX: 96 KB): above the default dynamic-LDS cap
-      hipFuncSetAttribute((const void *)boot_prep_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
     hipLaunchKernelGGL(prep_a_kernel<P>, dim3(1), dim3(64 * BW), 0, st, fb, Q0, ps, apre);
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(64 * BW), prep_lds, st,
                        fb, idx, eta, off, lst, w.trace, mid && !nopf ? PFb : nullptr, mid ? E2b : nullptr, Q0, ps, Zc,
                        ldz, pz, ab, apre,
                        skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, split ? 2 : lowp ? 1 : 0);
     if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
-    if (cheb_lds > 65536)   // T > 3276: above the default dynamic-LDS cap
-      hipFuncSetAttribute((const void *)chk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cheb_lds);
   }
   const double *ftf = fb.FtF ? fb.FtF : FtF;
   const double beta0 = warm_started ? warm_beta() : 0.0;

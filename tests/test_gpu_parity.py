@@ -519,13 +519,16 @@ def test_direct_and_factored_agree(dfm, oracle):
     assert rel(b[:, 4:], a[:, 4:]) < STAT_RTOL
 
 
-def test_direct_and_factored_agree_at_large_T(dfm, oracle):
+@pytest.mark.parametrize("T,N", [(3300, 3600), (4096, 4400)])
+def test_direct_and_factored_agree_at_large_T(dfm, oracle, T, N):
     """T = 3300 (the factored solver's prep and last Horner step then need more
-    than 64 KB of dynamic LDS: 24 T + 8 and 20 T + 4 bytes) against the direct
-    (Gram-forming) path on the same draws (src/bootstrap.jl:41-51)."""
-    y, x, w = panel(oracle, 3300, 3600, 3, 23)
+    than 64 KB of dynamic LDS: 24 T + 8 and 20 T + 4 bytes) and T = 4096, the
+    largest the factored solver accepts (fact_t_max; boot_ap2_kernel's 16 T + 4
+    bytes cross 64 KB only there), against the direct (Gram-forming) path on
+    the same draws (src/bootstrap.jl:41-51)."""
+    y, x, w = panel(oracle, T, N, 3, 23)
     g = dfm.DynamicFactorModel(y, w, x, 3, "ICp2")
-    idx, eta = dfm.draw_wild_fast(10, 6, 3300)
+    idx, eta = dfm.draw_wild_fast(10, 6, T)
     stats = [dfm.Stat.V(), dfm.Stat.criterion(), dfm.Stat.eigenvalue(1), dfm.Stat.eigenvalue(3)]
     g.set_bootstrap_mode("direct")
     a = dfm.wild_bootstrap(g, 6, stats, idx=idx, eta=eta)
