@@ -55,6 +55,10 @@ class dfm_ss_spec(C.Structure):
     _fields_ = [("horizon", C.c_int32), ("dev", C.c_int32)]
 
 
+class dfm_ss_sim_spec(C.Structure):
+    _fields_ = [("horizon", C.c_int32), ("dev", C.c_int32), ("z_dev", C.c_int32), ("pass_draws", C.c_int64)]
+
+
 class dfm_ss_mf(C.Structure):
     _fields_ = [("n_w", C.c_int32), ("w", c_double_p), ("low", c_uint8_p)]
 
@@ -187,6 +191,9 @@ SIGNATURES = [
                                 C.c_int, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_mf), C.c_int,
                                 C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out), c_double_p, c_double_p,
                                 C.POINTER(dfm_ss_em_info), c_double_p]),
+    ("dfm_ss_simulate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_ss_params),
+                                  C.POINTER(dfm_ss_sim_spec), C.c_int64, C.c_void_p, C.c_int64, c_double_p,
+                                  c_double_p, c_double_p, c_double_p]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

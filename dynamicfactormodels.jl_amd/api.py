@@ -1229,6 +1229,28 @@ def _ss_mixed(low_freq, agg_weights, N):
     return low, w
 
 
+def _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, n_w=0):
+    """(``dfm_ss_params``, r, the arrays it points into) of one checked set of
+    parameters; the state keeps max(p, n_w) lags (n_w = 0: the plain model)."""
+    Lc = _colmajor(_f64(loadings, 2))
+    r = Lc.shape[1]
+    A = _f64(A, 2)
+    if Lc.shape[0] != N or A.shape[0] != r or r < 1 or A.shape[1] % r:
+        raise ValueError("loadings must be N x r and A r x rp")
+    p = A.shape[1] // r
+    s = r * max(p, n_w)
+    sg = np.ascontiguousarray(_f64(sigma2).ravel())
+    Ac, Qc = _colmajor(A), _colmajor(_f64(Q, 2))
+    a0c = None if a0 is None else np.ascontiguousarray(_f64(a0).ravel())
+    P0c = None if P0 is None else _colmajor(_f64(P0, 2))
+    if len(sg) != N or Qc.shape != (r, r) or (a0c is not None and len(a0c) != s) or \
+            (P0c is not None and P0c.shape != (s, s)):
+        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have s entries and P0 be s x s "
+                         "(s = r p, or r max(p, len(agg_weights)) with low-frequency series)")
+    cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
+    return _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c)), r, (Lc, sg, Ac, Qc, a0c, P0c)
+
+
 def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0, low_freq=None,
                     agg_weights=None, ctx: Optional[Context] = None) -> KalmanResult:
     """Kalman filter and Rauch-Tung-Striebel smoother over the observed entries
@@ -1248,24 +1270,9 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     mixed = _ss_mixed(low_freq, agg_weights, np.shape(loadings)[0])   # before anything touches the device
     ctx = ctx or default_context()
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
-    Lc = _colmajor(_f64(loadings, 2))
-    r = Lc.shape[1]
-    A = _f64(A, 2)
-    if Lc.shape[0] != N or A.shape[0] != r or r < 1 or A.shape[1] % r:
-        raise ValueError("loadings must be N x r and A r x rp")
-    p = A.shape[1] // r
     any_low = mixed is not None and bool(mixed[0].any())
-    s = r * (max(p, len(mixed[1])) if any_low else p)
-    sg = np.ascontiguousarray(_f64(sigma2).ravel())
-    Ac, Qc = _colmajor(A), _colmajor(_f64(Q, 2))
-    a0c = None if a0 is None else np.ascontiguousarray(_f64(a0).ravel())
-    P0c = None if P0 is None else _colmajor(_f64(P0, 2))
-    if len(sg) != N or Qc.shape != (r, r) or (a0c is not None and len(a0c) != s) or \
-            (P0c is not None and P0c.shape != (s, s)):
-        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have s entries and P0 be s x s "
-                         "(s = r p, or r max(p, len(agg_weights)) with low-frequency series)")
+    params, r, _keep = _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, len(mixed[1]) if any_low else 0)
     cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
-    params = _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c))
     h = int(horizon)
     spec = _lib.dfm_ss_spec(h, int(dev))
     filt = np.zeros((M, T, r))
@@ -1290,6 +1297,70 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     if single:
         return KalmanResult(filt[0], sm[0], cov[0], float(ll[0]), int(nobs[0]), None if agg is None else agg[0])
     return KalmanResult(filt, sm, cov, ll, nobs, agg)
+
+
+@dataclass
+class SimulationResult:
+    """One ``simulation_smoother`` call: ``draws`` (D, T + h, r), joint draws
+    of the factor path given the observed entries, and ``smoothed`` (T + h,
+    r), ``smoothed_cov`` (T + h, r, r), ``loglik`` as ``KalmanResult`` holds
+    them."""
+    draws: np.ndarray
+    smoothed: np.ndarray
+    smoothed_cov: np.ndarray
+    loglik: float
+
+
+def simulation_smoother(x, loadings, sigma2, A, Q, *, draws: int, z=None, rng: Optional[np.random.Generator] = None,
+                        a0=None, P0=None, horizon: int = 0, pass_draws: Optional[int] = None,
+                        ctx: Optional[Context] = None) -> SimulationResult:
+    """Simulation smoother of Durbin & Koopman (2002): ``draws`` joint draws of
+    f_1..f_{T+h} given the observed entries of one panel (``dfm_ss_simulate``;
+    the algorithm is stated in ``include/dfm.h``).  ``x`` is one (T, N) panel,
+    host or column-major device tensor; the parameters, ``a0``, ``P0`` and
+    ``horizon`` are ``kalman_smoother``'s.  The covariance recursion runs once;
+    a draw is a mean-only recursion on the device.
+
+    ``z`` holds the standard normals, nz = s + 2 r (T + h) per draw, draw d's
+    row [z0 | u_0 zeta_0 | u_1 zeta_1 | ...]: a host array (D, nz), or a
+    float64 device tensor of shape (D, nz) with strides (1, ldz), e.g.
+    ``torch.randn(nz, D, dtype=torch.float64, device="cuda").T``.  When it is
+    omitted ``rng`` draws it on the host.  ``z`` is not scanned: a NaN in draw
+    d's row makes draw d NaN and touches no other draw.  ``pass_draws`` caps
+    the draws per device pass (default: the library's workspace rule); the
+    result does not depend on it."""
+    ctx = ctx or default_context()
+    single, (buf, _, T, N, ldx, _, dev) = _ss_panels(x)
+    if not single:
+        raise ValueError("x must be one (T, N) panel")
+    params, r, _keep = _ss_param_block(N, loadings, sigma2, A, Q, a0, P0)
+    D, h = int(draws), int(horizon)
+    if D < 1 or h < 0:
+        raise ValueError("draws must be >= 1 and horizon >= 0")
+    nz = r * params.p + 2 * r * (T + h)
+    if z is None:
+        z = (rng or np.random.default_rng()).standard_normal((D, nz))
+    if _is_device_tensor(z):
+        if z.dim() != 2 or tuple(z.shape) != (D, nz) or z.dtype.itemsize != 8 or not z.dtype.is_floating_point:
+            raise ValueError(f"z must be a float64 (draws, {nz}) tensor")
+        if z.stride(0) != 1 or z.stride(1) < D:
+            raise ValueError("a device z must have strides (1, ldz), ldz >= draws")
+        zbuf, zp, ldz, z_dev = z, z.data_ptr(), int(z.stride(1)), 1
+    else:
+        zbuf = np.asfortranarray(_f64(z, 2))   # column-major: the draw index fastest
+        if zbuf.shape != (D, nz):
+            raise ValueError(f"z must be (draws, {nz})")
+        zp, ldz, z_dev = zbuf.ctypes.data, D, 0
+    spec = _lib.dfm_ss_sim_spec(h, int(dev), z_dev, int(pass_draws or 0))
+    out = np.zeros((D, T + h, r))
+    sm = np.zeros((T + h, r))
+    cov = np.zeros((T + h, r, r))
+    ll = np.zeros(1)
+    xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data)
+    ctx.check(ctx.lib.dfm_ss_simulate(ctx.h, xp, T, N, ldx, C.byref(params), C.byref(spec), D, C.c_void_p(zp), ldz,
+                                      _lib.ptr(out), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll)))
+    del buf, zbuf
+    return SimulationResult(out, sm, cov, float(ll[0]))
 
 
 def _ss_start_axis(v, base_ndim, name):

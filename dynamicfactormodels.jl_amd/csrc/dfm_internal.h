@@ -7,6 +7,7 @@
 #include "dfm_criteria.h"
 
 struct dfm_ctx;   // dfm_host.h
+struct dfm_ss_mf;   // include/dfm.h
 
 namespace dfm {
 
@@ -307,5 +308,44 @@ hipError_t launch_chow_wide(int nb, const double *X, int64_t ld, int64_t sX, con
 hipError_t launch_predict(const double *Xp, int64_t ld, int T, int N, const double *L, int r, const double *x_dev,
                           int64_t ldx, int64_t nn, const double *w_dev, int64_t ldw, int q, const double *beta_dev,
                           double *work, double *F_out, double *yhat, hipStream_t st);
+
+// ---- dfm_ss.hip
+constexpr int SS_LS = 33, SS_MAT = 32 * SS_LS;   // row stride and size of an LDS matrix (s <= 32)
+// C_t's lower triangle in a collapsed row: element (i, j) at column i (i + 1) / 2 + j.
+__host__ __device__ inline int ss_tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+struct SsParams {   // checked, host
+  int r = 0, p = 0;
+  const double *L = nullptr, *sigma2 = nullptr, *A = nullptr, *Q = nullptr, *a0 = nullptr, *P0 = nullptr;
+};
+// What a one-panel ss_smooth_core call holds when its launches are done and
+// checked, handed to `after` before it is freed: the collapsed rows, the
+// recursion's workspace, and the parameters on both sides of the bus.
+struct SsKept {
+  int T, Tt, r, s, ncols, KS, Tpad, NCP;
+  const double *part, *ws;                 // device: [chunk][Tpad][NCP]; a_t|t, a_t|t-1, P_t|t, P_t|t-1
+  const double *dTm, *dP0;                 // device, row-major s x s
+  const double *hTm, *hQ, *ha0, *hP0;      // host, row-major (Q r x r, a0 s)
+};
+struct SsAfter {
+  virtual int run(const SsKept &k) = 0;
+  virtual ~SsAfter() = default;
+};
+int ss_param_error(dfm_ctx *ctx, const char *who, int rc, int64_t where);
+int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx, int64_t stride,
+                   bool dev, const SsParams &pr, int h, double *filt, double *smooth, double *cov, double *loglik,
+                   int64_t *nobs, const dfm_ss_mf *mf = nullptr, double *agg = nullptr, SsAfter *after = nullptr,
+                   const char *who_plain = "dfm_ss_smooth");
+// One device block from the stream's pool, freed on the stream on every return path.
+struct StreamBuf {
+  void *p = nullptr;
+  hipStream_t st = nullptr;
+  ~StreamBuf() {
+    if (p) hipFreeAsync(p, st);
+  }
+  hipError_t alloc(size_t bytes, hipStream_t s) {
+    st = s;
+    return stream_malloc(&p, bytes > 8 ? bytes : 8, s);
+  }
+};
 
 }  // namespace dfm

@@ -39,6 +39,8 @@
 // Z_l a_t|T and the low class's moments, and the <true> instantiations of the
 // M-step kernels, which read and write a series' own class's columns and
 // regress the VAR on its own lags.
+// dfm_ss_simulate (dfm_ss_sim.hip) runs the plain smoother's launches through
+// ss_smooth_core and draws from what they leave on the device.
 // No kernel uses an atomic, and the K splits depend on N and T alone: results
 // are bit-identical run to run, and panel b of a batch is bit-identical to a
 // call on panel b alone.
@@ -50,13 +52,11 @@
 namespace {
 
 constexpr int SS_KC = 256;                    // panel columns per K chunk (a multiple of 16)
-constexpr int SS_LS = 33, SS_MAT = 32 * SS_LS;   // row stride and size of an LDS matrix (s <= 32)
 
 DFM_DEV int ss_offA(int a, int kc) { return a * 16 + (kc ^ (((a >> 1) & 1) << 3)); }   // [a][k]
 DFM_DEV int ss_offB(int a, int kc) { return kc * 64 + (a ^ ((kc & 7) << 2)); }         // [k][a]
 
-// Columns of a collapsed row: C_t's lower triangle (i (i + 1) / 2 + j), b_t, q_t, n_t, l_t.
-__host__ __device__ inline int ss_tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+// Columns of a collapsed row: C_t's lower triangle (ss_tri), b_t, q_t, n_t, l_t.
 inline int ss_ncols(int r) { return r * (r + 1) / 2 + r + 3; }
 
 // Tile (blockIdx.x, blockIdx.y % nct) of K chunk blockIdx.y / nct of panel
@@ -809,25 +809,9 @@ __global__ __launch_bounds__(256) void ss_transition_kernel(const double *__rest
   }
 }
 
-// One device block, freed on the stream on every return path.
-struct StreamBuf {
-  void *p = nullptr;
-  hipStream_t st = nullptr;
-  ~StreamBuf() {
-    if (p) hipFreeAsync(p, st);
-  }
-  hipError_t alloc(size_t bytes, hipStream_t s) {
-    st = s;
-    return stream_malloc(&p, std::max<size_t>(bytes, 8), s);
-  }
-};
+}  // namespace
 
-struct SsParams {   // checked, host
-  int r = 0, p = 0;
-  const double *L = nullptr, *sigma2 = nullptr, *A = nullptr, *Q = nullptr, *a0 = nullptr, *P0 = nullptr;
-};
-
-int ss_param_error(dfm_ctx *ctx, const char *who, int rc, int64_t where) {
+int dfm::ss_param_error(dfm_ctx *ctx, const char *who, int rc, int64_t where) {
   switch (rc) {
     case SS_E_LIMIT: return fail(ctx, rc, "%s: the state-space pass serves 1 <= r <= 16, 1 <= p <= 8, r p <= 32", who);
     case SS_E_SIGMA:
@@ -840,6 +824,8 @@ int ss_param_error(dfm_ctx *ctx, const char *who, int rc, int64_t where) {
   }
   return fail(ctx, rc, "%s: bad arguments", who);
 }
+
+namespace {
 
 // A parameter block: the collapse's operands Wm, Wv (Npad x NCP row-major) and
 // winv (Npad), the companion matrix, Q (row-major), a0 (32), P0 (row-major),
@@ -898,13 +884,18 @@ int ss_fill_block(const SsParams &pr, int N, int NCP, const SsBlock &B, double *
   return 0;
 }
 
+}  // namespace
+
 // The smoother over M panels (layout of dfm_mc).  Outputs host, any nullptr.
 // mf: the mixed-frequency model (checked; pr is then the padded state's: p =
 // max(p, n_w), A = [A 0]) with its smoothed aggregate agg; null: the plain model.
-int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx, int64_t stride,
-                   bool dev, const SsParams &pr, int h, double *filt, double *smooth, double *cov, double *loglik,
-                   int64_t *nobs, const dfm_ss_mf *mf = nullptr, double *agg = nullptr) {
-  const char *who = mf ? "dfm_ss_smooth_mf" : "dfm_ss_smooth";
+// after (M = 1): called once the panel's launches are done and checked, with
+// what they left on the device (dfm_ss_simulate draws from it); who_plain names
+// the plain model's caller in the messages.
+int dfm::ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx, int64_t stride,
+                        bool dev, const SsParams &pr, int h, double *filt, double *smooth, double *cov, double *loglik,
+                        int64_t *nobs, const dfm_ss_mf *mf, double *agg, SsAfter *after, const char *who_plain) {
+  const char *who = mf ? "dfm_ss_smooth_mf" : who_plain;
   if (M < 0 || h < 0 || h > (1 << 20)) return fail(ctx, -2, "%s: bad arguments", who);
   int64_t where = -1;
   int rc = ss_check_params(N64, pr.r, pr.p, pr.L, pr.sigma2, pr.A, pr.Q, pr.a0, pr.P0, &where);
@@ -989,9 +980,16 @@ int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_
                     (hflag[i] & 2) ? "a G = I + C_t Pff is" : "a P_{t+1|t} is");
       if (nobs) nobs[c0 + i] = (int64_t)hn[i];
     }
+    if (after && M == 1) {
+      const SsKept kept{T, Tt, r, s, ncols, KS, Tpad, NCP, part, ws, dp + oTm, dp + oP0,
+                        &hp[oTm], &hp[oQ], &hp[oa0], &hp[oP0]};
+      if ((rc = after->run(kept))) return rc;
+    }
   }
   return 0;
 }
+
+namespace {
 
 // The EM over M panels (include/dfm.h).  The panel and the starts go up once;
 // per iteration one read-back (logliks and flags) decides which panels stop,

@@ -4,7 +4,9 @@
 // steps 2-3 of the two-step fit (idiosyncratic variances, VAR(p) by OLS), and
 // of the quasi-ML EM the spec's defaults, the stopping rule and the checks;
 // of the mixed-frequency model the limits, [A 0], Z_l and the fit's start
-// values of the low series.
+// values of the low series; of the simulation smoother (dfm_ss_sim.hip) the
+// factor of a positive semi-definite matrix, the count of normals, the
+// argument checks and the draws per pass.
 // No HIP includes: a plain C++ compiler builds it alone (tests/c_harness).
 //
 // Layout: every matrix the caller passes is column-major (include/dfm.h);
@@ -386,6 +388,56 @@ inline bool ss_em_empty_column(const double *X, int64_t M, int64_t T, int64_t N,
       }
     }
   return false;
+}
+
+// ------------------------------------- the simulation smoother (dfm_ss_simulate)
+constexpr int64_t SS_SIM_DMAX = (int64_t)1 << 24;   // draws per call
+
+// Lower-triangular factor R of the positive semi-definite n x n row-major Cm
+// (its lower triangle is read), R R' = Cm; R: n x n row-major, the upper
+// triangle zero.  The Cholesky loop with one rule for a rank-deficient matrix:
+// at column j, d = C_jj - sum_{k<j} R_jk^2; d <= 1e-12 C_jj (or a NaN d) leaves
+// column j zero, otherwise R_jj = sqrt(d) and the column follows as usual.
+inline void ss_psd_cholesky(const double *Cm, int n, double *R) {
+  for (int e = 0; e < n * n; ++e) R[e] = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const double cjj = Cm[j * n + j];
+    double d = cjj;
+    for (int k = 0; k < j; ++k) d -= R[j * n + k] * R[j * n + k];
+    if (!(d > 1e-12 * cjj)) continue;
+    d = sqrt(d);
+    R[j * n + j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double v = Cm[i * n + j];
+      for (int k = 0; k < j; ++k) v -= R[i * n + k] * R[j * n + k];
+      R[i * n + j] = v / d;
+    }
+  }
+}
+
+// Standard normals per draw: z0 (s), then u_t (r) and zeta_t (r) for each of the Tt rows.
+inline int64_t ss_sim_nz(int64_t Tt, int r, int s) { return (int64_t)s + 2 * (int64_t)r * Tt; }
+
+// The draws' arguments: 1 <= D <= 2^24, z and the output present, ldz >= D,
+// 0 <= horizon <= 2^20, pass_draws >= 0.
+inline int ss_sim_check_args(int64_t D, bool have_z, bool have_draws, int64_t ldz, int64_t horizon, int64_t pass_draws) {
+  if (D < 1 || D > SS_SIM_DMAX || !have_z || !have_draws || ldz < D) return -2;
+  if (horizon < 0 || horizon > (1 << 20) || pass_draws < 0) return -2;
+  return 0;
+}
+
+// Draws per pass.  pass_draws > 0: that many (at the most D).  Otherwise the
+// smoother's half-GB rule over the doubles a draw keeps on the device: c_t|t
+// (Tt x s), its output rows as the lanes store them and as they leave for the
+// host (2 Tt r), and its normals when they come from the host (z_host);
+// rounded down to whole waves of 64 draws once there is more than one.
+inline int64_t ss_sim_draws_per_pass(int64_t Tt, int r, int s, int64_t D, int64_t pass_draws, bool z_host = true) {
+  if (pass_draws > 0) return pass_draws < D ? pass_draws : D;
+  const int64_t per = 8 * (Tt * s + 2 * Tt * r + (z_host ? ss_sim_nz(Tt, r, s) : 0));
+  int64_t n = ((int64_t)1 << 29) / per;
+  if (n > 64) n &= ~(int64_t)63;
+  if (n < 1) n = 1;
+  return n < D ? n : D;
 }
 
 }  // namespace dfm

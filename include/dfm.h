@@ -709,6 +709,55 @@ int dfm_ss_fit_mf(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t l
                   const dfm_ss_fit_out *out, double *a0_out, double *loglik_path, dfm_ss_em_info *ml_info,
                   double *smoothed_agg);
 
+/* Simulation smoother (Durbin & Koopman 2002), dfm_ss_simulate (dfm_ss_sim.hip):
+ * D joint draws of f_1..f_{T+h} given the observed entries of one panel, for
+ * the plain model of dfm_ss_smooth, Tt = T + h rows, s = r p.  The smoother's
+ * recursion runs once on the panel and leaves C_t, b_t, n_t, P_t|t-1, P_t|t.
+ *
+ * Per-row gains (they do not depend on the draw; the rows are independent):
+ *   n_t > 0: G = I + C_t Pff_t|t-1, K_t = Pf_t|t-1 G^-1 (s x r);  n_t = 0: K_t = 0
+ *   t < Tt - 1: J_t = P_t|t Tm' P_{t+1|t}^-1
+ *   R_t: the lower-triangular factor of the positive semi-definite C_t, R_t R_t'
+ *   = C_t, by the Cholesky loop with one rule for a rank-deficient row (n_t <
+ *   r, or a zero loading column): at column j, d = C_jj - sum_{k<j} R_jk^2; if
+ *   d <= 1e-12 C_jj column j of R_t is zero, otherwise R_jj = sqrt(d) and the
+ *   column follows as usual.  (In exact arithmetic a zero pivot of a PSD matrix
+ *   has a zero column below it, so R R' = C still holds; a zero pivot's
+ *   rounding residue is about r 2^-53 C_jj, under 2e-15 at r = 16.)
+ *   L0: the same factor of P0 (s x s);  Lq: the Cholesky factor of Q (5 when Q
+ *   is not positive definite).
+ *
+ * Draw d, from standard normals z0 (s), u_t (r), zeta_t (r):
+ *   alpha+_0 = a0 + L0 z0;  alpha+_t = Tm alpha+_{t-1} + [Lq u_t; 0]  (t >= 1; u_0 is not read)
+ *   f+_t = alpha+_t[:r]
+ *   b*_t = b_t - C_t f+_t - R_t zeta_t          (rows with n_t > 0; zeta_t is not read otherwise)
+ *   c = 0;  per row: if n_t > 0: c <- c + K_t (b*_t - C_t c[:r]);  c_t|t = c;  c <- Tm c
+ *   backwards: c_{Tt-1|T} = c_{Tt-1|Tt-1};  c_t|T = c_t|t + J_t (c_{t+1|T} - Tm c_t|t)
+ *   draw: f~_t = f+_t + c_t|T[:r].
+ * The smoother is affine in the data and in a0: smoothing x - x+ from a zero
+ * prior mean and adding alpha+ is a draw from the posterior (the mean
+ * correction).  A pseudo-panel x+ enters the filter only through its collapsed
+ * b+_t = C_t f+_t + N(0, C_t) = C_t f+_t + R_t zeta_t: none is formed, and a
+ * row costs 2 r normals per draw whatever N is.
+ *
+ * Normals: nz = s + 2 r Tt per draw, draw d's vector [z0 | u_0 zeta_0 | u_1
+ * zeta_1 | ...]; z is column-major D x nz, the draw index fastest (ldz >= D),
+ * host memory or (z_dev) device memory.  The first s + 2 r T entries of an
+ * h-row call are the h = 0 call's.  z is not scanned: a NaN among draw d's
+ * normals makes draw d NaN and touches no other draw.  A draw's result depends
+ * on neither D, its position in the call nor the pass it falls in.
+ *
+ * Return codes are dfm_ss_smooth's; -2 also for D < 1, D > 2^24, a NULL z or
+ * draws, ldz < D and pass_draws < 0. */
+typedef struct dfm_ss_sim_spec {
+  int32_t horizon, dev /* X on the device */, z_dev /* z on the device */;
+  int64_t pass_draws;   /* 0: the workspace rule; > 0: at most that many draws per pass */
+} dfm_ss_sim_spec;
+int dfm_ss_simulate(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_ss_params *params,
+                    const dfm_ss_sim_spec *spec, int64_t D, const double *z, int64_t ldz,
+                    double *draws /* host, D x (T+h) x r row-major */,
+                    double *smoothed, double *smoothed_cov, double *loglik /* as dfm_ss_smooth, M = 1; any NULL */);
+
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
  * JOINT: OLS of y on [w x], White HC0, |t_x| > crit_value (the reference's
