@@ -1229,6 +1229,17 @@ def _ss_mixed(low_freq, agg_weights, N):
     return low, w
 
 
+def _dptr(a):
+    """The ``double *`` of a float64 array (None stays None: not given, or not wanted)."""
+    return None if a is None else a.ctypes.data_as(_lib.c_double_p)
+
+
+def _ss_mf_struct(mixed):
+    """The ``dfm_ss_mf`` of ``_ss_mixed``'s (mask, weights), which the caller keeps alive."""
+    low, w = mixed
+    return _lib.dfm_ss_mf(len(w), _dptr(w), low.ctypes.data_as(_lib.c_uint8_p))
+
+
 def _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, n_w=0):
     """(``dfm_ss_params``, r, the arrays it points into) of one checked set of
     parameters; the state keeps max(p, n_w) lags (n_w = 0: the plain model)."""
@@ -1247,8 +1258,8 @@ def _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, n_w=0):
             (P0c is not None and P0c.shape != (s, s)):
         raise ValueError("sigma2 must have N entries, Q be r x r, a0 have s entries and P0 be s x s "
                          "(s = r p, or r max(p, len(agg_weights)) with low-frequency series)")
-    cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
-    return _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c)), r, (Lc, sg, Ac, Qc, a0c, P0c)
+    return _lib.dfm_ss_params(r, p, _dptr(Lc), _dptr(sg), _dptr(Ac), _dptr(Qc), _dptr(a0c), _dptr(P0c)), r, \
+        (Lc, sg, Ac, Qc, a0c, P0c)
 
 
 def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0, low_freq=None,
@@ -1272,7 +1283,6 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
     any_low = mixed is not None and bool(mixed[0].any())
     params, r, _keep = _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, len(mixed[1]) if any_low else 0)
-    cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
     h = int(horizon)
     spec = _lib.dfm_ss_spec(h, int(dev))
     filt = np.zeros((M, T, r))
@@ -1287,9 +1297,8 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
                                         _lib.ptr(filt), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll),
                                         nobs.ctypes.data_as(_lib.c_int64_p)))
     else:
-        low, w = mixed
         agg = np.zeros((M, T + max(h, 0), r)) if any_low else None
-        mf = _lib.dfm_ss_mf(len(w), cp(w), low.ctypes.data_as(_lib.c_uint8_p))
+        mf = _ss_mf_struct(mixed)
         ctx.check(ctx.lib.dfm_ss_smooth_mf(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), C.byref(mf),
                                            C.byref(spec), _lib.ptr(filt), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll),
                                            nobs.ctypes.data_as(_lib.c_int64_p), _lib.ptr(agg)))
@@ -1408,27 +1417,18 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     for name, (a, lead) in arrs.items():
         if lead and a.shape[0] != M:
             raise ValueError(f"{name} has {a.shape[0]} per-panel starts for {M} panels")
-    get = lambda name, k: arrs[name][0][k] if arrs[name][1] else arrs[name][0]   # noqa: E731
-    r = arrs["loadings"][0].shape[-1]
-    Ash = arrs["A"][0].shape[-2:]
-    if r < 1 or Ash[0] != r or Ash[1] % r or arrs["loadings"][0].shape[-2] != N:
-        raise ValueError("loadings must be N x r and A r x rp")
-    p = Ash[1] // r
     any_low = mixed is not None and bool(mixed[0].any())
-    s = r * (max(p, len(mixed[1])) if any_low else p)
-    if arrs["sigma2"][0].shape[-1] != N or arrs["Q"][0].shape[-2:] != (r, r) or \
-            ("a0" in arrs and arrs["a0"][0].shape[-1] != s) or ("P0" in arrs and arrs["P0"][0].shape[-2:] != (s, s)):
-        raise ValueError("sigma2 must have N entries, Q be r x r, a0 have s entries and P0 be s x s "
-                         "(s = r p, or r max(p, len(agg_weights)) with low-frequency series)")
-    cp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
-    keep, starts = [], (_lib.dfm_ss_params * max(n_start, 1))()
-    for k in range(n_start):
-        Lc, Ac, Qc = _colmajor(get("loadings", k)), _colmajor(get("A", k)), _colmajor(get("Q", k))
-        sg = np.ascontiguousarray(get("sigma2", k).ravel())
-        a0c = np.ascontiguousarray(get("a0", k).ravel()) if "a0" in arrs else None
-        P0c = _colmajor(get("P0", k)) if "P0" in arrs else None
-        keep.append((Lc, Ac, Qc, sg, a0c, P0c))
-        starts[k] = _lib.dfm_ss_params(r, p, cp(Lc), cp(sg), cp(Ac), cp(Qc), cp(a0c), cp(P0c))
+    n_w = len(mixed[1]) if any_low else 0
+
+    def start(k):   # panel k's set or the shared one; without a panel, zeros of a set's shapes: those are still checked
+        def pick(name):
+            a, lead = arrs.get(name, (None, False))
+            return a if not lead else a[k] if len(a) else np.zeros(a.shape[1:])
+        return _ss_param_block(N, *(pick(name) for name in ("loadings", "sigma2", "A", "Q", "a0", "P0")), n_w)
+    keep = [start(k) for k in range(max(n_start, 1))]
+    starts = (_lib.dfm_ss_params * len(keep))(*(blk[0] for blk in keep))
+    r, p = keep[0][1], keep[0][0].p
+    s = r * max(p, n_w)
     h, mi = int(horizon), int(max_iter)
     if h < 0:
         raise ValueError("horizon must be >= 0")
@@ -1441,16 +1441,15 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     nobs = np.zeros(M, dtype=np.int64)
     path = np.full((M, mi + 1), np.nan)
     agg = np.zeros((M, T + h, r)) if any_low else None
-    out = _lib.dfm_ss_em_out(cp(Lo), cp(so), cp(Ao), cp(Qo), cp(a0o), cp(P0o), cp(filt), cp(sm), cp(cov),
-                             nobs.ctypes.data_as(_lib.c_int64_p), cp(path), cp(agg))
+    out = _lib.dfm_ss_em_out(*(_dptr(a) for a in (Lo, so, Ao, Qo, a0o, P0o, filt, sm, cov)),
+                             nobs.ctypes.data_as(_lib.c_int64_p), _dptr(path), _dptr(agg))
     info = (_lib.dfm_ss_em_info * max(M, 1))()
     xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
     if mixed is None:
         ctx.check(ctx.lib.dfm_ss_em(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(spec), C.byref(out),
                                     info))
     else:
-        low, w = mixed
-        mf = _lib.dfm_ss_mf(len(w), cp(w), low.ctypes.data_as(_lib.c_uint8_p))
+        mf = _ss_mf_struct(mixed)
         ctx.check(ctx.lib.dfm_ss_em_mf(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(mf), C.byref(spec),
                                        C.byref(out), info))
     del buf, keep
@@ -1485,9 +1484,8 @@ def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context
     A = np.zeros((r, s), order="F")
     Q = np.zeros((r, r), order="F")
     P0 = np.zeros((s, s), order="F")
-    cp = lambda a: a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
-    ctx.check(ctx.lib.dfm_ss_estimate(ctx.h, cp(Zc), T, N, T, cp(Fc), cp(Lc), r, p, _lib.ptr(sg), cp(A), cp(Q),
-                                      cp(P0)))
+    ctx.check(ctx.lib.dfm_ss_estimate(ctx.h, _dptr(Zc), T, N, T, _dptr(Fc), _dptr(Lc), r, p, _lib.ptr(sg), _dptr(A),
+                                      _dptr(Q), _dptr(P0)))
     return sg, np.ascontiguousarray(A), np.ascontiguousarray(Q), np.ascontiguousarray(P0)
 
 
@@ -1531,9 +1529,8 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     mu, sd, sg, ev, ll = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(cap), np.zeros(1)
     L, F, A, Q, P0 = np.zeros(N * cap), np.zeros(T * cap), np.zeros(cap * sc), np.zeros(cap * cap), np.zeros(sc * sc)
     filt, sm, cov = np.zeros(T * cap), np.zeros((T + h) * cap), np.zeros((T + h) * cap * cap)
-    cp = lambda a: a.ctypes.data_as(_lib.c_double_p)   # noqa: E731
-    out = _lib.dfm_ss_fit_out(cp(mu), cp(sd), cp(L), cp(sg), cp(A), cp(Q), cp(P0), cp(filt), cp(sm), cp(cov), cp(ll),
-                              cp(xs), cp(xc), cp(fc), cp(Z), cp(X2), cp(F), cp(ev))
+    out = _lib.dfm_ss_fit_out(*(_dptr(a) for a in (mu, sd, L, sg, A, Q, P0, filt, sm, cov, ll, xs, xc, fc, Z, X2, F,
+                                                   ev)))
     info = _lib.dfm_em_info()
     ml = {}
     if method == "ml" or mixed is not None:
@@ -1542,14 +1539,13 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
         mspec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, 0, float(ml_tol))
         if mixed is None:
             ctx.check(ctx.lib.dfm_ss_fit_ml(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(info),
-                                            C.byref(out), cp(a0), cp(path), C.byref(minfo)))
+                                            C.byref(out), _dptr(a0), _dptr(path), C.byref(minfo)))
         else:
-            low, w = mixed
             agg = np.zeros((T + h) * cap)
-            mf = _lib.dfm_ss_mf(len(w), cp(w), low.ctypes.data_as(_lib.c_uint8_p))
+            mf = _ss_mf_struct(mixed)
             ctx.check(ctx.lib.dfm_ss_fit_mf(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(mf),
-                                            int(method == "ml"), C.byref(info), C.byref(out), cp(a0), cp(path),
-                                            C.byref(minfo), cp(agg)))
+                                            int(method == "ml"), C.byref(info), C.byref(out), _dptr(a0), _dptr(path),
+                                            C.byref(minfo), _dptr(agg)))
             if any_low:
                 ml["smoothed_agg"] = agg[:(T + h) * int(info.r)].reshape(T + h, int(info.r)).copy()
         if method == "ml":

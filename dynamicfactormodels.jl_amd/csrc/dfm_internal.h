@@ -5,9 +5,13 @@
 #pragma once
 #include "dfm_common.h"
 #include "dfm_criteria.h"
+#include <vector>
 
 struct dfm_ctx;   // dfm_host.h
 struct dfm_ss_mf;   // include/dfm.h
+struct dfm_ss_params;
+struct dfm_ss_em_out;
+struct dfm_ss_em_info;
 
 namespace dfm {
 
@@ -313,15 +317,40 @@ hipError_t launch_predict(const double *Xp, int64_t ld, int T, int N, const doub
 constexpr int SS_LS = 33, SS_MAT = 32 * SS_LS;   // row stride and size of an LDS matrix (s <= 32)
 // C_t's lower triangle in a collapsed row: element (i, j) at column i (i + 1) / 2 + j.
 __host__ __device__ inline int ss_tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+constexpr int SS_KC = 256;                    // panel columns per K chunk (a multiple of 16)
+DFM_DEV int ss_offA(int a, int kc) { return a * 16 + (kc ^ (((a >> 1) & 1) << 3)); }   // [a][k]
+DFM_DEV int ss_offB(int a, int kc) { return kc * 64 + (a ^ ((kc & 7) << 2)); }         // [k][a]
+// Columns of a collapsed row: C_t's lower triangle (ss_tri), b_t, q_t, n_t, l_t.
+inline int ss_ncols(int r) { return r * (r + 1) / 2 + r + 3; }
+// The smoother's moments of a panel (ss_smoother_kernel<true>): S11, S10, S00, a_1|T, P_1|T at SS_M*.
+constexpr int SS_M11 = 0, SS_M10 = 256, SS_M00 = 768, SS_MA1 = 1792, SS_MP1 = 1824, SS_MOM = 2848;
 struct SsParams {   // checked, host
   int r = 0, p = 0;
   const double *L = nullptr, *sigma2 = nullptr, *A = nullptr, *Q = nullptr, *a0 = nullptr, *P0 = nullptr;
 };
+// The launch geometry of a pass over panels of one shape, stated once (ss_geom).
+// mixed: the mixed-frequency model, whose collapsed row holds a tri(C) | b
+// group per class and the low class's count after l_t.
+struct SsGeom {
+  int T, Tt, N, r, s;              // Tt = T + horizon rows, s the state
+  bool mixed;
+  int cq, ncols, nct, NCP, Npad;   // q_t's column, a collapsed row's columns, their 64-wide tiles and 64 nct; N to 16
+  int nrt, Tpad, KS;               // the collapse: 64-row tiles, 64 nrt, K chunks of SS_KC columns
+  int nrn, Nr, KT;                 // the M-step (its transpose): 64-series tiles, 64 nrn, K chunks of SS_KC rows
+};
+SsGeom ss_geom(int T, int h, int N, int r, int s, bool mixed);
+// Panel b's parameter block (ss_block), as the kernels address it.
+struct SsBlock {
+  int64_t stride, oWm, oWv, owi, oTm, oQ, oa0, oP0, oL, osig;
+};
+SsBlock ss_block(const SsGeom &G);
+int ss_fill_block(const SsParams &pr, const SsGeom &G, const SsBlock &B, double *hp, const uint8_t *low = nullptr);
 // What a one-panel ss_smooth_core call holds when its launches are done and
-// checked, handed to `after` before it is freed: the collapsed rows, the
-// recursion's workspace, and the parameters on both sides of the bus.
+// checked, handed to `after` before it is freed: the geometry they ran at, the
+// collapsed rows, the recursion's workspace, and the parameters on both sides
+// of the bus.
 struct SsKept {
-  int T, Tt, r, s, ncols, KS, Tpad, NCP;
+  SsGeom g;
   const double *part, *ws;                 // device: [chunk][Tpad][NCP]; a_t|t, a_t|t-1, P_t|t, P_t|t-1
   const double *dTm, *dP0;                 // device, row-major s x s
   const double *hTm, *hQ, *ha0, *hP0;      // host, row-major (Q r x r, a0 s)
@@ -347,5 +376,64 @@ struct StreamBuf {
     return stream_malloc(&p, bytes > 8 ? bytes : 8, s);
   }
 };
+// The panels of a pass where the kernels read them: a device batch in place, a
+// host batch through one device buffer of the largest pass's span.
+struct SsStage {
+  const double *X;
+  int64_t ldx, stride;
+  int T, N;
+  bool dev;
+  hipStream_t st;
+  StreamBuf dx;
+  int64_t span(int64_t n) const { return (n - 1) * stride + ldx * (int64_t)(N - 1) + T; }
+  hipError_t alloc(int64_t mb) { return dev ? hipSuccess : dx.alloc((size_t)span(mb) * 8, st); }
+  hipError_t pass(int64_t c0, int64_t n, const double **src) {   // panels c0 .. c0 + n - 1
+    *src = X + c0 * stride;
+    if (dev) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(dx.p, *src, (size_t)span(n) * 8, hipMemcpyHostToDevice, st);
+    *src = (const double *)dx.p;
+    return e;
+  }
+};
+// One E-step over the n panels of a pass (ss_estep): the collapse, then the
+// filter and the smoother.
+struct SsEstep {
+  const double *X;                           // the staged panels (SsStage::pass) and their layout
+  int64_t ldx, stride;
+  const double *par;                         // the parameter block of the pass's first panel (device) and the
+  int64_t pstride;                           // panel stride of the blocks (0: every panel reads that one)
+  const int *active;                         // null, or per panel: 0 = frozen
+  double *part, *ws;                         // the collapsed rows and the recursion's workspace
+  double *filt, *smooth, *cov, *ll, *nobs;   // per panel T x r, Tt x r, Tt x r x r, 1, 1 (nullptr: not wanted)
+  int *flag;                                 // per panel, for ss_estep_error
+  double *opnd, *mom;                        // given: the smoother also leaves the M-step's operand rows and moments
+  int nw;                                    // mixed frequency: the weights (device) and the smoothed aggregate
+  const double *w;
+  double *agg;
+};
+int ss_estep(dfm_ctx *ctx, const SsGeom &G, const SsBlock &B, const SsEstep &e, int64_t n);
+// A panel's non-zero E-step flag as SS_E_SINGULAR; iteration >= 0: the EM's.
+int ss_estep_error(dfm_ctx *ctx, const char *who, long long panel, int flag, int iteration = -1);
+// The mixed-frequency arguments of the entry point `who`, in the order and the
+// words all three refuse them.  *lags: 0 when no series is marked (the caller
+// runs the plain entry point), else the state's lags max(p, n_w).  rest_ok:
+// the caller's own arguments, refused after the mask and before the weights
+// (r and p are read only when it holds); dims names what the weights' message
+// asks to be >= 1.
+int ss_mf_args(dfm_ctx *ctx, const char *who, const dfm_ss_mf *mf, int64_t N, bool rest_ok, int r, int p,
+               const char *dims, int *lags);
+// The padded state's copies of n parameter sets of one (r, p): p = L and A =
+// [A 0] (held by Apad).  -1, or the first set with another (r, p) or no A.
+int64_t ss_mf_pad_params(const dfm_ss_params *sets, int64_t n, int r, int p, int L, std::vector<dfm_ss_params> &padded,
+                         std::vector<double> &Apad);
+
+// ---- dfm_ss_em.hip
+// mf: the mixed-frequency model (checked): the starts are then the padded
+// state's (p = max(p_var, n_w), A = [A 0]), p_var the VAR's own lag count
+// (out.A is r x r p_var); null: the plain model.
+int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx,
+               int64_t stride, bool dev, const dfm_ss_params *starts, int64_t n_start, int max_iter, double tol,
+               bool update_init, int h, const dfm_ss_em_out &out, dfm_ss_em_info *info, const dfm_ss_mf *mf = nullptr,
+               int p_var = 0);
 
 }  // namespace dfm

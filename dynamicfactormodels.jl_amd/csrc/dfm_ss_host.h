@@ -1,10 +1,11 @@
 // dfm_ss_host.h — the host arithmetic of the state-space pass (dfm_ss.hip):
 // the limits, the companion form of a VAR(p), the stationary covariance by the
 // doubling iteration, the argument checks of the smoother's parameters and
-// steps 2-3 of the two-step fit (idiosyncratic variances, VAR(p) by OLS), and
-// of the quasi-ML EM the spec's defaults, the stopping rule and the checks;
-// of the mixed-frequency model the limits, [A 0], Z_l and the fit's start
-// values of the low series; of the simulation smoother (dfm_ss_sim.hip) the
+// steps 2-3 of the two-step fit (dfm_ss_fit.hip: idiosyncratic variances,
+// VAR(p) by OLS), and of the quasi-ML EM (dfm_ss_em.hip) the spec's defaults,
+// the stopping rule and the checks; of the mixed-frequency model the limits,
+// [A 0], Z_l and the fit's start values of the low series; the panels per
+// pass of both drivers; of the simulation smoother (dfm_ss_sim.hip) the
 // factor of a positive semi-definite matrix, the count of normals, the
 // argument checks and the draws per pass.
 // No HIP includes: a plain C++ compiler builds it alone (tests/c_harness).
@@ -388,6 +389,17 @@ inline bool ss_em_empty_column(const double *X, int64_t M, int64_t T, int64_t N,
       }
     }
   return false;
+}
+
+// ------------------------------------------------- panels per pass (both drivers)
+// The half-GB rule of the smoother and the EM: as many panels per pass as keep
+// what they hold on the device (bytes_per_panel > 0 each) within 2^29 bytes, at
+// the most M and a launch grid's 65535, at the least one.
+inline int64_t ss_panels_per_pass(int64_t M, size_t bytes_per_panel) {
+  int64_t n = (int64_t)(((size_t)1 << 29) / bytes_per_panel);
+  if (n > 65535) n = 65535;
+  if (n > M) n = M;
+  return n < 1 ? 1 : n;
 }
 
 // ------------------------------------- the simulation smoother (dfm_ss_simulate)

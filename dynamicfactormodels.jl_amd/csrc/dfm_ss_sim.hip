@@ -4,7 +4,8 @@
 // normals and the return codes are stated in include/dfm.h).
 //
 // The smoother's own launches run once on the panel (ss_smooth_core of
-// dfm_ss.hip, which hands over what they leave on the device), then
+// dfm_ss.hip, which hands over what they leave on the device and the geometry
+// they ran at), then
 //   ss_gain_kernel          one workgroup per row t, the rows independent: the
 //                           row's K chunks added in the filter's order, K_t by
 //                           the filter's Gauss-Jordan inverse of G, J_t by the
@@ -323,7 +324,8 @@ struct SimRun : SsAfter {
   std::vector<double> Lq;   // r x r row-major, the Cholesky factor of Q
 
   int run(const SsKept &k) override {
-    const int Tt = k.Tt, r = k.r, s = k.s, ss = s * s, nrec = ss_rec_len(r, s);
+    const SsGeom &G = k.g;
+    const int Tt = G.Tt, r = G.r, s = G.s, ss = s * s, nrec = ss_rec_len(r, s);
     const int64_t nz = ss_sim_nz(Tt, r, s);
     hipStream_t st = ctx->stream;
     // ---- the constants: a0, L0, the companion matrix's first r rows, Lq
@@ -339,7 +341,7 @@ struct SimRun : SsAfter {
     HIPCHK(ctx, drec.alloc((size_t)Tt * nrec * 8, st));
     {
       Scope sc(ctx, DFM_KC_OLS);
-      const SsGainArgs ga{k.T, Tt, r, s, k.KS, k.Tpad, k.NCP, k.part, k.ws, k.dTm, k.dP0, (double *)drec.p};
+      const SsGainArgs ga{G.T, Tt, r, s, G.KS, G.Tpad, G.NCP, k.part, k.ws, k.dTm, k.dP0, (double *)drec.p};
       hipLaunchKernelGGL(ss_gain_kernel, dim3((unsigned)Tt), dim3(256), 0, st, ga);
     }
     HIPCHK(ctx, hipGetLastError());

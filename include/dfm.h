@@ -451,7 +451,7 @@ int dfm_model_fit_em(dfm_ctx *ctx, const double *y, const double *w, int q, int6
  * z-score's mu (N), sd (N) of a dfm_model_fit_em model; -1 for any other model. */
 int dfm_model_em_read(const dfm_model *m, double *X2, double *mu, double *sd);
 
-/* ------------------------------- state-space factor model (dfm_ss.hip)
+/* ---------- state-space factor model (dfm_ss.hip, dfm_ss_em.hip, dfm_ss_fit.hip)
  * The factors as a VAR(p), smoothed over the observed entries of a panel
  * (NaN = missing, m_ti = !isnan(x_ti)):
  *   x_t = Lambda f_t + e_t,  e_t ~ N(0, diag(sigma^2)),  Lambda N x r

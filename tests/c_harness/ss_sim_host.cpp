@@ -1,6 +1,6 @@
-// Stand-alone check of the simulation smoother's host arithmetic in
-// csrc/dfm_ss_host.h with a plain C++ compiler: no HIP, nothing linked from the
-// project.  The factor's inputs are integer-valued or dyadic, so every
+// Stand-alone check of the simulation smoother's host arithmetic, and of the
+// drivers' panels per pass, in csrc/dfm_ss_host.h with a plain C++ compiler: no
+// HIP, nothing linked from the project.  The factor's inputs are integer-valued or dyadic, so every
 // comparison is ==.
 #include "dfm_ss_host.h"
 
@@ -87,6 +87,23 @@ int main() {
   //   a draw larger than the half GB still gets a pass of its own; fewer than 64 are not rounded
   CHECK(ss_sim_draws_per_pass((int64_t)1 << 24, 16, 32, 5, 0) == 1);
   CHECK(ss_sim_draws_per_pass((int64_t)1 << 17, 16, 32, 100, 0, false) == 8);   // 2^29 / (8 x 2^17 x 64)
+
+  // ---- panels per pass of the smoother and the EM: min(M, 65535, 2^29 / bytes per panel), at least 1
+  CHECK(ss_panels_per_pass(3, 1000) == 3);                                      // M below both caps
+  CHECK(ss_panels_per_pass(100000, 8) == 65535);                                // a launch grid's cap
+  CHECK(ss_panels_per_pass(65535, 8) == 65535 && ss_panels_per_pass(65536, 8) == 65535);
+  CHECK(ss_panels_per_pass(1000, (size_t)1 << 20) == 512);                      // the half GB
+  CHECK(ss_panels_per_pass(1000, ((size_t)1 << 20) + 1) == 511);
+  CHECK(ss_panels_per_pass(5, (size_t)1 << 30) == 1);                           // a panel larger than the half GB
+  CHECK(ss_panels_per_pass(1, (size_t)1 << 30) == 1);
+  //   T = 8, N = 4, r = 8, p = 4, horizon 4088 (tests/test_gpu_ss.py): a panel of the smoother keeps
+  //   4096 + 4096 x 2112 + 64 + 32768 + 262144 + 2 doubles = 71598608 B -> 7 of M = 9 per pass
+  CHECK(ss_panels_per_pass(9, (size_t)8 * (4096 + 4096 * 2112 + 64 + 32768 + 262144 + 2)) == 7);
+  //   the EM's panel adds the M-step's rows (4096), the operand rows (512), the moments (2848) and its parameter
+  //   block (4244), and 8 ints: 71692240 B -> 7 as well; at horizon 2040 (tests/test_gpu_ss_em.py) 35909584 B ->
+  //   14 of M = 16
+  CHECK(ss_panels_per_pass(9, (size_t)8 * (8949826 + 4096 + 512 + 2848 + 4244) + 32) == 7);
+  CHECK(ss_panels_per_pass(16, (size_t)8 * (4096 + 2048 * 2112 + 64 + 16384 + 131072 + 2 + 11700) + 32) == 14);
   if (failures) return 1;
   std::printf("OK\n");
   return 0;

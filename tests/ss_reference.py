@@ -297,6 +297,22 @@ def synthetic_case(i):
     return X, L, sigma2, A, Q, smooth(X, L, sigma2, A, Q)
 
 
+def two_pass_case(M=9, horizon=4088):
+    """(panels, L, sigma2, A, Q, horizon): M tiny panels whose workspace is
+    large — T = 8, N = 4, r = 8, p = 4 (s = 32) and many forecast rows — so
+    that the half-GB rule of the drivers splits them into two passes: at Tt =
+    4096 the smoother's M = 9 into 7 and 2.  The parameters are those of
+    tools/ss_bench.py::parameters."""
+    T, N, r, p = 8, 4, 8, 4
+    rng = np.random.default_rng(23)
+    L = rng.standard_normal((N, r))
+    sigma2 = rng.uniform(0.5, 2.0, size=N)
+    A = np.hstack([0.5 * np.eye(r)] + [0.2 / k * np.eye(r) for k in range(1, p)])
+    panels = rng.standard_normal((M, T, N))
+    panels[2, 3, 1] = panels[7, 0, 2] = panels[8, 5, :] = np.nan
+    return panels, L, sigma2, A, np.eye(r), horizon
+
+
 def smoother_inputs():
     """Every (label, X, L, sigma2, A, Q, P0) the smoother tests run: the four
     two-step panels with the reference's fitted parameters, then the four

@@ -202,6 +202,20 @@ def test_batch_device_input_and_repeatability(dfm, ctx):
     assert np.array_equal(one_d.smoothed, a.smoothed[1]) and one_d.loglik == a.loglik[1]
 
 
+def test_pass_loop_taken_twice(dfm, ctx):
+    """S.two_pass_case: a panel of the smoother keeps 4096 (collapsed rows) + 4096 x 2112 (workspace) + 64 + 32768
+    + 262144 + 2 (outputs) doubles = 71598608 B: ss_panels_per_pass gives 7 per half GB
+    (tests/c_harness/ss_sim_host.cpp), so M = 9 runs as a pass of 7 and a pass of 2.  The first and last panel of
+    each pass against a call on that panel alone, bit for bit."""
+    panels, L, sigma2, A, Q, h = S.two_pass_case()
+    a = dfm.kalman_smoother(panels, L, sigma2, A, Q, horizon=h, ctx=ctx)
+    assert a.smoothed.shape == (9, 8 + h, 8) and a.n_observed[8] == 28
+    for k in (0, 6, 7, 8):
+        one = dfm.kalman_smoother(panels[k], L, sigma2, A, Q, horizon=h, ctx=ctx)
+        for f in ("filtered", "smoothed", "smoothed_cov", "loglik", "n_observed"):
+            assert np.array_equal(getattr(a, f)[k], getattr(one, f)), (k, f)
+
+
 # -------------------------------------------------------------------- errors
 def test_errors(dfm, ctx):
     """Every new return code from a minimal input; all are argument checks made before any device work."""

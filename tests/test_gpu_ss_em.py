@@ -183,6 +183,24 @@ def test_batch_with_a_shared_start(dfm, ctx, batch):
             assert np.array_equal(getattr(res, f)[k], getattr(one, f), equal_nan=True), (k, f)
 
 
+def test_pass_loop_taken_twice(dfm, ctx):
+    """S.two_pass_case under the EM, max_iter = 1 (two E-steps) from a shared start.  At the smoother's Tt = 4096
+    and M = 9 a panel keeps the smoother's 8949826 doubles, the M-step's rows (4096), the operand rows (512), the
+    moments (2848), its parameter block (4244) and 8 ints: 71692240 B, 7 per pass as for the smoother
+    (tests/c_harness/ss_sim_host.cpp) — but the five calls' ten serial recursions take 5 s.  So half the rows and
+    twice the panels: horizon 2040 (Tt = 2048), 4096 + 2048 x 2112 + 64 + 16384 + 131072 + 2 + 11700 doubles and 32
+    B = 35909584 B a panel, 2^29 / 35909584 = 14 per pass, and M = 16 runs as passes of 14 and 2.  The first and
+    last panel of each pass against a call on that panel alone, bit for bit."""
+    panels, L, sigma2, A, Q, h = S.two_pass_case(M=16, horizon=2040)
+    kw = dict(tol=0.0, max_iter=1, horizon=h, ctx=ctx)
+    res = dfm.ss_em(panels, L, sigma2, A, Q, **kw)
+    assert tuple(res.iterations) == (1,) * 16 and res.smoothed.shape == (16, 8 + h, 8)
+    for k in (0, 13, 14, 15):
+        one = dfm.ss_em(panels[k], L, sigma2, A, Q, **kw)
+        for f in FIELDS:
+            assert np.array_equal(getattr(res, f)[k], getattr(one, f), equal_nan=True), (k, f)
+
+
 # ---------------------------------------------------------------- bit for bit
 def test_repeat_device_input_and_horizon(dfm, ctx, batch):
     import torch

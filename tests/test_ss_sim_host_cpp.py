@@ -3,8 +3,10 @@ plain C++ compiler: tests/c_harness/ss_sim_host.cpp includes that header alone
 and links nothing from the project.  Built with AddressSanitizer + UBSan.
 ss_psd_cholesky runs on dyadic inputs and is checked as equalities (a rank-one
 matrix, a zero matrix, a full-rank one, a zero pivot between two others); then
-ss_sim_nz, every rejection of ss_sim_check_args, and ss_sim_draws_per_pass with
-and without a caller's pass_draws."""
+ss_sim_nz, every rejection of ss_sim_check_args, ss_sim_draws_per_pass with
+and without a caller's pass_draws, and ss_panels_per_pass of the smoother and
+the EM: M below the caps, the 65535 cap, the half-GB cap, a panel larger than
+half a GB, and the two-pass shapes of the GPU tests (7 of 9 panels, 14 of 16)."""
 import os
 import shutil
 import subprocess
