@@ -15,6 +15,7 @@ struct EigWork {
   double *S;               // nb x m x P: the direct path's second Horner vector (filters of degree > 2)
   double *part;            // nb x nrb x 3 x P x P
   double *rpart;           // nb x nrb x P
+  double *upart;           // nb x nrb x P: the Ritz vectors' squared norms by row block (judged_residual)
   double *small;           // nb x SMALL_STRIDE (A, Bm, theta, dead)
   int *done, *iters, *active;
   double *trace;           // nb

@@ -28,6 +28,32 @@ namespace dfm {
 constexpr int SMALL_CHOL1_DONE = 0x100;   // small_rr: R4 already holds chol(Q'Q)^-1 (eig_fused forms it during Y = G Q)
 constexpr int SMALL_STAGE_A = 0x200;      // small_rr: stop once A (R2), theta and Z'Z (R3) are formed
 constexpr int SMALL_STAGE_B = 0x400;      // small_rr: only chol(Z'Z) and Bm (eig_fused: beside the U pass)
+constexpr int SMALL_CHOL_OWN = 0x800;     // small_rr: chol(Q'Q)'s dead pivots by the column's own diagonal entry (eig_run; the
+                                          // factored solver's launch of eig_small_kernel keeps the largest-entry rule)
+
+// Upper end b of the Chebyshev filter's damped interval [0, b]: theta_p, the
+// block's last Ritz value, but no higher than 0.95 theta_k.  |T_d| = 1 at b,
+// at b / 2 and at 0, so with theta_k at b (theta_k tied with every guard
+// column, or k == p) the filter amplifies the wanted vector no more than the
+// whole unwanted spectrum and only the Rayleigh-Ritz step works on it: a tie
+// of p - k + 3 values across the k | k+1 boundary took 165 to more than 400
+// steps.  At 0.95 theta_k the last wanted vector gains T_2(2 / 0.95 - 1) =
+// 1.44 per degree-2 filter over everything in [0, b]; what lies between b and
+// theta_k grows by less than theta_k does.  theta_k <= 0: theta_p (b <= 0,
+// the callers' plain power steps).
+DFM_DEV double filter_top(const double *th, int k, int p) {
+  const double b = th[p - 1], tk = th[k - 1];
+  return tk > 0.0 ? fmin(b, 0.95 * tk) : b;
+}
+// A Ritz vector u = Q A e is a unit vector when chol(Q'Q) is sound.  Where Q'Q
+// is numerically singular (every filtered column of an exact-rank G lies in
+// its range) the factor is noise or has dead rows, and a column of U comes
+// out at norm ~ 0 — exactly 0 for a dead row, with theta = 0.  Such a pair has
+// a residual |G u - theta u| near 0 whatever theta is, and passed: zero
+// vectors for wanted null directions, or a Ritz value above lambda_1.  A pair
+// whose |u|^2 (us) is not within [1/2, 2] is not judged: residual infinite; its
+// column of Z is dead in chol(Z'Z) and is re-seeded by the apply step.
+DFM_DEV double judged_residual(double rs, double us) { return us > 0.5 && us < 2.0 ? rs : INFINITY; }
 
 // ----------------------------------------------------------------- init
 template <int P>
@@ -62,7 +88,7 @@ __global__ void eig_trace_kernel(const double *__restrict__ G, int64_t ldg, int6
 // tail: the small record's tail (theta[P], dead[P], residual history 2 x P);
 // rp: the nrb row-block residual partials (P apart); d: the replicate's done flag.
 template <int P>
-DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, double tr, int d, int rep, int rb,
+DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, const double *up, double tr, int d, int rep, int rb,
                             int nrb, int k, int p, double tol, int it, int check_only) {
   const int lane = threadIdx.x & 63;
   if (!d && it > 0) {
@@ -78,6 +104,11 @@ DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, double t
       for (int j = lane; j < k; j += 64) {
         double rs = 0.0;
         for (int r = 0; r < nrb; ++r) rs += rp[r * P + j];
+        if (up) {   // (the fused kernel folds the norm into rp itself)
+          double us = 0.0;
+          for (int r = 0; r < nrb; ++r) us += up[r * P + j];
+          rs = judged_residual(rs, us);
+        }
         const ColumnVerdict v = column_verdict(rs, j, th, th0, prev, k, p, tol, it, w.subspace);
         bsum += v.bnd;
         tsum += th[j];
@@ -98,13 +129,17 @@ DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, double t
       const int per = 64 / G;   // residual columns handled per pass
       for (int jj = 0; jj < 64 && j0 + jj < k; jj += per) {
         const int j = j0 + jj + lane / G, r = lane % G;
-        double v = 0.0;
+        double v = 0.0, us = 0.0;   // us: |u_j|^2 by the same tree (the fused kernel folds the norm into rp itself)
         if (j < k)
-          for (int rr = r; rr < nrb; rr += G) v += rp[rr * P + j];
-        for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+          for (int rr = r; rr < nrb; rr += G) {
+            v += rp[rr * P + j];
+            if (up) us += up[rr * P + j];
+          }
+        for (int o = G / 2; o >= 1; o >>= 1) { v += __shfl_xor(v, o); us += __shfl_xor(us, o); }
         // lanes with r == 0 hold the column sums
         bool okj = true;
         if (j < k && r == 0) {
+          if (up) v = judged_residual(v, us);
           const ColumnVerdict cv = column_verdict(v, j, th, th0, prev, k, p, tol, it, w.subspace);
           okj = cv.ok;
           if (rb == 0) next[j] = cv.res;
@@ -117,7 +152,10 @@ DFM_DEV int check_converged(EigWork &w, double *tail, const double *rp, double t
       if (rb == 0 && lane == 0) { w.done[rep] = 1; w.iters[rep] = it; }
     }
   }
-  if (rb == 0 && lane == 0 && !d) atomicAdd(&w.active[it], 1);
+  if (rb == 0 && lane == 0 && !d) {
+    atomicAdd(&w.active[it], 1);
+    if (check_only) w.iters[rep] = it;   // not converged: all maxit steps were taken (status 1)
+  }
   return d || check_only;
 }
 
@@ -147,7 +185,7 @@ __global__ __launch_bounds__(256) void eig_gq_kernel(const double *__restrict__ 
   const int rep = blockIdx.y, rb = blockIdx.x, nrb = gridDim.x;
   double *small = w.small + (int64_t)rep * small_stride<P>();
   if (tid < 64) {
-    const int d = check_converged<P>(w, small + 2 * P * P, w.rpart + (int64_t)rep * nrb * P, w.trace[rep], w.done[rep],
+    const int d = check_converged<P>(w, small + 2 * P * P, w.rpart + (int64_t)rep * nrb * P, w.upart + (int64_t)rep * nrb * P, w.trace[rep], w.done[rep],
                                      rep, rb, nrb, k, p, tol, it, check_only);
     if (tid == 0) s_skip = d;
   }
@@ -230,7 +268,7 @@ __global__ __launch_bounds__(256) void eig_gq_kernel(const double *__restrict__ 
 // one 64-row block per workgroup.
 template <int P>
 __global__ __launch_bounds__(256) void eig_cheb_kernel(const double *__restrict__ G, int64_t ldg,
-                                                       int64_t strideG, EigWork w, int m, int p,
+                                                       int64_t strideG, EigWork w, int m, int k, int p,
                                                        const double *Sin, double *Sout, double fai) {
   constexpr int SQ = P + 4;
   __shared__ __attribute__((aligned(16))) double sV[EROWS * SQ];
@@ -238,7 +276,7 @@ __global__ __launch_bounds__(256) void eig_cheb_kernel(const double *__restrict_
   const int rep = blockIdx.y, rb = blockIdx.x;
   if (w.done[rep]) return;
   const double *small = w.small + (int64_t)rep * small_stride<P>();
-  const double b = small[2 * P * P + p - 1];
+  const double b = filter_top(small + 2 * P * P, k, p);
   // b <= 0 (a degenerate block): plain power steps
   const double cb = b > 0.0 ? 1.0 / b : 1.0, cv0 = b > 0.0 ? fai : 0.0;
   const double *Gr = G + (int64_t)rep * strideG;
@@ -361,8 +399,14 @@ DFM_DEV double rl64(double x, int l) {   // lane l's x (l wave-uniform: a compil
 // from there as same-address LDS broadcasts, one instruction per double
 // where a readlane pair plus its hazard wait took three or four (this
 // wave's own writes, in LDS order).  Tiny pivots -> dead (unit diagonal,
-// zero column, zero row of Li).
-template <int P>
+// zero column, zero row of Li).  Tiny is 1e-22 of the largest diagonal entry
+// (Z'Z: the columns of Z = G U scale with their Ritz values, and a wanted
+// zero is dead), or with OWN of the column's own diagonal entry (Q'Q: the
+// filter leaves the columns of Q with norms T_d(theta_j / theta_p), 2^67 apart
+// on a spectrum that falls by 2^15 across the block, so only a column that is
+// linearly dependent on those before it, to 1e-11, is dead; against the
+// largest entry every short column was, and came back as theta = 0, u = 0).
+template <int P, bool OWN = false>
 DFM_DEV void wave_chol_inv(double *M, double *Li, int *dead, int p) {
   constexpr int S = P + 1;
   const int lane = threadIdx.x & 63;
@@ -381,7 +425,7 @@ DFM_DEV void wave_chol_inv(double *M, double *Li, int *dead, int p) {
   for (int j = 0; j < P; ++j) {
     if (j < p) {
       const double sj = rl64(r[j], j);
-      const bool dd = !(sj > thresh);
+      const bool dd = !(sj > (OWN ? 1e-22 * M[j * S + j] : thresh));   // (row j of M is still the input's)
       const double inv = dd ? 1.0 : rsqrt(sj);
       double lij = (lane > j && lane < p) ? (dd ? 0.0 : r[j] * inv) : 0.0;
       if (lane == j) { lij = dd ? 1.0 : sj * inv; inv_l = inv; dead_l = dd; }
@@ -467,7 +511,10 @@ DFM_DEV void small_rr(SmallLds<P> &sm, EigWork &w, int rep, int p, int jsweeps, 
   if (!(jsweeps & SMALL_STAGE_B)) {
   wave_sym<P>(Hq);
   // 2. Q'Q = L L',  Li = L^-1;  H~ = Li (Q'Y) Li'
-  if (!(jsweeps & SMALL_CHOL1_DONE)) wave_chol_inv<P>(sm.R2, sm.R4, sm.dead, p);
+  if (!(jsweeps & SMALL_CHOL1_DONE)) {
+    if (jsweeps & SMALL_CHOL_OWN) wave_chol_inv<P, true>(sm.R2, sm.R4, sm.dead, p);
+    else wave_chol_inv<P>(sm.R2, sm.R4, sm.dead, p);
+  }
   SMALL_STAMP(2);
   SMALL_STAMP(3);
   wave_mm<P, false, false>(sm.R4, Hq, sm.R2);   // Q'Q is dead once Li is formed
@@ -657,8 +704,9 @@ __global__ __launch_bounds__(256) void eig_apply_kernel(EigWork w, int m, int p,
                                                         double fa0) {
   constexpr int SQ = P + 1;
   __shared__ double sQ[EROWS * SQ], sY[EROWS * SQ], sW[EROWS * P];
-  __shared__ double sA[P * P], sB[P * P], sT[2 * P];
+  __shared__ double sA[P * P], sB[P * P], sT[2 * P], sUn[256];
   const int tid = threadIdx.x, rep = blockIdx.y, rb = blockIdx.x, nrb = gridDim.x;
+  double un = 0.0;   // this thread's rows' share of |u_c|^2, c = tid % P (256 % P == 0: one column per thread)
   if (w.done[rep]) return;
   const double *small = w.small + (int64_t)rep * small_stride<P>();
   double *Qr = w.Q + (int64_t)rep * m * P;
@@ -684,10 +732,11 @@ __global__ __launch_bounds__(256) void eig_apply_kernel(EigWork w, int m, int p,
     if (c < p && sT[P + c] != 0.0) qn = hash_unit(seed, row, 1000003ull * (it + 1) + c);
     if (c >= p) { qn = 0.0; qb = 0.0; }
     if (c < k) { const double wv = ya - sT[c] * u; sW[r * P + c] = row < m ? wv * wv : 0.0; }
+    if (row < m) un = fma(u, u, un);
     if (row < m) {
       Ur[(int64_t)row * P + c] = u;
       if (cheb) {   // the filter's first Horner term S = (a_d/b) V + a_{d-1} Q Bm, and V0 = Q Bm (dead: V)
-        const double bch = sT[p - 1];
+        const double bch = filter_top(sT, k, p);
         const bool dead = c < p && sT[P + c] != 0.0;
         const double sv = dead ? qn : (bch > 0.0 ? fma(fa1 / bch, qn, fa0 * qb) : qn);
         Yr[(int64_t)row * P + c] = c >= p ? 0.0 : sv;
@@ -697,11 +746,14 @@ __global__ __launch_bounds__(256) void eig_apply_kernel(EigWork w, int m, int p,
       }
     }
   }
+  sUn[tid] = un;
   __syncthreads();
   if (tid < k) {
-    double s = 0.0;
+    double s = 0.0, us = 0.0;
     for (int r = 0; r < EROWS; ++r) s += sW[r * P + tid];
+    for (int q = tid; q < 256; q += P) us += sUn[q];
     w.rpart[((int64_t)rep * nrb + rb) * P + tid] = s;
+    w.upart[((int64_t)rep * nrb + rb) * P + tid] = us;
   }
 }
 
@@ -798,6 +850,7 @@ size_t eig_workspace_bytes(int m, int nb, int P, int maxit) {
   s += (size_t)nb * (2 * P * P + 4 * P) * 8;     // small
   s += (size_t)nb * 8;                           // trace
   s += (size_t)(2 * nb + maxit + 2) * 4 + 256;   // done, iters, active
+  s += (size_t)nb * nrb * P * 8 + 256;           // upart
   return s;
 }
 
@@ -816,6 +869,7 @@ EigWork carve(char *base, int m, int nb, int P, int maxit) {
   w.done = (int *)take((size_t)nb * 4);
   w.iters = (int *)take((size_t)nb * 4);
   w.active = (int *)take((size_t)(maxit + 2) * 4);
+  w.upart = (double *)take((size_t)nb * nrb * P * 8);   // last: the members before it keep their places
   w.dbg = nullptr;
   w.subspace = 0;
   w.no_vectors = 0;
@@ -1014,6 +1068,7 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
   __shared__ SmallLds<P> sm;
   __shared__ double s_tail[4 * P];   // the small record's tail: theta[P], dead[P], residual history 2 x P
   __shared__ double s_rw[4][P];      // per-wave residual sums of one apply
+  __shared__ double s_uw[4][P];      // and of |u_c|^2 (judged_residual)
   __shared__ double s_res[P];        // their fixed-order total (check_converged's one "row block")
   __shared__ int s_done;
   __shared__ double s_ca[2][kChebDMax + 1];   // filter coefficients, degree 2 | 4 (indexed at run time: LDS, not the kernarg struct)
@@ -1073,7 +1128,7 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
     {
       FZ_THREAD;
       if (wave == 0) {
-        const int d = check_converged<P>(w, s_tail, s_res, tr, 0, rep, 0, 1, k, p, tol, it, 0);
+        const int d = check_converged<P>(w, s_tail, s_res, nullptr, tr, 0, rep, 0, 1, k, p, tol, it, 0);
         if (lane == 0) s_done = d;
       }
     }
@@ -1098,7 +1153,7 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
       } else {
         fz_xtx(sQ, sQ, sm.R2, mpad, lane);   // Q'Q
         wave_lds_sync();
-        wave_chol_inv<P>(sm.R2, sm.R4, sm.dead, p);
+        wave_chol_inv<P, true>(sm.R2, sm.R4, sm.dead, p);
       }
     }
     __syncthreads();
@@ -1120,9 +1175,9 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
         if (pf) {   // stamps of the Rayleigh-Ritz stages (the last step's) after the phase sums
           EigWork wd = w;
           wd.dbg = prof + 8;
-          small_rr<P>(sm, wd, rep, p, jsweeps | (OVL ? SMALL_CHOL1_DONE : 0) | SMALL_STAGE_A, nullptr, s_tail);
+          small_rr<P>(sm, wd, rep, p, jsweeps | (OVL ? SMALL_CHOL1_DONE : SMALL_CHOL_OWN) | SMALL_STAGE_A, nullptr, s_tail);
         } else {
-          small_rr<P>(sm, w, rep, p, jsweeps | (OVL ? SMALL_CHOL1_DONE : 0) | SMALL_STAGE_A, nullptr, s_tail);
+          small_rr<P>(sm, w, rep, p, jsweeps | (OVL ? SMALL_CHOL1_DONE : SMALL_CHOL_OWN) | SMALL_STAGE_A, nullptr, s_tail);
         }
       }
     }
@@ -1141,13 +1196,13 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
         } else {
           small_rr<P>(sm, w, rep, p, jsweeps | SMALL_STAGE_B, nullptr, s_tail);
         }
-        if (lane < P) s_rw[0][lane] = 0.0;
+        if (lane < P) { s_rw[0][lane] = 0.0; s_uw[0][lane] = 0.0; }
       } else {
         double bA[4];
 #pragma unroll
         for (int fb = 0; fb < 4; ++fb) bA[fb] = sm.R2[fkc * S + 4 * fb + fi];
         const double th_c = s_tail[oc];
-        double rs = 0.0;
+        double rs = 0.0, us = 0.0;
 #pragma unroll 1
         for (int g = wave - 1; g < ng; g += 3) {
           const int ra = 4 * g + fi;
@@ -1161,13 +1216,15 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
           const double u = mm4_fold(u4, lane), ya = mm4_fold(ya4, lane);
           const int row = 4 * g + orow;
           if (row < m) {
-            if (oc < k) { const double wv = ya - th_c * u; rs += wv * wv; }
+            if (oc < k) { const double wv = ya - th_c * u; rs += wv * wv; us = fma(u, u, us); }
             Ur[(int64_t)row * P + oc] = u;
           }
         }
         rs += __shfl_xor(rs, 16);
         rs += __shfl_xor(rs, 32);
-        if (lane < P) s_rw[wave][lane] = rs;
+        us += __shfl_xor(us, 16);
+        us += __shfl_xor(us, 32);
+        if (lane < P) { s_rw[wave][lane] = rs; s_uw[wave][lane] = us; }
       }
     }
     __syncthreads();
@@ -1177,10 +1234,12 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
     // (a_d / b) V + a_{d-1} V0 into Y, V0 into Q (dead columns re-randomised)
     const int dg = (warm_strict && it < 4) ? kChebDirectStrict : 2;
     const double *ca = s_ca[dg == 2 ? 0 : 1];
-    const double bch = s_tail[p - 1];
+    const double bch = filter_top(s_tail, k, p);
     {
       FZ_THREAD;
-      if (tid < P) s_res[tid] = ((s_rw[0][tid] + s_rw[1][tid]) + s_rw[2][tid]) + s_rw[3][tid];
+      if (tid < P)
+        s_res[tid] = judged_residual(((s_rw[0][tid] + s_rw[1][tid]) + s_rw[2][tid]) + s_rw[3][tid],
+                                     tid < k ? ((s_uw[0][tid] + s_uw[1][tid]) + s_uw[2][tid]) + s_uw[3][tid] : 1.0);
       const bool dead_c = oc < p && s_tail[P + oc] != 0.0;
       double bB[4];
 #pragma unroll
@@ -1240,6 +1299,7 @@ __global__ __launch_bounds__(256, NGW <= 9 ? 2 : 1) void eig_fused_kernel(
   }
   // the last apply's Ritz vectors (this workgroup's own global writes: the
   // barrier that ended the iteration makes them visible) -> signs, outputs
+  if (!s_done && threadIdx.x == 0) w.iters[rep] = it;   // not converged: it == maxit (check_converged's check-only record)
   eig_final_body<P>(Ur, s_tail, s_done, rep, m, k, lam, Uk, status);
   if (pf && threadIdx.x == 0) {
     for (int i = 0; i < 6; ++i) prof[i] = pacc[i];
@@ -1280,7 +1340,7 @@ static int eig_run_t(const double *G, int64_t ldg, int64_t strideG, int m, const
   // (single fits, nb = 1, too: cold-started, polished to 1e-14 by run_eig)
   const bool warm_strict = tol >= 0.0 && ((warm && kw >= k) || nb == 1);
   if constexpr (P == 16) {
-    const int ngw = fused_enabled() ? fused_ngw(m) : 0;
+    const int ngw = (a.fused < 0 ? fused_enabled() : a.fused != 0) ? fused_ngw(m) : 0;
     if (ngw) {
       ChebCo cc;
       shifted_cheb(kChebDirectStrict, cc.c4);
@@ -1364,7 +1424,7 @@ static int eig_run_t(const double *G, int64_t ldg, int64_t strideG, int m, const
     }
     if (check_only) break;
     { TimerScope ts(a, DFM_KC_EIG_SMALL);
-      hipLaunchKernelGGL(eig_small_kernel<P>, dim3(nb), dim3(64), 0, st, w, p, nrb, kJacobiSweeps);
+      hipLaunchKernelGGL(eig_small_kernel<P>, dim3(nb), dim3(64), 0, st, w, p, nrb, kJacobiSweeps | SMALL_CHOL_OWN);
     }
     { TimerScope ts(a, DFM_KC_EIG_APPLY);
       hipLaunchKernelGGL(eig_apply_kernel<P>, dim3(nrb, nb), dim3(256), 0, st, w, m, p, k, it, seed, rep0, cheb,
@@ -1372,7 +1432,7 @@ static int eig_run_t(const double *G, int64_t ldg, int64_t strideG, int m, const
       for (int j = 1; cheb && j < dg; ++j) {   // S_{dg-1-j}: in w.Y / w.S alternately, S_0 into w.Q
         const double *sin = (j & 1) ? w.Y : w.S;
         double *sout = j == dg - 1 ? w.Q : ((j & 1) ? w.S : w.Y);
-        hipLaunchKernelGGL(eig_cheb_kernel<P>, dim3(nrb, nb), dim3(256), 0, st, G, ldg, strideG, w, m, p, sin, sout,
+        hipLaunchKernelGGL(eig_cheb_kernel<P>, dim3(nrb, nb), dim3(256), 0, st, G, ldg, strideG, w, m, k, p, sin, sout,
                            ca[dg - 1 - j]);
       }
     }

@@ -168,6 +168,7 @@ struct EigArgs {
   timer_fn tf;
   void *tctx;
   int subspace = 0;               // EigWork::subspace
+  int fused = -1;                 // the one-workgroup solver (m <= 256, P = 16): -1 as DFM_EIG_FUSED says, 0 off, 1 on
 };
 int eig_run(const double *G, int64_t ldg, int64_t strideG, int m, const EigArgs &a, int *iters_host, int64_t rep0);
 

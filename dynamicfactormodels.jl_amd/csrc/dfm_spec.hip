@@ -185,8 +185,9 @@ __global__ __launch_bounds__(256) void bisect_kernel(const double *__restrict__ 
       if (i + 1 < m) emax = fmax(emax, e2[i]);
     }
     const double nrm = fmax(fabs(lo), fabs(hi));
-    lo -= 2.2e-16 * nrm * m + 1e-300;
-    hi += 2.2e-16 * nrm * m + 1e-300;
+    const double pad = nrm > 0.0 ? 2.2e-16 * nrm * m + 1e-300 : 0.0;   // T = 0: every eigenvalue is exactly 0
+    lo -= pad;
+    hi += pad;
     bnd[0] = lo; bnd[1] = hi;
     e2[m] = fmax(2.2e-308, emax * 2.2e-308);   // pivmin (slot m: LDS holds 2m+1)
   }
@@ -482,7 +483,8 @@ __global__ __launch_bounds__(64) void invit_kernel(const double *__restrict__ db
                *tn = tnb + rep;
   double *ua = uab + rep * mk, *ub = ubb + rep * mk, *uc = ucb + rep * mk, *ud = udb + rep * mk, *Z = Zb + rep * mk;
   unsigned char *piv = pivb + rep * mk;
-  const double xj = sig[j], tiny = 2.2e-16 * *tn;
+  // T = 0 (G = 0): every vector is an eigenvector; unit pivots return the start vectors (0 / 0 otherwise)
+  const double xj = sig[j], tiny = *tn > 0.0 ? 2.2e-16 * *tn : 1.0;
 #define IX(i) ((int64_t)(i) * k + j)
   for (int i = 0; i < m; ++i) { ua[IX(i)] = d[i] - xj; ub[IX(i)] = (i + 1 < m) ? e[i] : 0.0; ud[IX(i)] = 0.0; }
   for (int i = 0; i + 1 < m; ++i) {
