@@ -21,7 +21,8 @@ from .api import (Context, DFMError, Stat, DynamicFactorModel, DynamicFactorMode
                   chow_sweep, sup_chow_pvalues, sup_chow_range, ChowSweepResult, monte_carlo,
                   MonteCarloResult, em_factors, DynamicFactorModel_em, EMResult, stationary_covariance,
                   kalman_smoother, ss_parameters, DynamicFactorModel_ss, KalmanResult, StateSpaceResult,
-                  ss_em, StateSpaceEMResult, AGG_FLOW, AGG_MEAN, simulation_smoother, SimulationResult)
+                  ss_em, StateSpaceEMResult, AGG_FLOW, AGG_MEAN, simulation_smoother, SimulationResult,
+                  nowcast_news, NewsResult)
 from .api import (criterion_PCp1, criterion_PCp2, criterion_PCp3, criterion_ICp1,  # noqa: F401
                   criterion_ICp2, criterion_ICp3, criterion_BIC)
 from . import _lib
@@ -41,5 +42,5 @@ __all__ = [
     "em_factors", "DynamicFactorModel_em", "EMResult",
     "stationary_covariance", "kalman_smoother", "ss_parameters", "DynamicFactorModel_ss", "KalmanResult",
     "StateSpaceResult", "ss_em", "StateSpaceEMResult", "AGG_FLOW", "AGG_MEAN",
-    "simulation_smoother", "SimulationResult",
+    "simulation_smoother", "SimulationResult", "nowcast_news", "NewsResult",
 ]

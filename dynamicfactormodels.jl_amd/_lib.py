@@ -59,6 +59,16 @@ class dfm_ss_sim_spec(C.Structure):
     _fields_ = [("horizon", C.c_int32), ("dev", C.c_int32), ("z_dev", C.c_int32), ("pass_draws", C.c_int64)]
 
 
+class dfm_ss_news_spec(C.Structure):
+    _fields_ = [("horizon", C.c_int32), ("t_lo", C.c_int32), ("pass_releases", C.c_int64)]
+
+
+class dfm_ss_news_out(C.Structure):
+    _fields_ = [(n, c_double_p) for n in
+                ("smoothed_old", "smoothed_rev", "smoothed_new", "smoothed_agg_old", "smoothed_agg_rev",
+                 "smoothed_agg_new", "news", "release_forecast", "weights_f", "weights_agg")]
+
+
 class dfm_ss_mf(C.Structure):
     _fields_ = [("n_w", C.c_int32), ("w", c_double_p), ("low", c_uint8_p)]
 
@@ -194,6 +204,9 @@ SIGNATURES = [
     ("dfm_ss_simulate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_ss_params),
                                   C.POINTER(dfm_ss_sim_spec), C.c_int64, C.c_void_p, C.c_int64, c_double_p,
                                   c_double_p, c_double_p, c_double_p]),
+    ("dfm_ss_news", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int64,
+                              C.POINTER(dfm_ss_params), C.POINTER(dfm_ss_mf), C.POINTER(dfm_ss_news_spec), C.c_int64,
+                              c_int64_p, c_int64_p, C.POINTER(dfm_ss_news_out)]),
     ("dfm_targeted_hard", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int64,
                                     c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_double, c_double_p, c_uint8_p]),

@@ -1372,6 +1372,120 @@ def simulation_smoother(x, loadings, sigma2, A, Q, *, draws: int, z=None, rng: O
     return SimulationResult(out, sm, cov, float(ll[0]))
 
 
+@dataclass
+class NewsResult:
+    """One ``nowcast_news`` call, J releases and K targets.  ``releases``
+    (J, 2): (t, i) of every entry observed in the new vintage and missing in
+    the old one, sorted; ``news`` (J) = the released value minus
+    ``release_forecast`` (J), its forecast from the revised old vintage, in the
+    units the model sees (standardised when ``mean`` / ``std`` are given).
+    ``weights_f`` and ``weights_agg`` (J, T + h - t_lo, r): what one unit of
+    release j's news moves f_t|T and the aggregate sum_k w_k f_{t-k}|T by
+    (``weights_agg`` is None for the plain model).  The smoothed paths
+    (T + h, r) of the old, the revised and the new vintage, with their
+    aggregates (None for the plain model).  Per target (t, k), in original
+    units: ``old``, ``revised``, ``new`` (K each), ``revision_effect`` =
+    revised - old, ``impacts`` (K, J) and ``by_series`` (K, N), the impacts
+    summed over the releases of each series; new - revised ==
+    impacts.sum(axis=1) up to rounding."""
+    releases: np.ndarray
+    news: np.ndarray
+    release_forecast: np.ndarray
+    weights_f: np.ndarray
+    weights_agg: Optional[np.ndarray]
+    smoothed_old: np.ndarray
+    smoothed_revised: np.ndarray
+    smoothed_new: np.ndarray
+    smoothed_agg_old: Optional[np.ndarray]
+    smoothed_agg_revised: Optional[np.ndarray]
+    smoothed_agg_new: Optional[np.ndarray]
+    targets: np.ndarray
+    old: np.ndarray
+    revised: np.ndarray
+    new: np.ndarray
+    revision_effect: np.ndarray
+    impacts: np.ndarray
+    by_series: np.ndarray
+    t_lo: int = 0
+
+
+def nowcast_news(x_old, x_new, loadings, sigma2, A, Q, *, targets, a0=None, P0=None, horizon: int = 0, low_freq=None,
+                 agg_weights=None, mean=None, std=None, t_lo: int = 0, releases=None,
+                 pass_releases: Optional[int] = None, ctx: Optional[Context] = None) -> NewsResult:
+    """News decomposition of a forecast revision (Banbura & Modugno 2014;
+    ``dfm_ss_news``, stated in ``include/dfm.h``): when a new vintage ``x_new``
+    of the (T, N) panel ``x_old`` moves the smoothed path, which release moved
+    it and by how much.  The parameters, ``a0``, ``P0``, ``horizon``,
+    ``low_freq`` and ``agg_weights`` are ``kalman_smoother``'s and are shared
+    by both vintages.  The releases, the entries observed in ``x_new`` and NaN
+    in ``x_old``, are found here; every entry observed in ``x_old`` must be
+    observed in ``x_new`` (its value may differ: a revision, whose effect is
+    reported apart from the news).
+
+    ``targets``: (t, k) pairs, row t in [t_lo, T + horizon) of series k.  With
+    ``mean`` / ``std`` (a fit's) both vintages are standardised first and the
+    target quantities are in original units.  ``t_lo``: the weights are
+    returned for the rows from t_lo on.  ``releases``: a caller's own (J, 2)
+    list of (t, i), which the library checks against the two vintages (it must
+    be exactly the releases, sorted).  ``pass_releases`` caps the releases per
+    device pass; the result does not depend on it."""
+    xo, xn = _f64(x_old, 2), _f64(x_new, 2)
+    if xo.shape != xn.shape:
+        raise ValueError("x_old and x_new must be two vintages of one (T, N) panel")
+    T, N = xo.shape
+    mixed = _ss_mixed(low_freq, agg_weights, N)   # before anything touches the device
+    mu = np.zeros(N) if mean is None else _f64(mean).ravel()
+    sd = np.ones(N) if std is None else _f64(std).ravel()
+    if len(mu) != N or len(sd) != N:
+        raise ValueError("mean and std must have one entry per series")
+    if mean is not None or std is not None:
+        xo, xn = (xo - mu) / sd, (xn - mu) / sd
+    tg = np.asarray(targets, dtype=np.int64).reshape(-1, 2)
+    h, lo = int(horizon), int(t_lo)
+    if h < 0 or not 0 <= lo < T + h:
+        raise ValueError("horizon must be >= 0 and t_lo a row of the output")
+    if len(tg) and (tg[:, 0].min() < lo or tg[:, 0].max() >= T + h or tg[:, 1].min() < 0 or tg[:, 1].max() >= N):
+        raise ValueError("a target is (t, k) with t_lo <= t < T + horizon and 0 <= k < N")
+    ctx = ctx or default_context()
+    any_low = mixed is not None and bool(mixed[0].any())
+    params, r, _keep = _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, len(mixed[1]) if any_low else 0)
+    xo, xn = np.asfortranarray(xo), np.asfortranarray(xn)
+    if releases is None:
+        rel = np.argwhere(~np.isnan(xn) & np.isnan(xo)).astype(np.int64)   # row-major scan: sorted by (t, i)
+    else:
+        rel = np.asarray(releases, dtype=np.int64).reshape(-1, 2)
+    J, Tt = len(rel), T + h
+    rt, ri = np.ascontiguousarray(rel[:, 0]), np.ascontiguousarray(rel[:, 1])
+    sm = np.zeros((3, Tt, r))
+    agg = np.zeros((3, Tt, r)) if any_low else None
+    news, fc = np.zeros(J), np.zeros(J)
+    wf = np.zeros((J, Tt - lo, r))
+    wa = np.zeros((J, Tt - lo, r)) if any_low else None
+    sl = lambda a, k: None if a is None else _dptr(a[k])   # noqa: E731
+    out = _lib.dfm_ss_news_out(_dptr(sm[0]), _dptr(sm[1]), _dptr(sm[2]), sl(agg, 0), sl(agg, 1), sl(agg, 2),
+                               _dptr(news), _dptr(fc), _dptr(wf), _dptr(wa))
+    spec = _lib.dfm_ss_news_spec(h, lo, int(pass_releases or 0))
+    mf = None if mixed is None else _ss_mf_struct(mixed)
+    ctx.check(ctx.lib.dfm_ss_news(ctx.h, _dptr(xo), _dptr(xn), T, N, T, C.byref(params),
+                                  None if mf is None else C.byref(mf), C.byref(spec), J,
+                                  rt.ctypes.data_as(_lib.c_int64_p), ri.ctypes.data_as(_lib.c_int64_p), C.byref(out)))
+    # ---- the targets: lambda_k' (f_t|T or the aggregate, by k's class), back in original units
+    Lm = _f64(loadings, 2)
+    tt, tk = tg[:, 0], tg[:, 1]
+    lowk = mixed[0][tk].astype(bool) if any_low else np.zeros(len(tg), dtype=bool)
+    path = [np.where(lowk[:, None], agg[v][tt], sm[v][tt]) if any_low else sm[v][tt] for v in range(3)]
+    val = [np.einsum("kr,kr->k", Lm[tk], pv) * sd[tk] + mu[tk] for pv in path]
+    wt = wf[:, tt - lo, :]                                   # (J, K, r)
+    if any_low:
+        wt = np.where(lowk[None, :, None], wa[:, tt - lo, :], wt)
+    impacts = np.einsum("kr,jkr->kj", Lm[tk], wt) * news[None, :] * sd[tk][:, None]
+    by_series = np.zeros((len(tg), N))
+    if J:
+        np.add.at(by_series.T, ri, impacts.T)
+    return NewsResult(rel, news, fc, wf, wa, sm[0], sm[1], sm[2], *(3 * [None] if agg is None else list(agg)),
+                      tg, val[0], val[1], val[2], val[1] - val[0], impacts, by_series, lo)
+
+
 def _ss_start_axis(v, base_ndim, name):
     """(array, has a leading panel axis) of one start parameter; a list of
     per-panel arrays must be of one shape."""

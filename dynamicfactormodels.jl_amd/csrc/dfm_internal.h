@@ -428,6 +428,10 @@ int ss_mf_args(dfm_ctx *ctx, const char *who, const dfm_ss_mf *mf, int64_t N, bo
 int64_t ss_mf_pad_params(const dfm_ss_params *sets, int64_t n, int r, int p, int L, std::vector<dfm_ss_params> &padded,
                          std::vector<double> &Apad);
 
+// ---- dfm_ss_sim.hip
+// in: rows x n (n fastest, as the lanes of ss_sim_kernel / ss_news_kernel store) -> out: n x rows.
+hipError_t launch_ss_transpose(const double *in, int64_t rows, int64_t n, double *out, hipStream_t st);
+
 // ---- dfm_ss_em.hip
 // mf: the mixed-frequency model (checked): the starts are then the padded
 // state's (p = max(p_var, n_w), A = [A 0]), p_var the VAR's own lag count

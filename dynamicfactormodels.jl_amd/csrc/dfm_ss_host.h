@@ -7,7 +7,9 @@
 // [A 0], Z_l and the fit's start values of the low series; the panels per
 // pass of both drivers; of the simulation smoother (dfm_ss_sim.hip) the
 // factor of a positive semi-definite matrix, the count of normals, the
-// argument checks and the draws per pass.
+// argument checks and the draws per pass; of the news decomposition
+// (dfm_ss_news.hip) the argument checks, the check of the release list, the
+// revised panel and the releases per pass.
 // No HIP includes: a plain C++ compiler builds it alone (tests/c_harness).
 //
 // Layout: every matrix the caller passes is column-major (include/dfm.h);
@@ -450,6 +452,80 @@ inline int64_t ss_sim_draws_per_pass(int64_t Tt, int r, int s, int64_t D, int64_
   if (n > 64) n &= ~(int64_t)63;
   if (n < 1) n = 1;
   return n < D ? n : D;
+}
+
+// ------------------------------------------------ the news decomposition (dfm_ss_news)
+constexpr int64_t SS_NEWS_JMAX = (int64_t)1 << 24;   // releases per call
+
+// The call's own arguments: 0 <= J <= 2^24 with both lists present when J > 0,
+// 0 <= horizon <= 2^20, 0 <= t_lo < T + horizon, pass_releases >= 0.
+inline int ss_news_check_args(int64_t J, bool have_lists, int64_t T, int64_t horizon, int64_t t_lo,
+                              int64_t pass_releases) {
+  if (J < 0 || J > SS_NEWS_JMAX || (J > 0 && !have_lists)) return -2;
+  if (T < 1 || horizon < 0 || horizon > (1 << 20) || pass_releases < 0) return -2;
+  return (t_lo < 0 || t_lo >= T + horizon) ? -2 : 0;
+}
+
+// Why a release list is refused (ss_news_check_releases), in the order it is looked for.
+enum SsNewsBad {
+  SS_NEWS_OK = 0,
+  SS_NEWS_RANGE,       // an entry outside the panel
+  SS_NEWS_UNSORTED,    // an entry before its predecessor in (t, i)
+  SS_NEWS_DUPLICATE,   // an entry equal to its predecessor
+  SS_NEWS_DROPPED,     // observed in X_old, NaN in X_new: the old set is no subset of the new one
+  SS_NEWS_NOT_NEW,     // a listed entry that is NaN in X_new or observed in X_old
+  SS_NEWS_MISSING      // a release (observed in X_new, NaN in X_old) that the list leaves out
+};
+
+// The list must be exactly the entries observed in X_new and NaN in X_old,
+// sorted by (t, i).  First the list alone (range, order), then the panels row
+// by row; *bt, *bi: the first offending entry.  Panels column-major T x N (ldx).
+inline SsNewsBad ss_news_check_releases(const double *X_old, const double *X_new, int64_t T, int64_t N, int64_t ldx,
+                                        int64_t J, const int64_t *rel_t, const int64_t *rel_i, int64_t *bt,
+                                        int64_t *bi) {
+  auto bad = [&](SsNewsBad why, int64_t t, int64_t i) {
+    *bt = t, *bi = i;
+    return why;
+  };
+  for (int64_t j = 0; j < J; ++j) {
+    const int64_t t = rel_t[j], i = rel_i[j];
+    if (t < 0 || t >= T || i < 0 || i >= N) return bad(SS_NEWS_RANGE, t, i);
+    if (j == 0) continue;
+    if (t == rel_t[j - 1] && i == rel_i[j - 1]) return bad(SS_NEWS_DUPLICATE, t, i);
+    if (t < rel_t[j - 1] || (t == rel_t[j - 1] && i < rel_i[j - 1])) return bad(SS_NEWS_UNSORTED, t, i);
+  }
+  int64_t j = 0;
+  for (int64_t t = 0; t < T; ++t)
+    for (int64_t i = 0; i < N; ++i) {
+      const bool o = !isnan(X_old[i * ldx + t]), n = !isnan(X_new[i * ldx + t]);
+      const bool listed = j < J && rel_t[j] == t && rel_i[j] == i;
+      if (o && !n) return bad(SS_NEWS_DROPPED, t, i);
+      if (listed && !(n && !o)) return bad(SS_NEWS_NOT_NEW, t, i);
+      if (!listed && n && !o) return bad(SS_NEWS_MISSING, t, i);
+      if (listed) ++j;
+    }
+  return SS_NEWS_OK;
+}
+
+// X_rev: X_new's values on the old observed set, NaN elsewhere (T x N, ld T).
+inline void ss_news_revised(const double *X_old, const double *X_new, int64_t T, int64_t N, int64_t ldx, double *X_rev) {
+  for (int64_t i = 0; i < N; ++i)
+    for (int64_t t = 0; t < T; ++t) X_rev[i * T + t] = isnan(X_old[i * ldx + t]) ? NAN : X_new[i * ldx + t];
+}
+
+// Releases per pass.  pass_releases > 0: that many (at the most J).  Otherwise
+// the half-GB rule over the doubles a release keeps on the device: c_t|t (Tt x
+// s), its weights as the lanes store them and as they leave for the host (2
+// (Tt - t_lo) r, twice with the aggregate's), beta (r) and its row and class;
+// rounded down to whole waves of 64 once there is more than one.
+inline int64_t ss_news_releases_per_pass(int64_t Tt, int64_t t_lo, int r, int s, bool agg, int64_t J,
+                                         int64_t pass_releases) {
+  if (pass_releases > 0) return pass_releases < J ? pass_releases : J;
+  const int64_t per = 8 * (Tt * s + (agg ? 4 : 2) * (Tt - t_lo) * r + r + 1);
+  int64_t n = ((int64_t)1 << 29) / per;
+  if (n > 64) n &= ~(int64_t)63;
+  if (n < 1) n = 1;
+  return n < J ? n : J;
 }
 
 }  // namespace dfm

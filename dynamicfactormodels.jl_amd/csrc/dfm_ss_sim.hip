@@ -24,6 +24,7 @@
 #include "dfm_host.h"
 #include "dfm_small.h"
 #include "dfm_ss_host.h"
+#include "dfm_ss_lane.h"
 
 namespace {
 
@@ -154,27 +155,6 @@ struct SsSimArgs {
   const double *cst;     // a0 (s), L0 (s x s), the companion matrix's first r rows (r x s), Lq (r x r), row-major
   double *cf, *out;      // c_t|t [Tt][s][n] and the draws [Tt][r][n]
 };
-
-// v + sum_{k<n} a[k] x[64 k] (NEG: v - sum), the products added in the order of k: a from the
-// staged record or the constants (a broadcast read), x a lane's column.  Eight
-// pairs are read before their multiply-adds run, so a round costs one LDS
-// latency, not eight: the chain of a lane is serial and nothing else hides it.
-template <bool NEG>
-DFM_DEV double sim_dot(double v, const double *a, const double *x, int n) {
-  int k = 0;
-  for (; k + 8 <= n; k += 8) {
-    double av[8], xv[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      av[q] = a[k + q];
-      xv[q] = x[(k + q) * 64];
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v = fma(NEG ? -av[q] : av[q], xv[q], v);
-  }
-  for (; k < n; ++k) v = fma(NEG ? -a[k] : a[k], x[k * 64], v);
-  return v;
-}
 
 constexpr int SS_SIM_PRE = 17;   // 64 SS_SIM_PRE >= the forward record and J_t at r = 16, s = 32
 
@@ -370,12 +350,8 @@ struct SimRun : SsAfter {
       HIPCHK(ctx, hipGetLastError());
       {
         Scope sc(ctx, DFM_KC_GEMM);
-        const int nxt = (int)((n + 31) / 32);
-        const int64_t nyt = ((int64_t)per_out + 31) / 32;
-        hipLaunchKernelGGL(ss_sim_transpose_kernel, dim3((unsigned)(nxt * nyt)), dim3(256), 0, st, (const double *)o1,
-                           (int64_t)per_out, n, nxt, o2);
+        HIPCHK(ctx, launch_ss_transpose(o1, (int64_t)per_out, n, o2, st));
       }
-      HIPCHK(ctx, hipGetLastError());
       HIPCHK(ctx, hipMemcpyAsync(draws + (size_t)d0 * per_out, o2, (size_t)n * per_out * 8, hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
     }
@@ -384,6 +360,13 @@ struct SimRun : SsAfter {
 };
 
 }  // namespace
+
+hipError_t dfm::launch_ss_transpose(const double *in, int64_t rows, int64_t n, double *out, hipStream_t st) {
+  const int nxt = (int)((n + 31) / 32);
+  const int64_t nyt = (rows + 31) / 32;
+  hipLaunchKernelGGL(ss_sim_transpose_kernel, dim3((unsigned)(nxt * nyt)), dim3(256), 0, st, in, rows, n, nxt, out);
+  return hipGetLastError();
+}
 
 extern "C" int dfm_ss_simulate(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx,
                                const dfm_ss_params *params, const dfm_ss_sim_spec *spec, int64_t D, const double *z,

@@ -758,6 +758,72 @@ int dfm_ss_simulate(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t
                     double *draws /* host, D x (T+h) x r row-major */,
                     double *smoothed, double *smoothed_cov, double *loglik /* as dfm_ss_smooth, M = 1; any NULL */);
 
+/* News decomposition of a forecast revision (Banbura & Modugno 2014),
+ * dfm_ss_news (dfm_ss_news.hip): which release moved the smoothed path between
+ * two vintages of one panel, and by how much.  Two vintages X_old, X_new of one
+ * T x N panel share the parameters; Omega_new contains Omega_old, the observed
+ * sets.  The releases are the J entries (t_j, i_j) observed in X_new and NaN
+ * in X_old.  Entries observed in both may differ (a revision): X_rev has
+ * X_new's values on Omega_old and NaN elsewhere.  Three smoothed states over
+ * Tt = T + h rows: a_t|old, a_t|rev, a_t|new.  The revision effect is a|rev -
+ * a|old, the news effect a|new - a|rev.
+ *
+ * The news of release j, with c(i) the class of series i and Z_h, Z_l as above
+ * (the plain model has the high class only):
+ *   I_j = x_new[t_j, i_j] - lambda_{i_j}' Z_{c(i_j)} a_{t_j}|rev
+ *   (release_forecast_j is the subtracted term).
+ * The weights are the smoother's impulse responses under the NEW mask.  For
+ * release j, from c = 0 (s entries), the rows forwards; within a row the
+ * classes in the filter's order, and for each class with n^c_t > 0
+ *   z = Z_c c
+ *   d = beta - C^c_t z,  beta = lambda_{i_j} / sigma^2_{i_j} if t = t_j and c = c(i_j), else 0
+ *   c <- c + K^c_t d
+ * then c_t|t = c and c <- Tm c.  K^c_t = PZ G^-1 exactly as the filter forms
+ * it: the second class of a row uses the P left by the first class's update,
+ * a product local to the row that starts from the stored P_t|t-1.  Backwards
+ *   c_{Tt-1|T} = c_{Tt-1|Tt-1};  c_t|T = c_t|t + J_t (c_{t+1|T} - Tm c_t|t),
+ *   J_t = P_t|t Tm' P_{t+1|t}^-1.
+ * The weights of release j at row t are wf_j[t] = c_t|T[:r] and wagg_j[t] =
+ * Z_l c_t|T.  The smoother is affine in the data, and observing a value equal
+ * to its conditional mean moves nothing, so for every row t, forecast rows
+ * included,
+ *   a_t|new - a_t|rev = sum_j I_j c^j_t|T.
+ * For a target (t, k) the impact of release j is lambda_k' (wf_j[t], or
+ * wagg_j[t] when k is a low series) I_j.
+ *
+ * The covariance recursion is not repeated: the gains C^c_t, K^c_t, J_t are
+ * formed once per row and a release is a mean-only recursion, one GPU lane
+ * each, that starts at its own row t_j and runs backwards down to t_lo.  A
+ * release's weights depend on neither J, its position in the list nor the
+ * pass it falls in; they depend on X_new's mask only.
+ *
+ * X_old, X_new: host, column-major T x N (one ldx).  mf: NULL, or without a
+ * marked series, is the plain model.  rel_t, rel_i (J each): the list must be
+ * exactly the releases, sorted by (t, i): -2 otherwise, and -2 for an entry
+ * observed in X_old and NaN in X_new; the message names the first offending
+ * entry.  J = 0 is valid: the smooths are returned and nothing else runs.
+ * Other codes are dfm_ss_smooth_mf's; -2 also for J > 2^24, t_lo outside
+ * [0, T + h) and pass_releases < 0. */
+typedef struct dfm_ss_news_spec {
+  int32_t horizon;          /* h >= 0 forecast rows */
+  int32_t t_lo;             /* the weights cover the rows t_lo .. T + h - 1 */
+  int64_t pass_releases;    /* 0: the workspace rule; > 0: at most that many releases per pass */
+} dfm_ss_news_spec;
+/* Host memory, any may be NULL.  The smoothed rows as dfm_ss_smooth_mf returns
+ * them for X_old, X_rev and X_new, bit for bit ((T+h) x r row-major; the
+ * aggregates are not written for the plain model); news and release_forecast
+ * J; weights_f and weights_agg J x (T + h - t_lo) x r row-major (weights_agg
+ * is not written for the plain model). */
+typedef struct dfm_ss_news_out {
+  double *smoothed_old, *smoothed_rev, *smoothed_new;
+  double *smoothed_agg_old, *smoothed_agg_rev, *smoothed_agg_new;
+  double *news, *release_forecast;
+  double *weights_f, *weights_agg;
+} dfm_ss_news_out;
+int dfm_ss_news(dfm_ctx *ctx, const double *X_old, const double *X_new, int64_t T, int64_t N, int64_t ldx,
+                const dfm_ss_params *params, const dfm_ss_mf *mf, const dfm_ss_news_spec *spec, int64_t J,
+                const int64_t *rel_t, const int64_t *rel_i, const dfm_ss_news_out *out);
+
 /* --------------------------------------------------- targeted predictors
  * targeted_predictors(..., thresholding="hard") (src/targeted_predictors.jl:9-30).
  * JOINT: OLS of y on [w x], White HC0, |t_x| > crit_value (the reference's
