@@ -96,9 +96,11 @@ class Context:
         self.check(self.lib.dfm_ctx_gemm_products(self.h, C.byref(gp)))
         g32 = C.c_int64()
         self.check(self.lib.dfm_ctx_gemm_products_f32(self.h, C.byref(g32)))
+        gsl = C.c_int64()
+        self.check(self.lib.dfm_ctx_gemm_products_split_last(self.h, C.byref(gsl)))
         return {"batches": b.value, "iterations": t.value, "max_iterations": m.value,
                 "replicate_iterations": ri.value, "gemm_products": gp.value,
-                "gemm_products_f32": g32.value}
+                "gemm_products_f32": g32.value, "gemm_products_split_last": gsl.value}
 
     def close(self):
         if getattr(self, "h", None) and not _lib.shutting_down():

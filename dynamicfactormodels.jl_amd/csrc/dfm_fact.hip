@@ -1696,8 +1696,8 @@ static bool warm_keep_step0() {   // (read at every solve: one process can run b
 // EL a and F'F stay fp64) is damped by the fp64 product that follows.  The
 // CPU model (tools/eig_proto.py, F32 / NOISE) retires the same replicates at
 // the same steps with 64 times the fp32 noise in those products.  The last
-// product stays fp64: its rows go to the Rayleigh-Ritz step with no fp64
-// product behind them (the model degrades at 16 times the noise).  The strict
+// product stayed fp64 in round 8 (the model degrades at 16 times the noise;
+// round 19 measured the margin and moved it: fact_split_last_off).  The strict
 // and subspace rules keep fp64 throughout: they bound the eigenvector
 // residual, which is linear in the subspace error (the model needs more
 // products there).  DFM_FACT_F32=0 (A/B only, read at every solve) restores
@@ -1720,6 +1720,20 @@ static bool fact_f32_off() {
 // only, read at every solve) restores the fp32 launches bit for bit.
 static bool fact_split_off() {
   const char *e = getenv("DFM_FACT_SPLIT");
+  return e && atoi(e) == 0;
+}
+// With them the filter's last product, number d0, runs on the same kernel
+// (round 19): its last middle step hands it bf16 planes like the others, and
+// the GEMM's second epilogue writes hmax C32 as fp64 rows of HZ, which the last
+// Horner step gathers as it gathers an fp64 product's.  The argument is the
+// one above: the product shapes the subspace and no more, the Rayleigh-Ritz
+// product and the residual test behind it are fp64; the model (DESIGN.md
+// section 3, round 19) moves no replicate up to four times fp32's noise and
+// one in 400 at eight, and the split kernel's error is 0.82 of fp32's.
+// DFM_FACT_SPLIT_LAST=0 (A/B only, read at every solve) restores the fp64
+// launch bit for bit.
+static bool fact_split_last_off() {
+  const char *e = getenv("DFM_FACT_SPLIT_LAST");
   return e && atoi(e) == 0;
 }
 static bool ap2_probe_off() {
@@ -1822,6 +1836,20 @@ __global__ __launch_bounds__(1024) void q0_guards_kernel(double *__restrict__ Q0
     }
     __syncthreads();
   }
+}
+
+// Zero the pad rows T .. round_up(T, 16) - 1 of every replicate's fp64 Z (its
+// last 16-row chunk): gemmh_zrm_kernel reads them against H's zero k-padding,
+// so they must be finite.  A step 0 whose last product runs split
+// (fact_split_last_off) needs it: prep and every middle step wrote bf16 planes
+// there, no pass wrote the fp64 chunks, and the last Horner step (zscatter_tail)
+// stores rows < T only.  nb pz doubles per pad row, disjoint from those rows.
+__global__ void zpad_zero_kernel(double *__restrict__ Zc, int T, int pz, int64_t zrs, int nb) {
+  const int npad = ((T + 15) & ~15) - T;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)nb * pz * npad) return;
+  const int rep = (int)(i / (pz * npad)), e = (int)(i - (int64_t)rep * (pz * npad));
+  Zc[zrm_ix(rep, T + e % npad, e / npad, pz, zrs)] = 0.0;
 }
 
 // The kernel instances eig_run_fact2_t launches.  stg: the loaders staged
@@ -1942,6 +1970,8 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   // no such identity and always read stored PF.
   // ... as six bf16 terms on split operands where the model holds the split H (fact_split_off)
   const bool split = lowp && fb.Hs && !fact_split_off();
+  // ... the last product too, through that kernel's fp64 epilogue (fact_split_last_off)
+  const bool split_last = split && !fact_split_last_off();
   const bool nopf = skip0 && f.fscale > 0.0 && a.kw >= fb.r && !fact_pf_stored();
   // dynamic LDS above the default 64 KB cap: prep (24 T + 8 bytes) for T > 2730, the last Horner step (20 T + 4)
   // for T > 3276, ap2 (16 T + 4) at T = F2_T_MAX.  A refused cap is this solve's error, not a later launch's.
@@ -1992,6 +2022,18 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
               : launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
     return e == hipSuccess ? 0 : 1000 + (int)e;
   };
+  // ... or, product d0 of a split step 0, HZ = hmax HZ32 from the same planes, written as hz writes it (split_last).
+  // The fp64 Z's pad rows, which no pass of such a step wrote, are zeroed for the fp64 products that follow.
+  auto hz_split_rows = [&]() -> int {
+    TimerScope ts(a, DFM_KC_GEMM);
+    hipError_t e = launch_gemm_zrm_split_rows(fb.Hs, Zc, pz, zrs, HZ, ldz, fb.hmax, m, ncz, m, st);
+    if (e == hipSuccess && (m & 15)) {
+      const int64_t n = (int64_t)nb * pz * (16 - (m & 15));
+      hipLaunchKernelGGL(zpad_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Zc, m, pz, zrs, nb);
+      e = hipGetLastError();
+    }
+    return e == hipSuccess ? 0 : 1000 + (int)e;
+  };
   // a middle Horner step S_i = G* S_{i+1} / b + c V0 in row-local form (Z, a, cc only) ...
   // (lp: 0 = fp64 HZ in, fp64 Z out; 1 = HZ32 in, Z32 out; 2 = HZ32 in, fp64 Z out; 3 = HZ32 in, split Z out)
   auto horner_mid = [&](double c, double bbeta, double bfx, double lead, int lp = 0) {
@@ -2031,10 +2073,13 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     // left the Z, a, cc, PV, FV of Q0; a_d goes into the first step's scale),
     // d0 products, the last step writes the new basis into cur with its Z, a, cc
     // (lowp: products 1 .. d0 - 1 in fp32 — prep left Z0 as float, each middle step hands the next a float Z, the
-    // last of them an fp64 Z for product d0; split: bf16 planes where lowp has floats)
+    // last of them an fp64 Z for product d0; split: bf16 planes where lowp has floats; split_last: planes from the
+    // last middle step too, and product d0 on the split kernel with fp64 rows out)
     for (int sp = 1; sp <= d0; ++sp) {
-      if (int rc = (lowp && sp < d0) ? hz32() : hz(false)) return rc;
-      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, !lowp ? 0 : sp < d0 - 1 ? (split ? 3 : 1) : 2);
+      if (int rc = (lowp && sp < d0) ? hz32() : (split_last && sp == d0) ? hz_split_rows() : hz(false)) return rc;
+      if (sp < d0)
+        horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0,
+                   !lowp ? 0 : (sp < d0 - 1 || split_last) ? (split ? 3 : 1) : 2);
       else horner_last(ca0[0], 0.0, Q0, 0, bfix);
     }
     last_gemm = last_cheb = 0;
@@ -2114,6 +2159,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   if (steps < 0) steps = it;
   g_last_iters = steps;
   g_last_gemm_products_f32 = lowp ? (int64_t)(d0 - 1) * nb : 0;
+  g_last_gemm_products_split_last = split_last ? (int64_t)nb : 0;
   // the Chebyshev GEMM of iteration it runs after that iteration's check
   if (f.cnt) {   // (counted by eig_final_kernel below)
     g_last_rep_iters = g_last_gemm_products = 0;

@@ -1,7 +1,8 @@
-// dfm_fact_debug.hip — dfm_debug_hz_f32 (tests/test_gpu_f32_filter.py) and
-// dfm_debug_hz_split (tests/test_gpu_bf16_split.py): the fp32 and the
-// bf16-split H.Z GEMM of the factored solver's middle products, on operands
-// packed as the solver packs them (zrm_ix, Zs: dfm_internal.h).
+// dfm_fact_debug.hip — dfm_debug_hz_f32 (tests/test_gpu_f32_filter.py),
+// dfm_debug_hz_split (tests/test_gpu_bf16_split.py) and dfm_debug_hz_split_rows
+// (tests/test_gpu_split_last.py): the fp32 and the bf16-split H.Z GEMM of the
+// factored solver's warm filter, on operands packed as the solver packs them
+// (zrm_ix, Zs: dfm_internal.h).
 #include "dfm_internal.h"
 #include <vector>
 
@@ -112,5 +113,41 @@ extern "C" int dfm_debug_hz_split(dfm_ctx *ctx, const double *H, int64_t ldH, in
   hipFree(buf);
   if (e != hipSuccess) return 1000 + (int)e;
   if (hmax_out) *hmax_out = fact_hmax(hdh.data(), T);
+  return 0;
+}
+
+// The split product through the kernel's fp64 epilogue (round 19,
+// tests/test_gpu_split_last.py): the same Hs and Zs, and
+// launch_gemm_zrm_split_rows writes hmax C32 straight into the caller's out
+// (device, T rows of nb pz columns, row stride ldo >= nb pz).  Nothing of out
+// but those T x nb pz elements is written.
+extern "C" int dfm_debug_hz_split_rows(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
+                                       double *out, int64_t ldo, double *hmax_out) {
+  using namespace dfm;
+  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || pz > 32 || ldH < (T + 15) / 16 * 16 ||
+      ldo < (int64_t)nb * pz)
+    return -1;
+  hipStream_t st = ctx_stream(ctx);
+  const int64_t zrs = (int64_t)((T + 15) & ~15) * pz;
+  const int nch = (T + 15) >> 4;
+  char *buf = nullptr;
+  const size_t b_hd = ((size_t)T * 8 + 255) & ~size_t(255), b_hs = (hsplit_bytes(T) + 255) & ~size_t(255),
+               b_z = ((size_t)nb * zrs * 8 + 255) & ~size_t(255);
+  if (hipMalloc((void **)&buf, b_hd + b_hs + b_z) != hipSuccess) return 1002;
+  double *hd = (double *)buf;
+  char *Hs = buf + b_hd, *Zs = buf + b_hd + b_hs;
+  hipLaunchKernelGGL(dbg_diag_kernel, dim3((T + 255) / 256), dim3(256), 0, st, H, ldH, T, hd);
+  hipError_t e = launch_fact_hsplit(H, ldH, T, hd, Hs, st);
+  hipLaunchKernelGGL(dbg_pack_zs_kernel, dim3((unsigned)(((int64_t)nb * nch + 3) / 4)), dim3(256), 0, st, Z, T, nb, pz, Zs);
+  std::vector<double> hdh(T);   // hmax first: it is the launch's scale, as FactBase::hmax is the solver's
+  if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  const double hmax = e == hipSuccess ? fact_hmax(hdh.data(), T) : 1.0;
+  if (e == hipSuccess) e = launch_gemm_zrm_split_rows(Hs, Zs, pz, zrs, out, ldo, hmax, T, nb * pz, T, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(buf);
+  if (e != hipSuccess) return 1000 + (int)e;
+  if (hmax_out) *hmax_out = hmax;
   return 0;
 }

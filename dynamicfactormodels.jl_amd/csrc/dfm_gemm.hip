@@ -402,6 +402,10 @@ hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int 
 // 3-deep ring at 2 workgroups per CU (72 KB), six DMA instructions per wave
 // and stage.  Every output element adds its six terms in that order stage by
 // stage, whatever its tile, its place in the batch, nb or the lane.
+// ROWS64 (round 19, the warm filter's last product): the same accumulators
+// leave as fp64 rows scale * C32 of the column-interleaved HZ (row stride ldc)
+// that gemmh_zrm_kernel writes, instead of float chunk pieces; everything
+// before the epilogue is the same code.
 namespace {
 constexpr int SP_GT = 128, SP_KS = 16, SP_IMG = SP_GT * 16, SP_STAGE = 12 * SP_IMG;   // bytes
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -415,10 +419,12 @@ DFM_DEV void split_ring_wait(int s, int nst) {   // ring_wait at six DMA instruc
 }
 }  // namespace
 
+template <bool ROWS64>
 __global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__restrict__ Hs, int mrows,
                                                                 const char *__restrict__ Zs, int pz, int64_t zrs,
-                                                                float *__restrict__ C, int M, int Nc, int K, int nrb,
-                                                                int ncb) {
+                                                                std::conditional_t<ROWS64, double, float> *__restrict__ C,
+                                                                int M, int Nc, int K, int nrb, int ncb, int64_t ldc,
+                                                                double scale) {
   constexpr int NBUF = 3;
   __shared__ __attribute__((aligned(16))) char lds[NBUF * SP_STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -495,17 +501,30 @@ __global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__r
   for (int tj = 0; tj < 2; ++tj) {
     const int x = bbase + wc * 64 + 32 * tj + r32;
     if (x >= Nc) continue;
-    const int rep = x / pz, cc = x - rep * pz;
-    float *cp = C + (int64_t)rep * zrs + 16 * cc;
+    if constexpr (ROWS64) {
+      // hmax C32 as fp64 rows of HZ: a half-wave's 32 lanes write 32 consecutive columns of one row (256 B).  HZ
+      // has exactly M rows and no chunk pad rows, so every element has its own row test.
+      double *cp = C + x;
 #pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
+      for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int row = abase + wr * 64 + 32 * ti + 8 * g + 4 * hh;
-        if (row < M)   // (rows row .. row + 3 stay inside the chunk: its pad rows take discarded values)
-          *reinterpret_cast<f32x4 *>(cp + (int64_t)(row >> 4) * (16 * pz) + (row & 15)) =
-              f32x4{acc[ti][tj][4 * g], acc[ti][tj][4 * g + 1], acc[ti][tj][4 * g + 2], acc[ti][tj][4 * g + 3]};
-      }
+        for (int v = 0; v < 16; ++v) {
+          const int row = abase + wr * 64 + 32 * ti + 8 * (v >> 2) + 4 * hh + (v & 3);
+          if (row < M) cp[(int64_t)row * ldc] = scale * (double)acc[ti][tj][v];
+        }
+    } else {
+      const int rep = x / pz, cc = x - rep * pz;
+      float *cp = C + (int64_t)rep * zrs + 16 * cc;
+#pragma unroll
+      for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int row = abase + wr * 64 + 32 * ti + 8 * g + 4 * hh;
+          if (row < M)   // (rows row .. row + 3 stay inside the chunk: its pad rows take discarded values)
+            *reinterpret_cast<f32x4 *>(cp + (int64_t)(row >> 4) * (16 * pz) + (row & 15)) =
+                f32x4{acc[ti][tj][4 * g], acc[ti][tj][4 * g + 1], acc[ti][tj][4 * g + 2], acc[ti][tj][4 * g + 3]};
+        }
+    }
   }
 }
 
@@ -519,8 +538,24 @@ hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t
     return hipErrorInvalidValue;
   const int nrb = (M + SP_GT - 1) / SP_GT, ncb = (Nc + SP_GT - 1) / SP_GT;
   const int ncb8 = (ncb + 7) / 8 * 8;
-  hipLaunchKernelGGL(gemmh_zrm_split_kernel, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs, hsplit_rows(M),
-                     (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb);
+  hipLaunchKernelGGL(gemmh_zrm_split_kernel<false>, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs,
+                     hsplit_rows(M), (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb, (int64_t)0, 1.0);
+  return hipGetLastError();
+}
+
+// The same product delivered as fp64 rows, C (M x Nc, row stride ldc >= Nc) = scale C32 in launch_gemm_zrm's
+// column-interleaved layout (gemmh_zrm_split_kernel<true>): the last product of a warm filter (scale = hmax),
+// whose rows the last Horner step gathers as it gathers an fp64 product's.  Nothing outside rows < M and
+// columns < Nc is written.
+hipError_t launch_gemm_zrm_split_rows(const void *Hs, const void *Zs, int pz, int64_t zrs, double *C, int64_t ldc,
+                                      double scale, int M, int Nc, int K, hipStream_t st) {
+  const int64_t kpad = (K + SP_KS - 1) / SP_KS * SP_KS;
+  if (!Hs || !Zs || !C || M < 1 || pz < 1 || Nc < pz || Nc % pz || M != K || zrs < kpad * pz || (zrs & 3) || ldc < Nc)
+    return hipErrorInvalidValue;
+  const int nrb = (M + SP_GT - 1) / SP_GT, ncb = (Nc + SP_GT - 1) / SP_GT;
+  const int ncb8 = (ncb + 7) / 8 * 8;
+  hipLaunchKernelGGL(gemmh_zrm_split_kernel<true>, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs,
+                     hsplit_rows(M), (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb, ldc, scale);
   return hipGetLastError();
 }
 

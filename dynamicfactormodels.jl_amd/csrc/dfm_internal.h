@@ -135,6 +135,9 @@ inline int hsplit_rows(int T) { return (T + 127) & ~127; }
 inline size_t hsplit_bytes(int T) { return (size_t)((T + 15) / 16) * 6 * hsplit_rows(T) * 16; }
 hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
                                  hipStream_t st);
+// ... and C (M x Nc fp64, row stride ldc, launch_gemm_zrm's layout) = scale C32 from the same kernel's second epilogue
+hipError_t launch_gemm_zrm_split_rows(const void *Hs, const void *Zs, int pz, int64_t zrs, double *C, int64_t ldc,
+                                      double scale, int M, int Nc, int K, hipStream_t st);
 hipError_t launch_gemm_loadings(const double *Eaug, int64_t lda, const double *ZF, int Kp, int rp, int N, int nrep,
                                 int K, int r, double invT, double *Lout, hipStream_t st);
 int gram_dma_slots(int m);
@@ -152,6 +155,7 @@ extern thread_local int g_last_iters;   // per host thread: dfm_bootstrap_multi'
 extern thread_local int64_t g_last_rep_iters;
 extern thread_local int64_t g_last_gemm_products;
 extern thread_local int64_t g_last_gemm_products_f32;   // of those, the fp32 ones (factored solver, host-counted)
+extern thread_local int64_t g_last_gemm_products_split_last;   // ... and the warm filter's last products run split
 int eig_block_p(int m, int k, int req);
 int fact_block_p(int m, int k, int req);
 // What both solvers take besides the matrix.  Callers fill the members by name.

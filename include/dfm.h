@@ -118,6 +118,10 @@ int dfm_ctx_gemm_products(dfm_ctx *ctx, int64_t *products);
  * warm eigenvalue-rule solve's filter-only first step ((d0 - 1) nb per solve;
  * 0 under the strict rule or with DFM_FACT_F32=0). */
 int dfm_ctx_gemm_products_f32(dfm_ctx *ctx, int64_t *products);
+/* The last products of those filters run as six bf16 terms with an fp64 store
+ * (nb per such solve; 0 under the strict rule, with DFM_FACT_F32=0,
+ * DFM_FACT_SPLIT=0 or DFM_FACT_SPLIT_LAST=0).  Not part of the fp32 count. */
+int dfm_ctx_gemm_products_split_last(dfm_ctx *ctx, int64_t *products);
 int dfm_ctx_rep_iters(dfm_ctx *ctx, int64_t *rep_iters);
 const char *dfm_kernel_class_name(int cls);
 

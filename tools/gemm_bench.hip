@@ -140,7 +140,8 @@ __global__ void fillbf(uint16_t *p, size_t n, float s) {
 // beside gemmh_zrm_kernel on the same shape in fp64.  Operands in the chunk
 // layout, every element set (pad rows included: timing only).  Round 15:
 // gemmh_zrm_split_kernel (the same products as six bf16 terms) beside them, on
-// random planes.
+// random planes.  Round 19: the split kernel's fp64 epilogue (zrm_split64: the same
+// product stored as fp64 rows of the column-interleaved HZ, launch_gemm_zrm_split_rows).
 static void bench_f32() {
   const int T = 500, pz = 12;
   const int64_t lda = (T + 15) / 16 * 16, zrs = lda * pz;
@@ -159,9 +160,10 @@ static void bench_f32() {
     fill<<<((size_t)T * lda + 255) / 256, 256>>>(A64, (size_t)T * lda, 1.0, lda, T);
     fill<<<((size_t)nb * zrs + 255) / 256, 256>>>(Z64, (size_t)nb * zrs, 2.0, 1, 1);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int v = 0; v < 3; ++v) {
+    for (int v = 0; v < 4; ++v) {
       auto run = [&]() {
-        if (v == 2) launch_gemm_zrm_split(Hs, Zs, pz, zrs, C, T, Nc, T, 0);
+        if (v == 3) launch_gemm_zrm_split_rows(Hs, Zs, pz, zrs, C64, Nc, 3.0, T, Nc, T, 0);
+        else if (v == 2) launch_gemm_zrm_split(Hs, Zs, pz, zrs, C, T, Nc, T, 0);
         else if (v == 0) launch_gemm_zrm_f32(A, lda, Z, pz, zrs, C, T, Nc, T, 0);
         else launch_gemm_zrm(A64, lda, Z64, pz, zrs, C64, Nc, T, Nc, T, 0, nullptr, nullptr, nullptr);
       };
@@ -174,7 +176,7 @@ static void bench_f32() {
       const double t = ms / reps * 1e-3, fl = 2.0 * T * (double)Nc * T, peak = v == 1 ? 78.6 : 157.3;
       // (zrm_split: the fp32-equivalent rate, one product's flops; it issues six times as many on the bf16 path)
       printf("%s M=K=%d pz=%d nb=%5d : %8.3f ms  %6.2f TF/s (%.1f%% of %.1f)  [%s]\n",
-             v == 0 ? "zrm_f32  " : v == 1 ? "zrm_f64  " : "zrm_split", T,
+             v == 0 ? "zrm_f32    " : v == 1 ? "zrm_f64    " : v == 2 ? "zrm_split  " : "zrm_split64", T,
              pz, nb, t * 1e3, fl / t / 1e12, fl / t / 1e12 / peak * 100, peak, hipGetErrorString(hipGetLastError()));
     }
     hipFree(Hs); hipFree(Zs);
