@@ -11,13 +11,15 @@
 // replicates.  H Z for a whole batch is ONE MFMA GEMM (dfm_gemm.hip) with H
 // resident in L2; everything else is O(T r p) per replicate.
 #include "dfm_eig.h"
+#include "dfm_fact_plan.h"
 #include "dfm_fact_ws.h"
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 namespace dfm {
+
+static_assert(kFilterDMax == kChebDMax, "the plan's products and shifted_cheb's coefficients share one highest degree");
 
 // waves per replicate workgroup of the factored passes (prep, y2, ap2, Chebyshev)
 constexpr int BW = 4;
@@ -26,6 +28,25 @@ constexpr int BW = 4;
 // middle products' Z32 and HZ32 use it with float elements, Z32 in the first
 // half of Z's region, HZ32 in HZ's)
 typedef float zf4 __attribute__((ext_vector_type(4)));
+
+// A staged 16-row Z chunk (st: 16 pz doubles, element 16 c + row, this wave's LDS) to replicate rep's chunk `tile` of
+// Zc as whole 16-B pieces, in the format the next H.Z product reads: fp64, float (round to nearest, the same chunk
+// indexing with float elements) or the chunk's 6 pz pieces of the three bf16 planes (dfm_internal.h: Zs).
+template <int P>
+DFM_DEV void zchunk_store(ZFmt zf, const double *st, double *__restrict__ Zc, int rep, int64_t zrs, int tile, int pz,
+                          int lane) {
+  if (zf == ZFmt::Split) {
+    zsplit_store_chunk<P == 16>(st, pz, lane, reinterpret_cast<char *>(Zc + (int64_t)rep * zrs) +
+                                                  (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz);
+  } else if (zf != ZFmt::F64) {
+    zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+    for (int e = lane; e < 4 * pz; e += 64)
+      zc4[e] = zf4{(float)st[4 * e], (float)st[4 * e + 1], (float)st[4 * e + 2], (float)st[4 * e + 3]};
+  } else {
+    double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
+    for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{st[2 * e], st[2 * e + 1]};
+  }
+}
 
 // a = F'Q0 of the first product for the whole batch: F and the warm start Q0
 // are shared by every replicate, so this one workgroup forms the 16 x P block
@@ -77,22 +98,18 @@ __global__ __launch_bounds__(64 * BW) void prep_a_kernel(FactBase fb, const doub
   }
 }
 
-// Shared tail of prep, ap2 and the last Horner step: Z = P' D Qn by CSR gather
-// (bucket s lists t ascending), cc = EL' Z, and ab[rep] = [a (16 x P); cc
-// (16 x P)], a = F' Qn, with fixed-order wave sums.
-// From ap2 / the last Horner step (PREP = false) a is the caller's
-// accumulator aacc and Z is stored directly.  From prep (PREP = true) a is
-// copied from apre (prep_a_kernel), a tile's Z chunk (16 rows x pz,
-// contiguous in the replicate-major layout) leaves through this wave's LDS
-// stage zst (16 pz doubles) as 16-B pieces instead of one 128-B-strided
-// element per lane, as float if z32 == 1, as the three bf16 planes of
-// gemmh_zrm_split_kernel's Zs if z32 == 2, and the same rows go to pvr (PV) if set.
-// The staged store measured -3 % in prep and +0.3 % in ap2 / the last Horner
-// step (profiles/r06_c3_ab.txt item 13), so those store directly.
+// Shared tail of prep, ap2 and the last Horner step: Z = P' D Qn by CSR gather (bucket s lists t ascending),
+// cc = EL' Z, and ab[rep] = [a (16 x P); cc (16 x P)], a = F' Qn, with fixed-order wave sums.
+// From ap2 / the last Horner step (PREP = false) a is the caller's accumulator aacc and Z is stored directly.  From
+// prep (PREP = true) a is copied from apre (prep_a_kernel), a tile's Z chunk (16 rows x pz, contiguous in the
+// replicate-major layout) leaves through this wave's LDS stage zst (16 pz doubles) as 16-B pieces instead of one
+// 128-B-strided element per lane, in the format zf (zchunk_store), and the same rows go to pvr (PV) if set.
+// The staged store measured -3 % in prep and +0.3 % in ap2 / the last Horner step (profiles/r06_c3_ab.txt item 13),
+// so those store directly.
 struct PrepTail {   // PREP = true
   const double *apre;
   double *zst, *pvr;
-  int z32;
+  ZFmt zf;
 };
 struct AccTail {   // PREP = false
   const dv4 *aacc;
@@ -174,17 +191,7 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
         for (int ct = 0; ct < NT; ++ct)
           if (16 * ct + li < pz) zst[16 * (16 * ct + li) + 4 * g + lk] = s0 + 4 * g + lk < T ? z[g][ct] : 0.0;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (src.z32 == 2) {   // the bf16-split H.Z GEMM's operand: the chunk's 6 pz pieces (dfm_internal.h: Zs)
-        zsplit_store_chunk<P == 16>(zst, pz, lane, reinterpret_cast<char *>(Zc + (int64_t)rep * zrs) +
-                                                       (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz);
-      } else if (src.z32) {   // the fp32 H.Z GEMM's operand: the same chunk indexing, float elements (round to nearest)
-        zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
-        for (int e = lane; e < 4 * pz; e += 64)
-          zc4[e] = zf4{(float)zst[4 * e], (float)zst[4 * e + 1], (float)zst[4 * e + 2], (float)zst[4 * e + 3]};
-      } else {
-        double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
-        for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{zst[2 * e], zst[2 * e + 1]};
-      }
+      zchunk_store<P>(src.zf, zst, Zc, rep, zrs, tile, pz, lane);
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -224,14 +231,11 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
   }
 }
 
-// Per replicate: CSR of idx (bucket s lists t ascending — fixed summation
-// order, bit-reproducible), PF = P'D F and e2 = P'D^2 1 for the middle Horner
-// steps, and trace(G*) = sum_t ||x*_t||^2 =
-// sum_t [F_t S F_t' + 2 eta_t F_t.(EL)_idx_t + eta_t^2 H_idx_t,idx_t];
-// then, from the CSR it still holds in LDS, the first H.Z product's operand
-// Z0 = P'D Q0 and the first step's ab = [a; cc] (a = F'Q0 from apre,
-// prep_a_kernel; cc = EL'Z0) through zscatter_tail.  Q0, Zc, ab and apre are
-// required; PF, E2, PV, FV are optional outputs.
+// Per replicate: CSR of idx (bucket s lists t ascending — fixed summation order, bit-reproducible), PF = P'D F and e2
+// = P'D^2 1 for the middle Horner steps, and trace(G*) = sum_t ||x*_t||^2 = sum_t [F_t S F_t' + 2 eta_t
+// F_t.(EL)_idx_t + eta_t^2 H_idx_t,idx_t]; then, from the CSR it still holds in LDS, the first H.Z product's operand
+// Z0 = P'D Q0 and the first step's ab = [a; cc] (a = F'Q0 from apre, prep_a_kernel; cc = EL'Z0) through
+// zscatter_tail.  Q0, Zc, ab and apre are required; PF, E2, PV, FV are optional outputs.
 template <int P>
 __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const int32_t *__restrict__ idx,
                                                             const double *__restrict__ eta, int *__restrict__ off,
@@ -240,9 +244,8 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
                                                             const double *__restrict__ Q0, int ps,
                                                             double *__restrict__ Zc, int64_t ldz, int pz,
                                                             double *__restrict__ ab, const double *__restrict__ apre,
-                                                            double *__restrict__ PV, double *__restrict__ FV, int z32) {
-  // z32: Z0 leaves as float (1: the first product runs in fp32) or as three bf16 planes (2: as six bf16 terms);
-  // PV, FV, a, cc stay fp64
+                                                            double *__restrict__ PV, double *__restrict__ FV, ZFmt zf) {
+  // zf: the format Z0 leaves in (the first product's operand, FilterPlan::z0); PV, FV, a, cc stay fp64
   static_assert(64 * BW == 256, "the scans and the tree sum below are written for 256 threads");
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
@@ -276,11 +279,9 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
   __syncthreads();
   for (int s = tid; s <= T; s += 256) off[(int64_t)rep * (T + 1) + s] = cnt[s];
   __syncthreads();
-  // placement: LDS atomics hand out slots inside each bucket (any order),
-  // then each bucket is insertion-sorted by t — ascending t per bucket, the
-  // serial counting sort's order, in O(T) work (buckets are short)
-  // (in LDS, then one coalesced copy out: the shifts of a sort in global
-  // memory were chains of dependent global round trips)
+  // placement: LDS atomics hand out slots inside each bucket (any order), then each bucket is insertion-sorted by t —
+  // ascending t per bucket, the serial counting sort's order, in O(T) work (buckets are short) (in LDS, then one
+  // coalesced copy out: the shifts of a sort in global memory were chains of dependent global round trips)
   int *L = sh + 2 * T + 1;
   for (int t = tid; t < T; t += 256) L[atomicAdd(&cnt[six[t]], 1)] = t;
   __syncthreads();   // cnt[s] is now the END of bucket s; L visible workgroup-wide
@@ -355,8 +356,8 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
     {
       const int64_t zrs = zrm_stride(T, pz);
       const int npad = ((T + 15) & ~15) - T;
-      if (z32 == 2) {   // (the staged store writes the whole last chunk, its zero pad rows included)
-      } else if (z32)
+      if (zf == ZFmt::Split) {   // (the staged store writes the whole last chunk, its zero pad rows included)
+      } else if (zf != ZFmt::F64)
         for (int e = tid; e < npad * pz; e += 256)
           reinterpret_cast<float *>(Zc)[zrm_ix(rep, T + e / pz, e % pz, pz, zrs)] = 0.0f;
       else
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
     // (PV, FV: a warm solve without a first Rayleigh-Ritz step filters V0 = Q0 itself, so the middle Horner
     // steps' PV = P'D V0 is Z0 row by row and FV = F'V0 is a)
     zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, sred, ps,
-                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, z32});
+                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, zf});
     if (FV)
       for (int e = tid; e < 16 * P; e += 256) FV[(int64_t)rep * 16 * P + e] = apre[e];
   }
@@ -1298,28 +1299,22 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_pv_kernel(FactBase fb, EigWor
   }
 }
 
-// LP (the fp32 middle products of a warm eigenvalue-rule solve): 0 =
-// HZ and Z in fp64 as described; 1 = HZ arrives as float HZ32 = H32 Z32 in Z's
-// replicate-major chunk layout (this replicate's 16-row tile one contiguous
-// 64 pz-byte piece, fetched as 16-B pieces and transposed through the EL
-// stage) and is scaled by hscale = hmax on the way in, Z leaves as float Z32,
-// rounded to nearest; 2 = HZ32 in, fp64 Z out in the normal layout (the last
-// middle step, whose Z feeds the filter's fp64 product); 3 = as 1 with Z
-// leaving as the three bf16 planes of gemmh_zrm_split_kernel's Zs (the
-// same doubles of the stage, split on the way out).  All arithmetic, a
-// and cc stay fp64 in every mode; cc is formed from the unrounded Z.
+// HF, ZF (dfm_fact_plan.h; the reduced-precision products of a warm eigenvalue-rule solve): how HZ arrives and how Z
+// leaves.  Rows64: fp64 rows as described.  Chunk32: float HZ32 in Z's replicate-major chunk layout (this replicate's
+// 16-row tile one contiguous 64 pz-byte piece, fetched as 16-B pieces and transposed through the EL stage), scaled by
+// hscale = hmax on the way in.  Z leaves as zchunk_store writes it: fp64 in the normal layout (behind Chunk32: the
+// last middle step in front of an fp64 product), float Z32, rounded to nearest, or the three bf16 planes (the same
+// doubles of the stage, split on the way out).  All arithmetic, a and cc stay fp64 in every mode; cc is formed from
+// the unrounded Z.
 //
-// NOPF (a warm solve that starts with the filter, eig_run_fact2_t; selected by
-// DFM_FACT_PF=0 only, see fact_pf_stored): no stored PF.  There V0 = Q0, whose
-// first r columns are the warm vectors bit for bit (eig_init_kernel;
-// q0_guards_kernel leaves them), and F = pfs * warm[:, :r]
-// with one rounding per element (FactArgs::fscale), so
+// NOPF (a warm solve that starts with the filter, eig_run_fact2_t; selected by DFM_FACT_PF=0 only, FilterPlan::nopf):
+// no stored PF.  There V0 = Q0, whose first r columns are the warm vectors bit for bit (eig_init_kernel;
+// q0_guards_kernel leaves them), and F = pfs * warm[:, :r] with one rounding per element (FactArgs::fscale), so
 //   PF = P'D F = pfs * (P'D Q0)[:, :r] = pfs * PV[:, :r]
-// up to the rounding of the bucket sums.  The tile's 16 PV rows — one
-// contiguous range of 16 ps doubles — arrive as 16-B pieces in the stage the
-// PF rows take otherwise, and pA, pfa (columns < r, times pfs) and pv are read
-// from there: no PF loads, no PV row gathers.  PF and pfr are not read.
-template <int P, bool FAST, int LP, bool NOPF = false>
+// up to the rounding of the bucket sums.  The tile's 16 PV rows — one contiguous range of 16 ps doubles — arrive as
+// 16-B pieces in the stage the PF rows take otherwise, and pA, pfa (columns < r, times pfs) and pv are read from
+// there: no PF loads, no PV row gathers.  PF and pfr are not read.
+template <int P, bool FAST, HzFmt HF, ZFmt ZF, bool NOPF = false>
 __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, EigWork w, int T, int p,
                                                             const double *__restrict__ HZ, int64_t ldz, int pz,
                                                             double *__restrict__ ab, double fai, double bbeta, int k,
@@ -1330,10 +1325,10 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
                                                             const double *__restrict__ FtF,
                                                             double *__restrict__ Zc, int ps, double bfix,
                                                             double lead, double hscale, double pfs) {
-  // bfix > 0: the interval end of a filter-only first step (boot_cheb_kernel);
-  // lead: the scale of the incoming S_{i+1} not yet applied to its Z, a, cc —
-  // the filter's leading coefficient a_d at the first step of such a filter
+  // bfix > 0: the interval end of a filter-only first step (boot_cheb_kernel); lead: the scale of the incoming
+  // S_{i+1} not yet applied to its Z, a, cc — the filter's leading coefficient a_d at the first step of such a filter
   // (S_d = a_d V0 is never formed: prep left the Z, a, cc of V0), else 1
+  static_assert(HF == HzFmt::Chunk32 || ZF == ZFmt::F64, "a step fed fp64 rows writes an fp64 Z");
   constexpr int NT = P / 16;
   const int rep = blockIdx.x;
   if (w.done[rep]) return;
@@ -1341,14 +1336,11 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   const int li = lane & 15, lk = lane >> 4;
   __shared__ double sa[16 * P], sb[16 * P];
   __shared__ double sred[NT * 256];
-  // per-wave staging (this pass is bound by the texture-address unit,
-  // TA_TA_BUSY 0.95 of its cycles): the tile's PF and EL rows arrive as ONE
-  // contiguous 16-row range each (16 r doubles) instead of two differently
-  // shaped gathers of the same rows, and the tile's Z chunk (16 rows x pz,
-  // contiguous in the replicate-major layout) leaves as whole 16-B pieces
-  // instead of one 128-B-strided element per lane
-  // stage 0 holds the PF rows (16 x (r | 1) <= 16 x 17) and then the Z chunk (16 x pz <= 16 x P)
-  // (NOPF: the PV rows instead, 16 x (ps | 1) <= 16 x (P + 1))
+  // per-wave staging (this pass is bound by the texture-address unit, TA_TA_BUSY 0.95 of its cycles): the tile's PF
+  // and EL rows arrive as ONE contiguous 16-row range each (16 r doubles) instead of two differently shaped gathers
+  // of the same rows, and the tile's Z chunk (16 rows x pz, contiguous in the replicate-major layout) leaves as whole
+  // 16-B pieces instead of one 128-B-strided element per lane stage 0 holds the PF rows (16 x (r | 1) <= 16 x 17) and
+  // then the Z chunk (16 x pz <= 16 x P) (NOPF: the PV rows instead, 16 x (ps | 1) <= 16 x (P + 1))
   constexpr int MID_STG = NOPF ? 16 * (P + 1) : 16 * (P > 17 ? P : 17);
   static_assert(MID_STG >= 16 * P && MID_STG >= 16 * 17, "the stage holds a Z chunk of pz <= P columns and 16 PF rows");
   static_assert(!NOPF || MID_STG >= 16 * (P | 1), "... or 16 PV rows of ps <= P columns at an odd stride");
@@ -1383,10 +1375,10 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
   double *sP = stgP[wave], *sE = stgE[wave];
   const int64_t zrs = zrm_stride(T, pz);
   for (int tile = wave; tile < ntile; tile += BW) {
-    // LP == 3: the lane number is re-read per tile, so the tile's lane-dependent addresses are formed here from one
+    // Split: the lane number is re-read per tile, so the tile's lane-dependent addresses are formed here from one
     // register and not carried through the loop as invariants (the split store below needs their registers: 128 VGPRs)
     int lane_t = lane;
-    if constexpr (LP == 3) asm volatile("" : "+v"(lane_t));
+    if constexpr (ZF == ZFmt::Split) asm volatile("" : "+v"(lane_t));
     const int lane = lane_t, li = lane & 15, lk = lane >> 4;
     const int t0 = tile * 16;
     const int nr = min(16, T - t0) * r;   // valid doubles of the tile's contiguous PF / EL range
@@ -1414,8 +1406,8 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
       }
     }
     const double e2l = t0 + li < T ? e2r[t0 + li] : 0.0;
-    zf4 h4[NT];   // LP: the tile's HZ32 chunk, piece e = 64 u + lane: column e >> 2, rows 4 (e & 3) .. + 3
-    if constexpr (LP != 0) {
+    zf4 h4[NT];   // Chunk32: the tile's HZ32 chunk, piece e = 64 u + lane: column e >> 2, rows 4 (e & 3) .. + 3
+    if constexpr (HF == HzFmt::Chunk32) {
       const zf4 *hc = reinterpret_cast<const zf4 *>(reinterpret_cast<const float *>(HZ) + (int64_t)rep * zrs +
                                                      (int64_t)tile * 16 * pz);
 #pragma unroll
@@ -1428,7 +1420,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
 #pragma unroll
       for (int ct = 0; ct < NT; ++ct) {
         const int c = 16 * ct + li;
-        if constexpr (LP == 0) hz[ct][g] = c < pz ? HZ[(int64_t)sc * ldz + (int64_t)rep * pz + c] : 0.0;
+        if constexpr (HF == HzFmt::Rows64) hz[ct][g] = c < pz ? HZ[(int64_t)sc * ldz + (int64_t)rep * pz + c] : 0.0;
         if constexpr (!NOPF) pv[ct][g] = c < ps ? pvr[(int64_t)sc * ps + c] : 0.0;
       }
     }
@@ -1479,10 +1471,9 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) pv[ct][g] = 16 * ct + li < ps ? sP[(4 * g + lk) * RP + 16 * ct + li] : 0.0;
     }
-    if constexpr (LP != 0) {
-      // HZ32 through the EL stage (its reads above are complete in this wave's
-      // LDS order): column c at float offset 17 c (17 pz <= 17 P floats fit the
-      // stage's 16 x 17 doubles), read back in the accumulator layout
+    if constexpr (HF == HzFmt::Chunk32) {
+      // HZ32 through the EL stage (its reads above are complete in this wave's LDS order): column c at float offset
+      // 17 c (17 pz <= 17 P floats fit the stage's 16 x 17 doubles), read back in the accumulator layout
       static_assert(17 * P <= 2 * 16 * 17, "the EL stage holds the HZ32 chunk");
       float *sH = reinterpret_cast<float *>(sE);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1532,9 +1523,8 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         zv[ct][g] = z;
       }
     }
-    // the Z chunk through the PF staging (its reads above are complete in
-    // this wave's LDS order): chunk element 16 c + (s & 15); rows past T hold
-    // z = 0, the value boot_prep_kernel left in the chunk's pad rows
+    // the Z chunk through the PF staging (its reads above are complete in this wave's LDS order): chunk element 16 c
+    // + (s & 15); rows past T hold z = 0, the value boot_prep_kernel left in the chunk's pad rows
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -1544,12 +1534,13 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         if (c < pz) sP[16 * c + 4 * g + lk] = zv[ct][g];
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (LP == 3) {   // (split below, behind the tile's last MFMAs: their operands' registers are free there)
-    } else if constexpr (LP == 1) {
+    // (ZFmt::Split leaves below, behind the tile's last MFMAs: their operands' registers are free there)
+    // (zchunk_store's other two formats, written out: through the helper these instances spill differently)
+    if constexpr (ZF == ZFmt::F32) {
       zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
       for (int e = lane; e < 4 * pz; e += 64)
         zc4[e] = zf4{(float)sP[4 * e], (float)sP[4 * e + 1], (float)sP[4 * e + 2], (float)sP[4 * e + 3]};
-    } else {
+    } else if constexpr (ZF == ZFmt::F64) {
       double2 *zc2 = reinterpret_cast<double2 *>(Zc + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
       for (int e = lane; e < 8 * pz; e += 64) zc2[e] = double2{sP[2 * e], sP[2 * e + 1]};
     }
@@ -1560,10 +1551,9 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
         aacc[ct] = mfma16(pfa[g], uv[ct][g], aacc[ct]);
         cacc[ct] = mfma16(ea[g], zv[ct][g], cacc[ct]);
       }
-    if constexpr (LP == 3) {   // (the stage is this wave's until the next tile's PF rows, behind these reads in its LDS order)
+    if constexpr (ZF == ZFmt::Split) {   // (the stage is this wave's until the next tile's PF rows, behind these reads in its LDS order)
       asm volatile("" ::: "memory");
-      zsplit_store_chunk<P == 16>(sP, pz, lane, reinterpret_cast<char *>(Zc + (int64_t)rep * zrs) +
-                                                    (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz);
+      zchunk_store<P>(ZF, sP, Zc, rep, zrs, tile, pz, lane);
     }
   }
   // a_i = (F'F bB + PF'u) / b + a_i FV  (dd columns: FV; columns >= p: 0)
@@ -1628,131 +1618,6 @@ __global__ __launch_bounds__(1024) void active_list_kernel(const int *__restrict
   if (tid == 1023) *count = part[1023];
 }
 
-// Filter schedule of the factored solver.  From a warm start (the base fit's
-// eigenvectors): a degree-6 filter on [0, max(theta_p, 0.2 theta_k)] after
-// the first Rayleigh-Ritz step, degree 2 on [0, theta_p] after the later ones.
-// C3 (tools/eig_proto.py, the CPU model of this loop; tools/c3_excess.py, the
-// convergence excess measured on the GPU): with degree 2 throughout the first
-// filter gains only ~3e3 in the eigenvalue bound (theta_16 ~ 0.8e3 far below
-// lambda_17 ~ 8e3) against ~5e4 for the later ones, and replicates retire at
-// the 4th (96 %) or 5th Rayleigh-Ritz step after 7.09 products; with this
-// schedule every replicate of the CPU model retires at the 2nd step after 7
-// products — two Rayleigh-Ritz passes and the straggler tail fewer, two more
-// Chebyshev passes.  Cold starts (no warm vectors: expanding windows) keep
-// degree 2 on [0, theta_p].
-constexpr int kChebWarmD0 = 6, kChebD = 2;
-constexpr double kChebWarmBeta = 0.2;
-// The filter amplifies wanted eigenvalue lambda_1 over lambda_k by about
-// T_d(x_1) / T_d(x_k) ~ (x_1 / x_k)^d, x = 2 lambda / b - 1 (x_k = 9 at
-// b = 0.2 lambda_k): the filtered block's condition number.  Its degree is
-// capped so that stays below ~1e6 (CholQR2 keeps every wanted direction in
-// fp64): C3's lambda_1 / lambda_8 = 1.6 allows 6 (the cap); a panel with one
-// dominant factor (C2's base fit: lambda_1 / lambda_4 = 50) gets 3.
-// DFM_FACT_D0 / DFM_FACT_BETA (A/B only) override the first filter's degree
-// cap and interval factor.
-static int warm_d0_cap() {
-  static const int v = [] { const char *e = getenv("DFM_FACT_D0"); return e ? std::max(kChebD, std::min(kChebDMax, atoi(e))) : kChebWarmD0; }();
-  return v;
-}
-static double warm_beta() {
-  static const double v = [] { const char *e = getenv("DFM_FACT_BETA"); return e ? atof(e) : kChebWarmBeta; }();
-  return v;
-}
-// A warm start whose first filter has middle steps (degree >= 3) skips the
-// first Rayleigh-Ritz step: the filter is a polynomial in G*, so
-// span(p(G*) Q0 Bm) = span(p(G*) Q0) for any invertible Bm and the next
-// Rayleigh-Ritz step, which reads only the span, loses nothing; the interval
-// end is kWarmFixBeta lambda_k of the BASE fit, one number for the whole
-// job (model-only: the same in every batch, lane and shard).  The guards'
-// branch of filter_end (theta_p) is not taken over: it needs a product, an
-// end short of lambda_{p+1} only slows the filter, and in the CPU model it
-// never binds (theta_p / theta_k of a step on the start block <= 0.022 at
-// C3, <= 0.095 at T = 120, N = 300, against the 0.2 it must exceed).  Gone per solve: step
-// 0's y2, eig_small, pv and ap2; one more middle Horner step instead.  The
-// guard columns are orthonormalised once against the warm vectors
-// (q0_guards_kernel): with raw random guards the filtered block's condition
-// number is ~4e7 (CPU model, tools/eig_proto.py) and the Cholesky of its Gram
-// matrix fails.  The first Rayleigh-Ritz step diagonalises a projected
-// matrix that no earlier step has pre-rotated; its kJacobiSweeps = 2 sweeps
-// still suffice (CPU model: the same retirement as with 4; measured, a cap
-// of 4 there: 47 replicate-steps in 205 k fewer, eig_small +0.05 ms per C3
-// step, profiles/r07_c3_ab.txt).
-// That step runs as loop step 1 (itc = 2 in ap2): decide_converged's
-// previous-residual record needs no initialisation for it — the stagnation
-// test that reads the record is guarded by itc > 2, and loop step 2 reads the
-// slot ((itc - 1) & 1) that loop step 1 wrote, as any later pair of steps.
-// DFM_FACT_STEP0=1 (A/B only) restores the first Rayleigh-Ritz step.
-constexpr double kWarmFixBeta = 0.21;
-static bool warm_keep_step0() {   // (read at every solve: one process can run both schedules)
-  const char *e = getenv("DFM_FACT_STEP0");
-  return e && atoi(e) != 0;
-}
-// Under the eigenvalue rule (tol < 0) the middle products of that filter-only
-// step — products 1 .. d0 - 1 of its d0 — run in fp32
-// (gemmh_zrm_f32_kernel).  The filter only has to deliver a good subspace: the Rayleigh-Ritz
-// step behind it and the Kato-Temple stopping rule stay fp64 and measure the
-// true residual, the eigenvalue error is quadratic in the subspace error, and
-// the rounding noise (relative to the idiosyncratic part H Z alone: PF bB,
-// EL a and F'F stay fp64) is damped by the fp64 product that follows.  The
-// CPU model (tools/eig_proto.py, F32 / NOISE) retires the same replicates at
-// the same steps with 64 times the fp32 noise in those products.  The last
-// product stayed fp64 in round 8 (the model degrades at 16 times the noise;
-// round 19 measured the margin and moved it: fact_split_last_off).  The strict
-// and subspace rules keep fp64 throughout: they bound the eigenvector
-// residual, which is linear in the subspace error (the model needs more
-// products there).  DFM_FACT_F32=0 (A/B only, read at every solve) restores
-// the fp64 middle products.
-static bool fact_f32_off() {
-  const char *e = getenv("DFM_FACT_F32");
-  return e && atoi(e) == 0;
-}
-// ap2 decides before it writes (boot_ap2_kernel's probe) on the Rayleigh-Ritz
-// steps it >= first_poll: the step most replicates are expected to retire at,
-// and on — every step of a warm solve (C3: 97 % retire at the first one and,
-// under eigenvalue-only statistics, leave without V0, Qn and their MFMAs).
-// The earlier steps of a cold solve keep the one-pass form: everybody goes
-// on there and the second read of Q and Y would be pure cost.  The bits do
-// not depend on it.  DFM_AP2_PROBE=0 (A/B only, read at every solve) keeps
-// the one-pass form throughout.
-// By default those products run as six bf16 MFMA terms on operands split into
-// three bf16 planes (gemmh_zrm_split_kernel, round 15): as accurate as the
-// fp32 kernel, on the 16 times faster bf16 matrix path.  DFM_FACT_SPLIT=0 (A/B
-// only, read at every solve) restores the fp32 launches bit for bit.
-static bool fact_split_off() {
-  const char *e = getenv("DFM_FACT_SPLIT");
-  return e && atoi(e) == 0;
-}
-// With them the filter's last product, number d0, runs on the same kernel
-// (round 19): its last middle step hands it bf16 planes like the others, and
-// the GEMM's second epilogue writes hmax C32 as fp64 rows of HZ, which the last
-// Horner step gathers as it gathers an fp64 product's.  The argument is the
-// one above: the product shapes the subspace and no more, the Rayleigh-Ritz
-// product and the residual test behind it are fp64; the model (DESIGN.md
-// section 3, round 19) moves no replicate up to four times fp32's noise and
-// one in 400 at eight, and the split kernel's error is 0.82 of fp32's.
-// DFM_FACT_SPLIT_LAST=0 (A/B only, read at every solve) restores the fp64
-// launch bit for bit.
-static bool fact_split_last_off() {
-  const char *e = getenv("DFM_FACT_SPLIT_LAST");
-  return e && atoi(e) == 0;
-}
-static bool ap2_probe_off() {
-  const char *e = getenv("DFM_AP2_PROBE");
-  return e && atoi(e) == 0;
-}
-// The middle steps of a solve that starts with the filter read stored PF
-// (boot_prep_kernel writes it), as every other solve's do.  DFM_FACT_PF=0
-// (A/B only, read at every solve) selects the NOPF kernels instead: measured
-// at C3 (profiles/r10_c3_ab.txt) they move 0.30 GB less per launch and take
-// 0.19 ms off a 9.34 ms step (prep -0.10, the five middle steps -0.09: the
-// pass is bound by its load latency, not its bytes) — 2.3 times the parent's
-// run-to-run spread, short of the 3 times this project asks of a change, so
-// the stored form stays the default.
-static bool fact_pf_stored() {
-  const char *e = getenv("DFM_FACT_PF");
-  return !(e && *e && atoi(e) == 0);
-}
-
 // Guard columns kw..p-1 of the shared warm start Q0 (m rows of ps columns),
 // orthonormalised against the warm columns 0..kw-1 (one projection; the warm
 // columns, left bit-for-bit as they are, are orthogonal eigenvectors) and
@@ -1762,7 +1627,6 @@ static bool fact_pf_stored() {
 // The kernel also opens the filter-only step's record: active[0] = nb, what
 // a first Rayleigh-Ritz step that retires no replicate would have counted
 // (every replicate runs step 0; count_iters_body prices its products from it).
-constexpr int Q0G_PMAX = 32;                        // the widest block (eig_run_factored: p <= 32)
 constexpr int Q0G_SUMS = Q0G_PMAX * Q0G_PMAX;       // sums per phase: (ng + 1) kw <= 272 (ng + kw <= 32), ng^2 <= 1024
 __global__ __launch_bounds__(1024) void q0_guards_kernel(double *__restrict__ Q0, int m, int ps, int kw, int p,
                                                          int *__restrict__ active, int nb) {
@@ -1838,12 +1702,10 @@ __global__ __launch_bounds__(1024) void q0_guards_kernel(double *__restrict__ Q0
   }
 }
 
-// Zero the pad rows T .. round_up(T, 16) - 1 of every replicate's fp64 Z (its
-// last 16-row chunk): gemmh_zrm_kernel reads them against H's zero k-padding,
-// so they must be finite.  A step 0 whose last product runs split
-// (fact_split_last_off) needs it: prep and every middle step wrote bf16 planes
-// there, no pass wrote the fp64 chunks, and the last Horner step (zscatter_tail)
-// stores rows < T only.  nb pz doubles per pad row, disjoint from those rows.
+// Zero the pad rows T .. round_up(T, 16) - 1 of every replicate's fp64 Z (its last 16-row chunk): gemmh_zrm_kernel
+// reads them against H's zero k-padding, so they must be finite.  A step 0 whose last product runs split
+// (FilterPlan::zero_zpad) needs it: prep and every middle step wrote bf16 planes there, no pass wrote the fp64 chunks,
+// and the last Horner step (zscatter_tail) stores rows < T only.  nb pz doubles per pad row, disjoint from those rows.
 __global__ void zpad_zero_kernel(double *__restrict__ Zc, int T, int pz, int64_t zrs, int nb) {
   const int npad = ((T + 15) & ~15) - T;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1852,32 +1714,25 @@ __global__ void zpad_zero_kernel(double *__restrict__ Zc, int T, int pz, int64_t
   Zc[zrm_ix(rep, T + e % npad, e / npad, pz, zrs)] = 0.0;
 }
 
-// The kernel instances eig_run_fact2_t launches.  stg: the loaders staged
-// through LDS (y2_load's STG, the middle steps' FAST), which exist for P = 16
-// only.  lp, nopf: boot_cheb_mid_kernel's LP and NOPF.
+// The kernel instances eig_run_fact2_t launches.  stg: the loaders staged through LDS (y2_load's STG, the middle
+// steps' FAST), which exist for P = 16 only.  hf, zf, nopf: boot_cheb_mid_kernel's HF, ZF and NOPF; the four (hf, zf)
+// pairs are the ones a consistent FilterPlan holds.
 template <int P>
 static auto y2_instance(bool stg) { return stg ? boot_y2_kernel<P, P == 16> : boot_y2_kernel<P, false>; }
 template <int P>
 static auto cheb_instance(bool stg) { return stg ? boot_cheb_kernel<P, P == 16> : boot_cheb_kernel<P, false>; }
-template <int P>
-static auto cheb_mid_instance(bool stg, int lp, bool nopf) {
-  constexpr bool F = P == 16;
-  static constexpr decltype(&boot_cheb_mid_kernel<P, false, 0, false>) tab[2][2][4] = {
-      {{boot_cheb_mid_kernel<P, false, 0, false>, boot_cheb_mid_kernel<P, false, 1, false>,
-        boot_cheb_mid_kernel<P, false, 2, false>, boot_cheb_mid_kernel<P, false, 3, false>},
-       {boot_cheb_mid_kernel<P, F, 0, false>, boot_cheb_mid_kernel<P, F, 1, false>, boot_cheb_mid_kernel<P, F, 2, false>,
-        boot_cheb_mid_kernel<P, F, 3, false>}},
-      {{boot_cheb_mid_kernel<P, false, 0, true>, boot_cheb_mid_kernel<P, false, 1, true>,
-        boot_cheb_mid_kernel<P, false, 2, true>, boot_cheb_mid_kernel<P, false, 3, true>},
-       {boot_cheb_mid_kernel<P, F, 0, true>, boot_cheb_mid_kernel<P, F, 1, true>, boot_cheb_mid_kernel<P, F, 2, true>,
-        boot_cheb_mid_kernel<P, F, 3, true>}}};
-  return tab[nopf][stg][lp];
+template <int P, bool FAST, bool NOPF>
+static auto cheb_mid_pair(HzFmt hf, ZFmt zf) {
+  if (hf == HzFmt::Rows64) return boot_cheb_mid_kernel<P, FAST, HzFmt::Rows64, ZFmt::F64, NOPF>;
+  if (zf == ZFmt::F32) return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::F32, NOPF>;
+  if (zf == ZFmt::F64) return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::F64, NOPF>;
+  return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::Split, NOPF>;
 }
-
-static int first_filter_degree(double spread) {
-  const double ratio = std::max(1.0001, 1.1 * spread);
-  const int d = (int)std::floor(std::log(1e6) / std::log(ratio));
-  return std::max(kChebD, std::min(warm_d0_cap(), d));
+template <int P>
+static auto cheb_mid_instance(bool stg, HzFmt hf, ZFmt zf, bool nopf) {
+  constexpr bool F = P == 16;
+  if (!nopf) return !stg ? cheb_mid_pair<P, false, false>(hf, zf) : cheb_mid_pair<P, F, false>(hf, zf);
+  return !stg ? cheb_mid_pair<P, false, true>(hf, zf) : cheb_mid_pair<P, F, true>(hf, zf);
 }
 
 template <int P>
@@ -1888,27 +1743,34 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   int *off = f.off, *lst = f.lst;
   const PollBuf *pb = f.pb;
   hipStream_t st = a.st;
+  // Step 0's schedule, kernels and formats (dfm_fact_plan.h): one plan, checked before the first launch
+  const FactSwitches sw = read_fact_switches();
+  FilterPlanIn pin;
+  pin.warm = a.warm; pin.kw = a.kw; pin.k = k; pin.p = p; pin.P = P; pin.r = fb.r; pin.T = m; pin.maxit = maxit;
+  pin.tol = a.tol; pin.spread = f.spread; pin.lamk = f.lamk; pin.fscale = f.fscale;
+  pin.has_H32 = fb.H32 != nullptr; pin.has_Hs = fb.Hs != nullptr; pin.hmax = fb.hmax;
+  const FilterPlan plan = plan_first_filter(pin, sw);
+  if (!plan.consistent()) return 1003;
+  const bool warm_started = plan.warm_started, mid = plan.mid, skip0 = plan.skip0, stg_ok = plan.stg_ok, nopf = plan.nopf;
+  const int d0 = plan.d0;
   EigWork w = carve(a.ws, m, nb, P, maxit);
   w.subspace = a.subspace;
   w.no_vectors = a.Uk == nullptr;
   // Z / HZ hold pz = p rounded up to even columns per replicate (the GEMM's
   // 16-byte DMA pairs): the H.Z GEMM's work scales with the block p, not P
   const int pz = (p + 1) & ~1;
-  // (measured and rejected: Z / HZ rows padded to 128-B lines cut the
-  // H.Z GEMM's FETCH_SIZE 0.40 -> 0.32 GB per launch — unpadded, a 512-B tile
-  // row straddles five lines, one shared with another XCD's column block — but
-  // left the GEMM's time unchanged and slowed the gathering passes 2-4 % with
-  // an even or an odd number of lines per row: C3 15.09 -> 15.27-15.38 ms)
+  // (measured and rejected: Z / HZ rows padded to 128-B lines cut the H.Z GEMM's FETCH_SIZE 0.40 -> 0.32 GB per
+  // launch — unpadded, a 512-B tile row straddles five lines, one shared with another XCD's column block — but left
+  // the GEMM's time unchanged and slowed the gathering passes 2-4 % with an even or an odd number of lines per row:
+  // C3 15.09 -> 15.27-15.38 ms)
   const int ncz = nb * pz;
   const int64_t ldz = ncz;           // HZ: T x nb pz, column-interleaved (rows gathered by idx)
   const int64_t zrs = z_rows(m) * pz;   // Z: replicate-major 16-row chunks (zrm_ix), nb zrs <= z_rows ldz
-  // the per-replicate T-row buffers (Q, Y, V0 in U, PV in S, the warm start
-  // Q0) hold compact rows of ps = pz columns (columns >= p are zero, so the
-  // register layouts' columns ps..P-1 load as zero and are never stored):
-  // ~20 % fewer bytes in the per-replicate passes at C3 (P = 16, pz = 12).
-  // Replicate slots keep the P-column stride (T P doubles), so a retired
-  // replicate's final Ritz vectors (U, row stride P, eig_final_kernel) never
-  // overlap another replicate's compact rows.
+  // the per-replicate T-row buffers (Q, Y, V0 in U, PV in S, the warm start Q0) hold compact rows of ps = pz columns
+  // (columns >= p are zero, so the register layouts' columns ps..P-1 load as zero and are never stored): ~20 % fewer
+  // bytes in the per-replicate passes at C3 (P = 16, pz = 12). Replicate slots keep the P-column stride (T P
+  // doubles), so a retired replicate's final Ritz vectors (U, row stride P, eig_final_kernel) never overlap another
+  // replicate's compact rows.
   const int ps = pz;
   const FactWsLayout wl = fact_ws_layout(m, nb, P, pz);
   auto ws_at = [&](size_t o) { return (double *)(f.fws + o); };
@@ -1951,28 +1813,9 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   struct Q0Free { char *q; hipStream_t s; ~Q0Free() { hipFreeAsync(q, s); } } q0free{qblk, st};
   const double *qin = Q0;
   int64_t qs = 0;
-  const bool warm_started = a.warm && a.kw >= k && f.spread >= 1.0;
-  const int d0 = warm_started ? first_filter_degree(f.spread) : kChebD;
-  // a first filter of degree >= 3 has middle Horner steps (boot_cheb_mid_kernel)
-  const bool mid = d0 >= 3;
-  // ... and, from a warm start, no Rayleigh-Ritz step in front of it (warm_keep_step0)
-  const double bfix = kWarmFixBeta * f.lamk;
-  const bool skip0 = warm_started && mid && maxit >= 2 && bfix > 0.0 && p <= Q0G_PMAX && !warm_keep_step0();
-  // y2 and the Horner steps stage F / EL[idx] rows through LDS for even r <= 8 (y2_load's STG)
-  const bool stg_ok = P == 16 && fb.r <= 8 && (fb.r & 1) == 0 && pz <= 16;
+  const double bfix = kWarmFixBeta * f.lamk;   // the filter-only step's interval end
   auto chk = cheb_instance<P>(stg_ok);
   auto y2k = y2_instance<P>(stg_ok);
-  // ... whose middle products run in fp32 under the eigenvalue rule (fact_f32_off)
-  const bool lowp = skip0 && a.tol < 0.0 && fb.H32 && std::isfinite(fb.hmax) && fb.hmax > 0.0 && m >= 16 && !fact_f32_off();
-  // ... and may take PF = P'D F from PV's rows (boot_cheb_mid_kernel's NOPF; off by default, fact_pf_stored):
-  // that step filters V0 = Q0, whose first kw >= r columns are the warm vectors, and F = fscale * warm[:, :r].
-  // The middle steps behind a first Rayleigh-Ritz step (warm_keep_step0; PV = P'D (Q Bm), boot_pv_kernel) have
-  // no such identity and always read stored PF.
-  // ... as six bf16 terms on split operands where the model holds the split H (fact_split_off)
-  const bool split = lowp && fb.Hs && !fact_split_off();
-  // ... the last product too, through that kernel's fp64 epilogue (fact_split_last_off)
-  const bool split_last = split && !fact_split_last_off();
-  const bool nopf = skip0 && f.fscale > 0.0 && a.kw >= fb.r && !fact_pf_stored();
   // dynamic LDS above the default 64 KB cap: prep (24 T + 8 bytes) for T > 2730, the last Horner step (20 T + 4)
   // for T > 3276, ap2 (16 T + 4) at T = F2_T_MAX.  A refused cap is this solve's error, not a later launch's.
   const size_t prep_lds = (size_t)((4 * m + 3) & ~1) * 4 + (size_t)m * 8;
@@ -1996,50 +1839,53 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(64 * BW), prep_lds, st,
                        fb, idx, eta, off, lst, w.trace, mid && !nopf ? PFb : nullptr, mid ? E2b : nullptr, Q0, ps, Zc,
                        ldz, pz, ab, apre,
-                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, split ? 2 : lowp ? 1 : 0);
+                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, plan.z0);
     if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
   }
   const double *ftf = fb.FtF ? fb.FtF : FtF;
-  const double beta0 = warm_started ? warm_beta() : 0.0;
+  const double beta0 = warm_started ? sw.beta : 0.0;
   double ca0[kChebDMax + 1], ca1[kChebDMax + 1];
   shifted_cheb(d0, ca0);
   shifted_cheb(kChebD, ca1);
-  // The schedule's three products.  HZ = H Z for the whole batch, or for the
-  // listed replicates' column groups once the straggler list is on:
-  auto hz = [&](bool listed) -> int {
+  // One H.Z product for the whole batch, by the kernel the plan names:
+  //   F64        HZ = H Z in fp64 rows — listed: for the listed replicates' column groups, once the straggler list is on
+  //   F32        HZ32 = H32 Z32 in fp32 (Z32 in the first half of Z's region, HZ32 in HZ's, both in Z's chunk layout;
+  //              every replicate is active there: no col_done, no list)
+  //   Split      the same HZ32 from the bf16 planes of H and Z, Zs in Z's region at the fp64 replicate stride
+  //   SplitRows  HZ = hmax HZ32 from the same planes, written as F64 writes it
+  // zpad: behind it the fp64 Z's pad rows, which no pass of step 0 wrote, are zeroed for the fp64 products that follow
+  auto product = [&](HzProduct kind, bool listed, bool zpad = false) -> int {
     TimerScope ts(a, DFM_KC_GEMM);
-    const hipError_t e = launch_gemm_zrm(fb.H, fb.ldH, Zc, pz, zrs, HZ, ldz, m, ncz, m, st, w.done,
-                                         listed ? alist : nullptr, listed ? acount : nullptr);
-    return e == hipSuccess ? 0 : 1000 + (int)e;
-  };
-  // ... or, a middle product of a lowp step 0, HZ32 = H32 Z32 in fp32 (Z32 in the first half of Z's region, HZ32 in
-  // HZ's, both in Z's chunk layout; every replicate is active there: no col_done, no list)
-  // (split: the same HZ32 from the bf16 planes of H and Z, Zs in Z's region at the fp64 replicate stride)
-  auto hz32 = [&]() -> int {
-    TimerScope ts(a, DFM_KC_GEMM);
-    const hipError_t e =
-        split ? launch_gemm_zrm_split(fb.Hs, Zc, pz, zrs, (float *)HZ, m, ncz, m, st)
-              : launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
-    return e == hipSuccess ? 0 : 1000 + (int)e;
-  };
-  // ... or, product d0 of a split step 0, HZ = hmax HZ32 from the same planes, written as hz writes it (split_last).
-  // The fp64 Z's pad rows, which no pass of such a step wrote, are zeroed for the fp64 products that follow.
-  auto hz_split_rows = [&]() -> int {
-    TimerScope ts(a, DFM_KC_GEMM);
-    hipError_t e = launch_gemm_zrm_split_rows(fb.Hs, Zc, pz, zrs, HZ, ldz, fb.hmax, m, ncz, m, st);
-    if (e == hipSuccess && (m & 15)) {
-      const int64_t n = (int64_t)nb * pz * (16 - (m & 15));
+    hipError_t e = hipErrorInvalidValue;
+    switch (kind) {
+      case HzProduct::F64:
+        e = launch_gemm_zrm(fb.H, fb.ldH, Zc, pz, zrs, HZ, ldz, m, ncz, m, st, w.done, listed ? alist : nullptr,
+                            listed ? acount : nullptr);
+        break;
+      case HzProduct::F32:
+        e = launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
+        break;
+      case HzProduct::Split:
+        e = launch_gemm_zrm_split(fb.Hs, Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
+        break;
+      case HzProduct::SplitRows:
+        e = launch_gemm_zrm_split_rows(fb.Hs, Zc, pz, zrs, HZ, ldz, fb.hmax, m, ncz, m, st);
+        break;
+    }
+    if (e == hipSuccess && zpad) {
+      const int64_t n = (int64_t)nb * pz * plan.pad_rows;
       hipLaunchKernelGGL(zpad_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Zc, m, pz, zrs, nb);
       e = hipGetLastError();
     }
     return e == hipSuccess ? 0 : 1000 + (int)e;
   };
-  // a middle Horner step S_i = G* S_{i+1} / b + c V0 in row-local form (Z, a, cc only) ...
-  // (lp: 0 = fp64 HZ in, fp64 Z out; 1 = HZ32 in, Z32 out; 2 = HZ32 in, fp64 Z out; 3 = HZ32 in, split Z out)
-  auto horner_mid = [&](double c, double bbeta, double bfx, double lead, int lp = 0) {
+  // a middle Horner step S_i = G* S_{i+1} / b + c V0 in row-local form (Z, a, cc only), reading HZ as hf and
+  // writing Z as zf ...
+  auto horner_mid = [&](double c, double bbeta, double bfx, double lead, HzFmt hf = HzFmt::Rows64,
+                        ZFmt zf = ZFmt::F64) {
     TimerScope ts(a, DFM_KC_EIG_APPLY);
-    hipLaunchKernelGGL(cheb_mid_instance<P>(stg_ok, lp, nopf), dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz, pz,
-                       ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale);
+    hipLaunchKernelGGL(cheb_mid_instance<P>(stg_ok, hf, zf, nopf), dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz,
+                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale);
   };
   // ... and the last one, S_0: the new basis into cur, with its Z, a, cc
   auto horner_last = [&](double c, double bbeta, const double *V0, int64_t v0s, double bfx) {
@@ -2048,38 +1894,28 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
                        bbeta, k, cur, Zc, ps, V0, v0s, bfx);
   };
 
-  // Convergence polls from the step most replicates retire at (first_poll)
-  // on.  After each such step the device rebuilds the list of active
-  // replicates (the GEMMs compact to it once it holds < 1/8 of the batch,
-  // decided on the device, so no host round trip sits in front of the
-  // straggler phase) and, with a pinned read-back buffer, the active count is
-  // copied to host[it] behind an event.  Outside the tail the host does not
-  // wait for it: it queues the next step first and reads the previous step's
-  // count then (one step of look-ahead — the GPU always has a step queued
-  // while the host decides; a step queued after the last replicate retired
-  // runs as a no-op and counts for nothing, its active count being 0).  In the
-  // straggler tail each step is short and most likely the last, so the count
-  // is awaited before the step's Chebyshev products, as a blocking poll
-  // (queued no-op steps cost more than the wait: 2.50 -> 2.58 ms per
-  // 1 250-replicate shard with look-ahead throughout).  Without the buffer: a
-  // blocking poll every `poll` steps, every step in the tail.
+  // Convergence polls from the step most replicates retire at (first_poll) on.  After each such step the device
+  // rebuilds the list of active replicates (the GEMMs compact to it once it holds < 1/8 of the batch, decided on the
+  // device, so no host round trip sits in front of the straggler phase) and, with a pinned read-back buffer, the
+  // active count is copied to host[it] behind an event.  Outside the tail the host does not wait for it: it queues
+  // the next step first and reads the previous step's count then (one step of look-ahead — the GPU always has a step
+  // queued while the host decides; a step queued after the last replicate retired runs as a no-op and counts for
+  // nothing, its active count being 0).  In the straggler tail each step is short and most likely the last, so the
+  // count is awaited before the step's Chebyshev products, as a blocking poll (queued no-op steps cost more than the
+  // wait: 2.50 -> 2.58 ms per 1 250-replicate shard with look-ahead throughout).  Without the buffer: a blocking poll
+  // every `poll` steps, every step in the tail.
   const int first_poll = warm_started ? 1 : poll - 1;
   const bool ahead = pb && pb->host && pb->cap >= maxit + 2;
-  const bool probe = !ap2_probe_off();
+  const bool probe = !sw.ap2_probe_off;
   int it = 0, last_gemm = -1, last_cheb = -1, next_poll = first_poll, pend = -1, steps = -1;
   bool tail = false;
   if (skip0) {
-    // Filter alone: step 0 without its Rayleigh-Ritz step.  S_d = a_d Q0 (prep
-    // left the Z, a, cc, PV, FV of Q0; a_d goes into the first step's scale),
-    // d0 products, the last step writes the new basis into cur with its Z, a, cc
-    // (lowp: products 1 .. d0 - 1 in fp32 — prep left Z0 as float, each middle step hands the next a float Z, the
-    // last of them an fp64 Z for product d0; split: bf16 planes where lowp has floats; split_last: planes from the
-    // last middle step too, and product d0 on the split kernel with fp64 rows out)
+    // Filter alone: step 0 without its Rayleigh-Ritz step.  S_d = a_d Q0 (prep left the Z, a, cc, PV, FV of Q0; a_d
+    // goes into the first step's scale), d0 products, the last step writes the new basis into cur with its Z, a, cc
+    // (the kernels of the products and the formats between them: plan, dfm_fact_plan.h)
     for (int sp = 1; sp <= d0; ++sp) {
-      if (int rc = (lowp && sp < d0) ? hz32() : (split_last && sp == d0) ? hz_split_rows() : hz(false)) return rc;
-      if (sp < d0)
-        horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0,
-                   !lowp ? 0 : (sp < d0 - 1 || split_last) ? (split ? 3 : 1) : 2);
+      if (int rc = product(plan.product[sp], false, sp == d0 && plan.zero_zpad)) return rc;
+      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, plan.mid_in[sp], plan.mid_out[sp]);
       else horner_last(ca0[0], 0.0, Q0, 0, bfix);
     }
     last_gemm = last_cheb = 0;
@@ -2093,7 +1929,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     const double bb = it == 0 ? beta0 : 0.0;
     hipError_t e;
     // Rayleigh-Ritz step: Y = G* Q, the p x p problem, U / residuals / the next product's operands
-    if (int rc = hz(cl_on)) return rc;
+    if (int rc = product(HzProduct::F64, cl_on)) return rc;
     last_gemm = it;
     { TimerScope ts(a, DFM_KC_EIG_GQ);
       hipLaunchKernelGGL(y2k, dim3(nb), dim3(64 * BW), (size_t)m * 12, st, fb, w, m, idx, eta, HZ, ldz, pz,
@@ -2145,7 +1981,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
       // Filter: d - 1 products G* S_{i+1} and Horner steps S_i, i = d-2 .. 0: the new
       // basis S_0 goes back into cur (Q), Y stays in alt
       for (int sp = 2; sp <= dg; ++sp) {
-        if (int rc = hz(cl_on)) return rc;
+        if (int rc = product(HzProduct::F64, cl_on)) return rc;
         if (mid && it == 0 && sp < dg) horner_mid(ca[dg - sp], bb, 0.0, 1.0);
         else horner_last(ca[dg - sp], bb, w.U, (int64_t)m * P, 0.0);
       }
@@ -2158,8 +1994,8 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   }
   if (steps < 0) steps = it;
   g_last_iters = steps;
-  g_last_gemm_products_f32 = lowp ? (int64_t)(d0 - 1) * nb : 0;
-  g_last_gemm_products_split_last = split_last ? (int64_t)nb : 0;
+  g_last_gemm_products_f32 = (int64_t)plan.products_f32 * nb;
+  g_last_gemm_products_split_last = (int64_t)plan.products_split_last * nb;
   // the Chebyshev GEMM of iteration it runs after that iteration's check
   if (f.cnt) {   // (counted by eig_final_kernel below)
     g_last_rep_iters = g_last_gemm_products = 0;

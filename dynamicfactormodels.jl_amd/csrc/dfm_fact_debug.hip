@@ -1,8 +1,7 @@
-// dfm_fact_debug.hip — dfm_debug_hz_f32 (tests/test_gpu_f32_filter.py),
-// dfm_debug_hz_split (tests/test_gpu_bf16_split.py) and dfm_debug_hz_split_rows
-// (tests/test_gpu_split_last.py): the fp32 and the bf16-split H.Z GEMM of the
-// factored solver's warm filter, on operands packed as the solver packs them
-// (zrm_ix, Zs: dfm_internal.h).
+// dfm_fact_debug.hip — dfm_debug_hz_f32 (tests/test_gpu_f32_filter.py), dfm_debug_hz_split
+// (tests/test_gpu_bf16_split.py) and dfm_debug_hz_split_rows (tests/test_gpu_split_last.py): the fp32 and the
+// bf16-split H.Z GEMM of the factored solver's warm filter, on operands packed as the solver packs them (zrm_ix, Zs:
+// dfm_internal.h).
 #include "dfm_internal.h"
 #include <vector>
 
@@ -46,108 +45,79 @@ __global__ void dbg_unpack_hz32_kernel(const float *__restrict__ C32, int T, int
   const int x = (int)(i - (int64_t)s * nb * pz), rep = x / pz, c = x - rep * pz;
   out[i] = (double)C32[zrm_ix(rep, s, c, pz, zrm_stride(T, pz))];
 }
-}  // namespace dfm
-
-// Debug entry, not part of include/dfm.h.  H: device, T x ldH fp64, ldH >=
-// round_up(T, 16) with zero padding columns; Z: device, T x nb pz fp64
-// (replicate rep's columns rep pz .. rep pz + pz - 1).  Builds H32 =
-// float(H / hmax) (fact_h32_kernel) and Z32, runs gemmh_zrm_f32_kernel and
-// writes out = double(H32 Z32) as T x nb pz — NOT rescaled by hmax, which is
-// returned in *hmax_out (may be null).
-extern "C" int dfm_debug_hz_f32(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
-                                double *out, double *hmax_out) {
-  using namespace dfm;
-  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || ldH < (T + 15) / 16 * 16 || (ldH & 3)) return -1;
-  hipStream_t st = ctx_stream(ctx);
-  const int64_t zrs = (int64_t)((T + 15) & ~15) * pz;
-  char *buf = nullptr;
-  const size_t b_hd = ((size_t)T * 8 + 255) & ~size_t(255), b_h32 = ((size_t)T * ldH * 4 + 255) & ~size_t(255),
-               b_z = ((size_t)nb * zrs * 4 + 255) & ~size_t(255);
-  if (hipMalloc((void **)&buf, b_hd + b_h32 + 2 * b_z) != hipSuccess) return 1002;
-  double *hd = (double *)buf;
-  float *H32 = (float *)(buf + b_hd), *Z32 = (float *)(buf + b_hd + b_h32), *C32 = (float *)(buf + b_hd + b_h32 + b_z);
-  hipLaunchKernelGGL(dbg_diag_kernel, dim3((T + 255) / 256), dim3(256), 0, st, H, ldH, T, hd);
-  hipError_t e = launch_fact_h32(H, ldH, T, hd, H32, st);
-  hipLaunchKernelGGL(dbg_pack_z32_kernel, dim3((unsigned)(((int64_t)nb * zrs + 255) / 256)), dim3(256), 0, st, Z, T, nb,
-                     pz, Z32);
-  if (e == hipSuccess) e = launch_gemm_zrm_f32(H32, ldH, Z32, pz, zrs, C32, T, nb * pz, T, st);
-  hipLaunchKernelGGL(dbg_unpack_hz32_kernel, dim3((unsigned)(((int64_t)T * nb * pz + 255) / 256)), dim3(256), 0, st, C32,
-                     T, nb, pz, out);
-  std::vector<double> hdh(T);
-  if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = hipGetLastError();
-  hipFree(buf);
-  if (e != hipSuccess) return 1000 + (int)e;
-  if (hmax_out) *hmax_out = fact_hmax(hdh.data(), T);
-  return 0;
-}
-
-// The same for the bf16-split product: Hs (fact_hsplit_kernel) and Zs (the
-// solver's zsplit_store_chunk), gemmh_zrm_split_kernel, out = double(C32);
-// pz <= 32.
-extern "C" int dfm_debug_hz_split(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
-                                  double *out, double *hmax_out) {
-  using namespace dfm;
-  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || pz > 32 || ldH < (T + 15) / 16 * 16) return -1;
-  hipStream_t st = ctx_stream(ctx);
-  const int64_t zrs = (int64_t)((T + 15) & ~15) * pz;
-  const int nch = (T + 15) >> 4;
-  char *buf = nullptr;
-  const size_t b_hd = ((size_t)T * 8 + 255) & ~size_t(255), b_hs = (hsplit_bytes(T) + 255) & ~size_t(255),
-               b_z = ((size_t)nb * zrs * 8 + 255) & ~size_t(255), b_c = ((size_t)nb * zrs * 4 + 255) & ~size_t(255);
-  if (hipMalloc((void **)&buf, b_hd + b_hs + b_z + b_c) != hipSuccess) return 1002;
-  double *hd = (double *)buf;
-  char *Hs = buf + b_hd, *Zs = buf + b_hd + b_hs;
-  float *C32 = (float *)(buf + b_hd + b_hs + b_z);
-  hipLaunchKernelGGL(dbg_diag_kernel, dim3((T + 255) / 256), dim3(256), 0, st, H, ldH, T, hd);
-  hipError_t e = launch_fact_hsplit(H, ldH, T, hd, Hs, st);
-  hipLaunchKernelGGL(dbg_pack_zs_kernel, dim3((unsigned)(((int64_t)nb * nch + 3) / 4)), dim3(256), 0, st, Z, T, nb, pz, Zs);
-  if (e == hipSuccess) e = launch_gemm_zrm_split(Hs, Zs, pz, zrs, C32, T, nb * pz, T, st);
-  hipLaunchKernelGGL(dbg_unpack_hz32_kernel, dim3((unsigned)(((int64_t)T * nb * pz + 255) / 256)), dim3(256), 0, st, C32,
-                     T, nb, pz, out);
-  std::vector<double> hdh(T);
-  if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = hipGetLastError();
-  hipFree(buf);
-  if (e != hipSuccess) return 1000 + (int)e;
-  if (hmax_out) *hmax_out = fact_hmax(hdh.data(), T);
-  return 0;
-}
-
-// The split product through the kernel's fp64 epilogue (round 19,
-// tests/test_gpu_split_last.py): the same Hs and Zs, and
-// launch_gemm_zrm_split_rows writes hmax C32 straight into the caller's out
-// (device, T rows of nb pz columns, row stride ldo >= nb pz).  Nothing of out
-// but those T x nb pz elements is written.
-extern "C" int dfm_debug_hz_split_rows(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
-                                       double *out, int64_t ldo, double *hmax_out) {
-  using namespace dfm;
-  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || pz > 32 || ldH < (T + 15) / 16 * 16 ||
-      ldo < (int64_t)nb * pz)
+// The three entries: one allocation [hd | packed H | packed Z | C32], the diagonal, H and Z packed as the solver packs
+// them — Hs (fact_hsplit_kernel) and Zs (the solver's zsplit_store_chunk), or for F32 H32 = float(H / hmax)
+// (fact_h32_kernel) and Z32 — then the product.  F32 and Split write out = double(C32) as T x nb pz, NOT rescaled by
+// hmax; SplitRows reads hmax back first (it is the launch's scale, as FactBase::hmax is the solver's) and lets
+// launch_gemm_zrm_split_rows write hmax C32 straight into out (row stride ldo).
+enum class DbgHz { F32, Split, SplitRows };
+static int dbg_hz(DbgHz kind, dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
+                  double *out, int64_t ldo, double *hmax_out) {
+  const bool split = kind != DbgHz::F32, rows = kind == DbgHz::SplitRows;
+  if (!ctx || !H || !Z || !out || T < 1 || nb < 1 || pz < 1 || ldH < (T + 15) / 16 * 16 ||
+      (split ? pz > 32 : (ldH & 3) != 0) || (rows && ldo < (int64_t)nb * pz))
     return -1;
   hipStream_t st = ctx_stream(ctx);
   const int64_t zrs = (int64_t)((T + 15) & ~15) * pz;
-  const int nch = (T + 15) >> 4;
+  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t b_hd = up((size_t)T * 8), b_h = up(split ? hsplit_bytes(T) : (size_t)T * ldH * 4),
+               b_z = up((size_t)nb * zrs * (split ? 8 : 4)), b_c = rows ? 0 : up((size_t)nb * zrs * 4);
   char *buf = nullptr;
-  const size_t b_hd = ((size_t)T * 8 + 255) & ~size_t(255), b_hs = (hsplit_bytes(T) + 255) & ~size_t(255),
-               b_z = ((size_t)nb * zrs * 8 + 255) & ~size_t(255);
-  if (hipMalloc((void **)&buf, b_hd + b_hs + b_z) != hipSuccess) return 1002;
+  if (hipMalloc((void **)&buf, b_hd + b_h + b_z + b_c) != hipSuccess) return 1002;
   double *hd = (double *)buf;
-  char *Hs = buf + b_hd, *Zs = buf + b_hd + b_hs;
+  char *Hp = buf + b_hd, *Zp = Hp + b_h;
+  float *C32 = (float *)(Zp + b_z);
   hipLaunchKernelGGL(dbg_diag_kernel, dim3((T + 255) / 256), dim3(256), 0, st, H, ldH, T, hd);
-  hipError_t e = launch_fact_hsplit(H, ldH, T, hd, Hs, st);
-  hipLaunchKernelGGL(dbg_pack_zs_kernel, dim3((unsigned)(((int64_t)nb * nch + 3) / 4)), dim3(256), 0, st, Z, T, nb, pz, Zs);
-  std::vector<double> hdh(T);   // hmax first: it is the launch's scale, as FactBase::hmax is the solver's
-  if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  const double hmax = e == hipSuccess ? fact_hmax(hdh.data(), T) : 1.0;
-  if (e == hipSuccess) e = launch_gemm_zrm_split_rows(Hs, Zs, pz, zrs, out, ldo, hmax, T, nb * pz, T, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  hipError_t e = split ? launch_fact_hsplit(H, ldH, T, hd, Hp, st) : launch_fact_h32(H, ldH, T, hd, (float *)Hp, st);
+  if (split)
+    hipLaunchKernelGGL(dbg_pack_zs_kernel, dim3((unsigned)(((int64_t)nb * ((T + 15) >> 4) + 3) / 4)), dim3(256), 0, st, Z,
+                       T, nb, pz, Zp);
+  else
+    hipLaunchKernelGGL(dbg_pack_z32_kernel, dim3((unsigned)(((int64_t)nb * zrs + 255) / 256)), dim3(256), 0, st, Z, T, nb,
+                       pz, (float *)Zp);
+  std::vector<double> hdh(T);
+  auto read_hmax = [&]() {   // behind everything queued so far
+    if (e == hipSuccess) e = hipMemcpyAsync(hdh.data(), hd, (size_t)T * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e == hipSuccess ? fact_hmax(hdh.data(), T) : 1.0;
+  };
+  double hmax = 1.0;
+  if (rows) {
+    hmax = read_hmax();
+    if (e == hipSuccess) e = launch_gemm_zrm_split_rows(Hp, Zp, pz, zrs, out, ldo, hmax, T, nb * pz, T, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  } else {
+    if (e == hipSuccess)
+      e = split ? launch_gemm_zrm_split(Hp, Zp, pz, zrs, C32, T, nb * pz, T, st)
+                : launch_gemm_zrm_f32((const float *)Hp, ldH, (const float *)Zp, pz, zrs, C32, T, nb * pz, T, st);
+    hipLaunchKernelGGL(dbg_unpack_hz32_kernel, dim3((unsigned)(((int64_t)T * nb * pz + 255) / 256)), dim3(256), 0, st, C32,
+                       T, nb, pz, out);
+    hmax = read_hmax();
+  }
   if (e == hipSuccess) e = hipGetLastError();
   hipFree(buf);
   if (e != hipSuccess) return 1000 + (int)e;
   if (hmax_out) *hmax_out = hmax;
   return 0;
+}
+}  // namespace dfm
+
+// Debug entries, not part of include/dfm.h.  H: device, T x ldH fp64, ldH >= round_up(T, 16) with zero padding
+// columns (a multiple of 4 for the fp32 kernel); Z: device, T x nb pz fp64 (replicate rep's columns rep pz .. rep pz +
+// pz - 1; pz <= 32 for the split kernel); out: device, T x nb pz; hmax is returned in *hmax_out (may be null).
+// gemmh_zrm_f32_kernel:
+extern "C" int dfm_debug_hz_f32(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
+                                double *out, double *hmax_out) {
+  return dfm::dbg_hz(dfm::DbgHz::F32, ctx, H, ldH, T, Z, nb, pz, out, 0, hmax_out);
+}
+// gemmh_zrm_split_kernel:
+extern "C" int dfm_debug_hz_split(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
+                                  double *out, double *hmax_out) {
+  return dfm::dbg_hz(dfm::DbgHz::Split, ctx, H, ldH, T, Z, nb, pz, out, 0, hmax_out);
+}
+// ... through its fp64 epilogue (tests/test_gpu_split_last.py): out has row stride ldo >= nb pz, and nothing of it but
+// the T x nb pz elements is written
+extern "C" int dfm_debug_hz_split_rows(dfm_ctx *ctx, const double *H, int64_t ldH, int T, const double *Z, int nb, int pz,
+                                       double *out, int64_t ldo, double *hmax_out) {
+  return dfm::dbg_hz(dfm::DbgHz::SplitRows, ctx, H, ldH, T, Z, nb, pz, out, ldo, hmax_out);
 }

@@ -246,27 +246,19 @@ hipError_t launch_gemm_zrm(const double *A, int64_t lda, const double *Z, int pz
 }
 
 // ---------------------------------------------------------------------------
-// gemmh_zrm_f32_kernel: C32 = H32 Z32 in fp32 (v_mfma_f32_32x32x2_f32) for the
-// middle products of a warm solve's filter-only first step under the
-// eigenvalue rule (round 8; dfm_fact.hip, eig_run_fact2_t: lowp).  H32 is the
-// model's H in float, divided by its largest diagonal entry (|H32| <= 1; lda
-// >= round_up(K, 16), zero k-padding); Z32 and C32 both use the replicate-
-// major 16-row chunk indexing of gemmh_zrm_kernel's Z with float elements
-// (element (s, c) of replicate rep at rep zrs + (s >> 4) 16 pz + 16 c +
-// (s & 15), chunk rows past the matrix zero in Z32, unspecified in C32).
-// 128 x 128 workgroup tile, each wave 64 x 64 as 2 x 2 MFMA tiles (64
-// accumulator VGPRs); 16-deep k stages by LDS-DMA through a 3-deep ring at 3
-// workgroups per CU (16 KB per stage), one barrier per stage as
-// gemmh_zrm_kernel.  Both LDS images are [a][k] with 64-B rows; the 16-B piece
-// q of row a sits at piece q ^ ((a >> 2) & 3), so the ds_read_b128 fragment
-// reads (32 rows x one piece per half-wave) touch 16 distinct 16-B slots in
-// each of the instruction's 16-lane groups.  Lane half h reads k = 8h .. 8h+7
-// of its row in two 16-B pieces and MFMA step e pairs k = e (h = 0) with
-// k = 8 + e (h = 1): a column's sum runs over k in one fixed order whatever
-// its tile, its place in the batch or nb.  The epilogue stores the
-// accumulator's four consecutive rows per register group as one 16-B piece
-// of the column's chunk.  No col_done / clist: every replicate is active in
-// step 0.
+// gemmh_zrm_f32_kernel: C32 = H32 Z32 in fp32 (v_mfma_f32_32x32x2_f32) for the middle products of a warm solve's
+// filter-only first step under the eigenvalue rule (dfm_fact_plan.h: HzProduct::F32).  H32 is the model's H in float,
+// divided by its largest diagonal entry (|H32| <= 1; lda >= round_up(K, 16), zero k-padding); Z32 and C32 both use the
+// replicate-major 16-row chunk indexing of gemmh_zrm_kernel's Z with float elements (element (s, c) of replicate rep
+// at rep zrs + (s >> 4) 16 pz + 16 c + (s & 15), chunk rows past the matrix zero in Z32, unspecified in C32).
+// 128 x 128 workgroup tile, each wave 64 x 64 as 2 x 2 MFMA tiles (64 accumulator VGPRs); 16-deep k stages by LDS-DMA
+// through a 3-deep ring at 3 workgroups per CU (16 KB per stage), one barrier per stage as gemmh_zrm_kernel.  Both
+// LDS images are [a][k] with 64-B rows; the 16-B piece q of row a sits at piece q ^ ((a >> 2) & 3), so the
+// ds_read_b128 fragment reads (32 rows x one piece per half-wave) touch 16 distinct 16-B slots in each of the
+// instruction's 16-lane groups.  Lane half h reads k = 8h .. 8h+7 of its row in two 16-B pieces and MFMA step e pairs
+// k = e (h = 0) with k = 8 + e (h = 1): a column's sum runs over k in one fixed order whatever its tile, its place in
+// the batch or nb.  The epilogue stores the accumulator's four consecutive rows per register group as one 16-B piece
+// of the column's chunk.  No col_done / clist: every replicate is active in step 0.
 namespace {
 constexpr int F32_GT = 128, F32_KS = 16, F32_STAGE = 2 * F32_GT * F32_KS;   // floats per stage (A + B)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -384,28 +376,22 @@ hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int 
 }
 
 // ---------------------------------------------------------------------------
-// gemmh_zrm_split_kernel: the same product, C32 ~ (H / hmax) Z, as six bf16
-// MFMA terms (round 15).  Both operands arrive split into three bf16 planes,
-// x ~ h + m + l (dfm_internal.h: Hs, Zs; the GEMM converts nothing), and
-// C32 = sum over the plane pairs of weight >= 2^-18 — (l,h) (h,l) (m,m) (m,h)
-// (h,m) (h,h), the small terms first — on v_mfma_f32_32x32x16_bf16 with fp32
-// accumulators: a product of two bf16 numbers is exact in fp32, and the
-// dropped pairs and split remainders are below 2^-25 |H| |Z|.
-// Tile, waves, XCD order and epilogue are gemmh_zrm_f32_kernel's.  One k = 16
-// stage is 24 KB: per operand six [128 rows] images of 16-B pieces, one per
-// (plane, k half) — piece (pi, kh, a) at (2 pi + kh) 128 + a, so a wave's
-// 1 KB DMA instruction fills 64 consecutive rows of one image from 64
-// consecutive pieces of Hs (or one image's pieces of consecutive Z columns),
-// and a ds_read_b128 fragment read (lane: row l & 31, k half l >> 5) touches
-// 16 distinct 16-B slots in each of its 16-lane groups with no swizzle.  The
-// six terms share one set of fragments per stage: 12 reads per 24 MFMAs.
-// 3-deep ring at 2 workgroups per CU (72 KB), six DMA instructions per wave
-// and stage.  Every output element adds its six terms in that order stage by
-// stage, whatever its tile, its place in the batch, nb or the lane.
-// ROWS64 (round 19, the warm filter's last product): the same accumulators
-// leave as fp64 rows scale * C32 of the column-interleaved HZ (row stride ldc)
-// that gemmh_zrm_kernel writes, instead of float chunk pieces; everything
-// before the epilogue is the same code.
+// gemmh_zrm_split_kernel: the same product, C32 ~ (H / hmax) Z, as six bf16 MFMA terms (HzProduct::Split).  Both
+// operands arrive split into three bf16 planes, x ~ h + m + l (dfm_internal.h: Hs, Zs; the GEMM converts nothing), and
+// C32 = sum over the plane pairs of weight >= 2^-18 — (l,h) (h,l) (m,m) (m,h) (h,m) (h,h), the small terms first — on
+// v_mfma_f32_32x32x16_bf16 with fp32 accumulators: a product of two bf16 numbers is exact in fp32, and the dropped
+// pairs and split remainders are below 2^-25 |H| |Z|.
+// Tile, waves, XCD order and epilogue are gemmh_zrm_f32_kernel's.  One k = 16 stage is 24 KB: per operand six
+// [128 rows] images of 16-B pieces, one per (plane, k half) — piece (pi, kh, a) at (2 pi + kh) 128 + a, so a wave's
+// 1 KB DMA instruction fills 64 consecutive rows of one image from 64 consecutive pieces of Hs (or one image's pieces
+// of consecutive Z columns), and a ds_read_b128 fragment read (lane: row l & 31, k half l >> 5) touches 16 distinct
+// 16-B slots in each of its 16-lane groups with no swizzle.  The six terms share one set of fragments per stage: 12
+// reads per 24 MFMAs.  3-deep ring at 2 workgroups per CU (72 KB), six DMA instructions per wave and stage.  Every
+// output element adds its six terms in that order stage by stage, whatever its tile, its place in the batch, nb or
+// the lane.
+// ROWS64 (HzProduct::SplitRows, the warm filter's last product): the same accumulators leave as fp64 rows scale * C32
+// of the column-interleaved HZ (row stride ldc) that gemmh_zrm_kernel writes, instead of float chunk pieces;
+// everything before the epilogue is the same code.
 namespace {
 constexpr int SP_GT = 128, SP_KS = 16, SP_IMG = SP_GT * 16, SP_STAGE = 12 * SP_IMG;   // bytes
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -528,35 +514,33 @@ __global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__r
   }
 }
 
-// Hs (hsplit_bytes(M), launch_fact_hsplit) times the split Z of nb = Nc / pz
-// replicates (dfm_internal.h: Zs; zrs = round_up(M, 16) pz, the fp64 Z's
-// replicate stride) -> C32 in launch_gemm_zrm_f32's layout (gemmh_zrm_split_kernel)
-hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
-                                 hipStream_t st) {
+// Hs (hsplit_bytes(M), launch_fact_hsplit) times the split Z of nb = Nc / pz replicates (dfm_internal.h: Zs; zrs =
+// round_up(M, 16) pz, the fp64 Z's replicate stride): one checked launcher for both epilogues of
+// gemmh_zrm_split_kernel (ldc and scale are the fp64 rows' alone) ...
+template <bool ROWS64, class CT>
+static hipError_t launch_split(const void *Hs, const void *Zs, int pz, int64_t zrs, CT *C, int64_t ldc, double scale,
+                               int M, int Nc, int K, hipStream_t st) {
   const int64_t kpad = (K + SP_KS - 1) / SP_KS * SP_KS;
-  if (!Hs || !Zs || M < 1 || pz < 1 || Nc < pz || Nc % pz || M != K || zrs < kpad * pz || (zrs & 3))
+  if (!Hs || !Zs || !C || M < 1 || pz < 1 || Nc < pz || Nc % pz || M != K || zrs < kpad * pz || (zrs & 3) ||
+      (ROWS64 && ldc < Nc))
     return hipErrorInvalidValue;
   const int nrb = (M + SP_GT - 1) / SP_GT, ncb = (Nc + SP_GT - 1) / SP_GT;
   const int ncb8 = (ncb + 7) / 8 * 8;
-  hipLaunchKernelGGL(gemmh_zrm_split_kernel<false>, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs,
-                     hsplit_rows(M), (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb, (int64_t)0, 1.0);
-  return hipGetLastError();
-}
-
-// The same product delivered as fp64 rows, C (M x Nc, row stride ldc >= Nc) = scale C32 in launch_gemm_zrm's
-// column-interleaved layout (gemmh_zrm_split_kernel<true>): the last product of a warm filter (scale = hmax),
-// whose rows the last Horner step gathers as it gathers an fp64 product's.  Nothing outside rows < M and
-// columns < Nc is written.
-hipError_t launch_gemm_zrm_split_rows(const void *Hs, const void *Zs, int pz, int64_t zrs, double *C, int64_t ldc,
-                                      double scale, int M, int Nc, int K, hipStream_t st) {
-  const int64_t kpad = (K + SP_KS - 1) / SP_KS * SP_KS;
-  if (!Hs || !Zs || !C || M < 1 || pz < 1 || Nc < pz || Nc % pz || M != K || zrs < kpad * pz || (zrs & 3) || ldc < Nc)
-    return hipErrorInvalidValue;
-  const int nrb = (M + SP_GT - 1) / SP_GT, ncb = (Nc + SP_GT - 1) / SP_GT;
-  const int ncb8 = (ncb + 7) / 8 * 8;
-  hipLaunchKernelGGL(gemmh_zrm_split_kernel<true>, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs,
+  hipLaunchKernelGGL(gemmh_zrm_split_kernel<ROWS64>, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs,
                      hsplit_rows(M), (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb, ldc, scale);
   return hipGetLastError();
+}
+// ... -> C32 in launch_gemm_zrm_f32's layout
+hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
+                                 hipStream_t st) {
+  return launch_split<false>(Hs, Zs, pz, zrs, C, 0, 1.0, M, Nc, K, st);
+}
+// ... or delivered as fp64 rows, C (M x Nc, row stride ldc >= Nc) = scale C32 in launch_gemm_zrm's column-interleaved
+// layout: the last product of a warm filter (scale = hmax), whose rows the last Horner step gathers as it gathers an
+// fp64 product's.  Nothing outside rows < M and columns < Nc is written.
+hipError_t launch_gemm_zrm_split_rows(const void *Hs, const void *Zs, int pz, int64_t zrs, double *C, int64_t ldc,
+                                      double scale, int M, int Nc, int K, hipStream_t st) {
+  return launch_split<true>(Hs, Zs, pz, zrs, C, ldc, scale, M, Nc, K, st);
 }
 
 // ---------------------------------------------------------------------------
