@@ -224,6 +224,7 @@ SIGNATURES = [
 # scan of tests/test_abi.py (letters and underscores) does not list
 EXTRA_SIGNATURES = [
     ("dfm_ctx_gemm_products_f32", C.c_int, [C.c_void_p, c_int64_p]),
+    ("dfm_ctx_gemm_products_split3", C.c_int, [C.c_void_p, c_int64_p]),
 ]
 
 # dfm_lasso_stats slots (include/dfm.h DFM_LASSO_STAT_*)

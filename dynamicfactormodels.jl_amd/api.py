@@ -98,9 +98,12 @@ class Context:
         self.check(self.lib.dfm_ctx_gemm_products_f32(self.h, C.byref(g32)))
         gsl = C.c_int64()
         self.check(self.lib.dfm_ctx_gemm_products_split_last(self.h, C.byref(gsl)))
+        gs3 = C.c_int64()
+        self.check(self.lib.dfm_ctx_gemm_products_split3(self.h, C.byref(gs3)))
         return {"batches": b.value, "iterations": t.value, "max_iterations": m.value,
                 "replicate_iterations": ri.value, "gemm_products": gp.value,
-                "gemm_products_f32": g32.value, "gemm_products_split_last": gsl.value}
+                "gemm_products_f32": g32.value, "gemm_products_split_last": gsl.value,
+                "gemm_products_split3": gs3.value}
 
     def close(self):
         if getattr(self, "h", None) and not _lib.shutting_down():

@@ -99,6 +99,7 @@ static void note_iters(dfm_ctx *ctx) {
   ctx->gemm_products += g_last_gemm_products;
   ctx->gemm_products_f32 += g_last_gemm_products_f32;
   ctx->gemm_products_split_last += g_last_gemm_products_split_last;
+  ctx->gemm_products_split3 += g_last_gemm_products_split3;
 }
 
 // Per-batch device workspace layout for the bootstrap.
@@ -262,8 +263,9 @@ static int bootstrap_lanes(dfm_model *M, int nl, int kind, int64_t B, const int3
     ctx->gemm_products += lc->gemm_products;
     ctx->gemm_products_f32 += lc->gemm_products_f32;
     ctx->gemm_products_split_last += lc->gemm_products_split_last;
+    ctx->gemm_products_split3 += lc->gemm_products_split3;
     lc->eig_batches = lc->eig_iters = lc->eig_iters_max = lc->rep_iters = lc->gemm_products = 0;
-    lc->gemm_products_f32 = lc->gemm_products_split_last = 0;
+    lc->gemm_products_f32 = lc->gemm_products_split_last = lc->gemm_products_split3 = 0;
   }
   if (rcl[0]) return rcl[0];
   for (int j = 1; j < nl; ++j)

@@ -291,7 +291,7 @@ int dfm_ctx_reset_timing(dfm_ctx *ctx) {
   merge_kids(ctx);
   for (int i = 0; i < DFM_KC_COUNT; ++i) { ctx->ms[i] = 0; ctx->launches[i] = 0; }
   ctx->eig_batches = ctx->eig_iters = ctx->eig_iters_max = ctx->rep_iters = ctx->gemm_products = 0;
-  ctx->gemm_products_f32 = ctx->gemm_products_split_last = 0;
+  ctx->gemm_products_f32 = ctx->gemm_products_split_last = ctx->gemm_products_split3 = 0;
   hipMemsetAsync(ctx->cnt_dev, 0, 2 * sizeof(long long), ctx->stream);
   return 0;
 }
@@ -318,6 +318,11 @@ int dfm_ctx_gemm_products(dfm_ctx *ctx, int64_t *products) {
 int dfm_ctx_gemm_products_f32(dfm_ctx *ctx, int64_t *products) {
   if (!ctx || !products) return -1;
   *products = ctx->gemm_products_f32;
+  return 0;
+}
+int dfm_ctx_gemm_products_split3(dfm_ctx *ctx, int64_t *products) {
+  if (!ctx || !products) return -1;
+  *products = ctx->gemm_products_split3;
   return 0;
 }
 int dfm_ctx_gemm_products_split_last(dfm_ctx *ctx, int64_t *products) {

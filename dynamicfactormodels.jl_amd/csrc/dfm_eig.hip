@@ -900,6 +900,7 @@ thread_local int g_last_iters = 0;   // iterations run by the last eig_run / eig
 thread_local int64_t g_last_rep_iters = 0;
 thread_local int64_t g_last_gemm_products_f32 = 0;   // of g_last_gemm_products, those run in fp32 (factored solver only)
 thread_local int64_t g_last_gemm_products_split_last = 0;   // the warm filter's last products run as bf16 terms (factored solver only)
+thread_local int64_t g_last_gemm_products_split3 = 0;   // of the fp32 ones, those run as three bf16 terms (factored solver only)
 thread_local int64_t g_last_gemm_products = 0;   // replicate-products of the last run: H . Z (factored, both Chebyshev GEMMs) or G S (fused direct solver)
 
 // Sum of the unconverged-replicate counts seen by the products of iterations
@@ -1384,7 +1385,7 @@ static int eig_run_t(const double *G, int64_t ldg, int64_t strideG, int m, const
       }
       g_last_rep_iters = s;
       g_last_gemm_products = prods;
-      g_last_gemm_products_f32 = g_last_gemm_products_split_last = 0;
+      g_last_gemm_products_f32 = g_last_gemm_products_split_last = g_last_gemm_products_split3 = 0;
       if (prof) {
         long long h[24];
         hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
@@ -1451,7 +1452,7 @@ static int eig_run_t(const double *G, int64_t ldg, int64_t strideG, int m, const
   g_last_iters = it;
   g_last_rep_iters = count_rep_iters(w.active, std::min(it, maxit - 1), 0, nb, st);
   g_last_gemm_products = g_last_rep_iters;
-  g_last_gemm_products_f32 = g_last_gemm_products_split_last = 0;
+  g_last_gemm_products_f32 = g_last_gemm_products_split_last = g_last_gemm_products_split3 = 0;
   { TimerScope ts(a, DFM_KC_EIG_OTHER);
     hipLaunchKernelGGL(eig_final_kernel<P>, dim3(nb), dim3(256), 0, st, w, m, k, lam, Uk, status, trace_out);
   }

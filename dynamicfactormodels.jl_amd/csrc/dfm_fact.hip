@@ -31,13 +31,14 @@ typedef float zf4 __attribute__((ext_vector_type(4)));
 
 // A staged 16-row Z chunk (st: 16 pz doubles, element 16 c + row, this wave's LDS) to replicate rep's chunk `tile` of
 // Zc as whole 16-B pieces, in the format the next H.Z product reads: fp64, float (round to nearest, the same chunk
-// indexing with float elements) or the chunk's 6 pz pieces of the three bf16 planes (dfm_internal.h: Zs).
+// indexing with float elements) or the chunk's 6 pz pieces of the three bf16 planes (dfm_internal.h: Zs; planes = 2:
+// the 4 pz pieces of planes h and m alone).
 template <int P>
 DFM_DEV void zchunk_store(ZFmt zf, const double *st, double *__restrict__ Zc, int rep, int64_t zrs, int tile, int pz,
-                          int lane) {
+                          int lane, int planes) {
   if (zf == ZFmt::Split) {
     zsplit_store_chunk<P == 16>(st, pz, lane, reinterpret_cast<char *>(Zc + (int64_t)rep * zrs) +
-                                                  (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz);
+                                                  (int64_t)__builtin_amdgcn_readfirstlane(tile) * 96 * pz, planes);
   } else if (zf != ZFmt::F64) {
     zf4 *zc4 = reinterpret_cast<zf4 *>(reinterpret_cast<float *>(Zc) + (int64_t)rep * zrs + (int64_t)tile * 16 * pz);
     for (int e = lane; e < 4 * pz; e += 64)
@@ -110,6 +111,7 @@ struct PrepTail {   // PREP = true
   const double *apre;
   double *zst, *pvr;
   ZFmt zf;
+  int planes;   // of a Split Z0 (FilterPlan::z0_planes)
 };
 struct AccTail {   // PREP = false
   const dv4 *aacc;
@@ -191,7 +193,7 @@ DFM_DEV void zscatter_tail(const FactBase &fb, int T, int r, int ntile, int tid,
         for (int ct = 0; ct < NT; ++ct)
           if (16 * ct + li < pz) zst[16 * (16 * ct + li) + 4 * g + lk] = s0 + 4 * g + lk < T ? z[g][ct] : 0.0;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      zchunk_store<P>(src.zf, zst, Zc, rep, zrs, tile, pz, lane);
+      zchunk_store<P>(src.zf, zst, Zc, rep, zrs, tile, pz, lane, src.planes);
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -244,8 +246,10 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
                                                             const double *__restrict__ Q0, int ps,
                                                             double *__restrict__ Zc, int64_t ldz, int pz,
                                                             double *__restrict__ ab, const double *__restrict__ apre,
-                                                            double *__restrict__ PV, double *__restrict__ FV, ZFmt zf) {
-  // zf: the format Z0 leaves in (the first product's operand, FilterPlan::z0); PV, FV, a, cc stay fp64
+                                                            double *__restrict__ PV, double *__restrict__ FV, ZFmt zf,
+                                                            int zplanes) {
+  // zf: the format Z0 leaves in (the first product's operand, FilterPlan::z0; zplanes: the planes of a Split one,
+  // FilterPlan::z0_planes); PV, FV, a, cc stay fp64
   static_assert(64 * BW == 256, "the scans and the tree sum below are written for 256 threads");
   constexpr int NT = P / 16;
   __shared__ double sred[NT * 256];
@@ -367,7 +371,7 @@ __global__ __launch_bounds__(64 * BW) void boot_prep_kernel(FactBase fb, const i
     // (PV, FV: a warm solve without a first Rayleigh-Ritz step filters V0 = Q0 itself, so the middle Horner
     // steps' PV = P'D V0 is Z0 row by row and FV = F'V0 is a)
     zscatter_tail<P, true>(fb, T, r, ntile, tid, wave, lane, set, so, L, Q0, Zc, pz, rep, ab, sred, ps,
-                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, zf});
+                           PrepTail{apre, zst[wave], PV ? PV + (int64_t)rep * T * P : nullptr, zf, zplanes});
     if (FV)
       for (int e = tid; e < 16 * P; e += 256) FV[(int64_t)rep * 16 * P + e] = apre[e];
   }
@@ -1314,7 +1318,12 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_pv_kernel(FactBase fb, EigWor
 // up to the rounding of the bucket sums.  The tile's 16 PV rows — one contiguous range of 16 ps doubles — arrive as
 // 16-B pieces in the stage the PF rows take otherwise, and pA, pfa (columns < r, times pfs) and pv are read from
 // there: no PF loads, no PV row gathers.  PF and pfr are not read.
-template <int P, bool FAST, HzFmt HF, ZFmt ZF, bool NOPF = false>
+//
+// ZPL: the planes of the Split Z this step writes (FilterPlan::mid_planes), or 0 for the run-time argument zplanes.
+// The P = 16 instances take the argument (wave-uniform; their registers do not move).  At P = 32 the live argument
+// costs <32, false, Chunk32, Split, false> 8 B more scratch, so there the count is an instance (ZPL = 3: the
+// parent's code; ZPL = 2 beside it) and the argument is dead.
+template <int P, bool FAST, HzFmt HF, ZFmt ZF, bool NOPF = false, int ZPL = 0>
 __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, EigWork w, int T, int p,
                                                             const double *__restrict__ HZ, int64_t ldz, int pz,
                                                             double *__restrict__ ab, double fai, double bbeta, int k,
@@ -1324,7 +1333,9 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
                                                             const double *__restrict__ FV,
                                                             const double *__restrict__ FtF,
                                                             double *__restrict__ Zc, int ps, double bfix,
-                                                            double lead, double hscale, double pfs) {
+                                                            double lead, double hscale, double pfs, int zplanes) {
+  // zplanes: see ZPL (read by ZF = Split alone)
+  static_assert(ZPL == 0 || (ZF == ZFmt::Split && (ZPL == 2 || ZPL == 3)), "a plane count belongs to a Split Z");
   // bfix > 0: the interval end of a filter-only first step (boot_cheb_kernel); lead: the scale of the incoming
   // S_{i+1} not yet applied to its Z, a, cc — the filter's leading coefficient a_d at the first step of such a filter
   // (S_d = a_d V0 is never formed: prep left the Z, a, cc of V0), else 1
@@ -1553,7 +1564,7 @@ __global__ __launch_bounds__(64 * BW, 4) void boot_cheb_mid_kernel(FactBase fb, 
       }
     if constexpr (ZF == ZFmt::Split) {   // (the stage is this wave's until the next tile's PF rows, behind these reads in its LDS order)
       asm volatile("" ::: "memory");
-      zchunk_store<P>(ZF, sP, Zc, rep, zrs, tile, pz, lane);
+      zchunk_store<P>(ZF, sP, Zc, rep, zrs, tile, pz, lane, ZPL ? ZPL : zplanes);
     }
   }
   // a_i = (F'F bB + PF'u) / b + a_i FV  (dd columns: FV; columns >= p: 0)
@@ -1716,23 +1727,28 @@ __global__ void zpad_zero_kernel(double *__restrict__ Zc, int T, int pz, int64_t
 
 // The kernel instances eig_run_fact2_t launches.  stg: the loaders staged through LDS (y2_load's STG, the middle
 // steps' FAST), which exist for P = 16 only.  hf, zf, nopf: boot_cheb_mid_kernel's HF, ZF and NOPF; the four (hf, zf)
-// pairs are the ones a consistent FilterPlan holds.
+// pairs are the ones a consistent FilterPlan holds.  zplanes: the planes of a Split Z, an instance (ZPL) at P = 32.
 template <int P>
 static auto y2_instance(bool stg) { return stg ? boot_y2_kernel<P, P == 16> : boot_y2_kernel<P, false>; }
 template <int P>
 static auto cheb_instance(bool stg) { return stg ? boot_cheb_kernel<P, P == 16> : boot_cheb_kernel<P, false>; }
 template <int P, bool FAST, bool NOPF>
-static auto cheb_mid_pair(HzFmt hf, ZFmt zf) {
+static auto cheb_mid_pair(HzFmt hf, ZFmt zf, int zplanes) {
   if (hf == HzFmt::Rows64) return boot_cheb_mid_kernel<P, FAST, HzFmt::Rows64, ZFmt::F64, NOPF>;
   if (zf == ZFmt::F32) return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::F32, NOPF>;
   if (zf == ZFmt::F64) return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::F64, NOPF>;
-  return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::Split, NOPF>;
+  if constexpr (P == 16) {
+    return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::Split, NOPF>;   // (planes: the argument)
+  } else {
+    if (zplanes == 2) return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::Split, NOPF, 2>;
+    return boot_cheb_mid_kernel<P, FAST, HzFmt::Chunk32, ZFmt::Split, NOPF, 3>;
+  }
 }
 template <int P>
-static auto cheb_mid_instance(bool stg, HzFmt hf, ZFmt zf, bool nopf) {
+static auto cheb_mid_instance(bool stg, HzFmt hf, ZFmt zf, bool nopf, int zplanes) {
   constexpr bool F = P == 16;
-  if (!nopf) return !stg ? cheb_mid_pair<P, false, false>(hf, zf) : cheb_mid_pair<P, F, false>(hf, zf);
-  return !stg ? cheb_mid_pair<P, false, true>(hf, zf) : cheb_mid_pair<P, F, true>(hf, zf);
+  if (!nopf) return !stg ? cheb_mid_pair<P, false, false>(hf, zf, zplanes) : cheb_mid_pair<P, F, false>(hf, zf, zplanes);
+  return !stg ? cheb_mid_pair<P, false, true>(hf, zf, zplanes) : cheb_mid_pair<P, F, true>(hf, zf, zplanes);
 }
 
 template <int P>
@@ -1839,7 +1855,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     hipLaunchKernelGGL(boot_prep_kernel<P>, dim3(nb), dim3(64 * BW), prep_lds, st,
                        fb, idx, eta, off, lst, w.trace, mid && !nopf ? PFb : nullptr, mid ? E2b : nullptr, Q0, ps, Zc,
                        ldz, pz, ab, apre,
-                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, plan.z0);
+                       skip0 ? w.S : nullptr, skip0 ? FVb : nullptr, plan.z0, plan.z0_planes);
     if (mid && !fb.FtF) hipLaunchKernelGGL(ftf_kernel, dim3(1), dim3(1024), 0, st, fb, FtF);
   }
   const double *ftf = fb.FtF ? fb.FtF : FtF;
@@ -1851,10 +1867,11 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   //   F64        HZ = H Z in fp64 rows — listed: for the listed replicates' column groups, once the straggler list is on
   //   F32        HZ32 = H32 Z32 in fp32 (Z32 in the first half of Z's region, HZ32 in HZ's, both in Z's chunk layout;
   //              every replicate is active there: no col_done, no list)
-  //   Split      the same HZ32 from the bf16 planes of H and Z, Zs in Z's region at the fp64 replicate stride
+  //   Split      the same HZ32 from the bf16 planes of H and Z, Zs in Z's region at the fp64 replicate stride, as
+  //              `terms` plane pairs (FilterPlan::terms)
   //   SplitRows  HZ = hmax HZ32 from the same planes, written as F64 writes it
   // zpad: behind it the fp64 Z's pad rows, which no pass of step 0 wrote, are zeroed for the fp64 products that follow
-  auto product = [&](HzProduct kind, bool listed, bool zpad = false) -> int {
+  auto product = [&](HzProduct kind, bool listed, bool zpad = false, int terms = 0) -> int {
     TimerScope ts(a, DFM_KC_GEMM);
     hipError_t e = hipErrorInvalidValue;
     switch (kind) {
@@ -1866,7 +1883,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
         e = launch_gemm_zrm_f32(fb.H32, fb.ldH, (const float *)Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
         break;
       case HzProduct::Split:
-        e = launch_gemm_zrm_split(fb.Hs, Zc, pz, zrs, (float *)HZ, m, ncz, m, st);
+        e = launch_gemm_zrm_split(fb.Hs, Zc, pz, zrs, (float *)HZ, m, ncz, m, terms, st);
         break;
       case HzProduct::SplitRows:
         e = launch_gemm_zrm_split_rows(fb.Hs, Zc, pz, zrs, HZ, ldz, fb.hmax, m, ncz, m, st);
@@ -1880,12 +1897,12 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     return e == hipSuccess ? 0 : 1000 + (int)e;
   };
   // a middle Horner step S_i = G* S_{i+1} / b + c V0 in row-local form (Z, a, cc only), reading HZ as hf and
-  // writing Z as zf ...
+  // writing Z as zf (a Split one with zplanes planes) ...
   auto horner_mid = [&](double c, double bbeta, double bfx, double lead, HzFmt hf = HzFmt::Rows64,
-                        ZFmt zf = ZFmt::F64) {
+                        ZFmt zf = ZFmt::F64, int zplanes = 0) {
     TimerScope ts(a, DFM_KC_EIG_APPLY);
-    hipLaunchKernelGGL(cheb_mid_instance<P>(stg_ok, hf, zf, nopf), dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz,
-                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale);
+    hipLaunchKernelGGL(cheb_mid_instance<P>(stg_ok, hf, zf, nopf, zplanes), dim3(nb), dim3(64 * BW), 0, st, fb, w, m, p, HZ, ldz,
+                       pz, ab, c, bbeta, k, PFb, E2b, w.S, FVb, ftf, Zc, ps, bfx, lead, fb.hmax, f.fscale, zplanes);
   };
   // ... and the last one, S_0: the new basis into cur, with its Z, a, cc
   auto horner_last = [&](double c, double bbeta, const double *V0, int64_t v0s, double bfx) {
@@ -1914,8 +1931,10 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
     // goes into the first step's scale), d0 products, the last step writes the new basis into cur with its Z, a, cc
     // (the kernels of the products and the formats between them: plan, dfm_fact_plan.h)
     for (int sp = 1; sp <= d0; ++sp) {
-      if (int rc = product(plan.product[sp], false, sp == d0 && plan.zero_zpad)) return rc;
-      if (sp < d0) horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, plan.mid_in[sp], plan.mid_out[sp]);
+      if (int rc = product(plan.product[sp], false, sp == d0 && plan.zero_zpad, plan.terms[sp])) return rc;
+      if (sp < d0)
+        horner_mid(ca0[d0 - sp], 0.0, bfix, sp == 1 ? ca0[d0] : 1.0, plan.mid_in[sp], plan.mid_out[sp],
+                   plan.mid_planes[sp]);
       else horner_last(ca0[0], 0.0, Q0, 0, bfix);
     }
     last_gemm = last_cheb = 0;
@@ -1996,6 +2015,7 @@ static int eig_run_fact2_t(const FactBase &fb, const EigArgs &a, const FactArgs 
   g_last_iters = steps;
   g_last_gemm_products_f32 = (int64_t)plan.products_f32 * nb;
   g_last_gemm_products_split_last = (int64_t)plan.products_split_last * nb;
+  g_last_gemm_products_split3 = (int64_t)plan.products_split3 * nb;
   // the Chebyshev GEMM of iteration it runs after that iteration's check
   if (f.cnt) {   // (counted by eig_final_kernel below)
     g_last_rep_iters = g_last_gemm_products = 0;

@@ -47,10 +47,11 @@ constexpr int Q0G_PMAX = 32;   // the widest block q0_guards_kernel takes (eig_r
 //   DFM_FACT_F32         on       0       fp64 middle products (2)                                  profiles/r08_c3_ab.txt
 //   DFM_FACT_SPLIT       on       0       the fp32 launches, bit for bit (3)                        profiles/r15_c3_ab.txt
 //   DFM_FACT_SPLIT_LAST  on       0       the fp64 last product, bit for bit (4)                    profiles/r19_c3_ab.txt
+//   DFM_FACT_SPLIT3      on       0       six terms in every split product, bit for bit (7)         profiles/r21_c3_ab.txt
 //   DFM_AP2_PROBE        on       0       ap2's one-pass form throughout (5)                        profiles/r10_c3_ab.txt
 //   DFM_FACT_PF          stored   0       the NOPF middle steps (6)                                 profiles/r10_c3_ab.txt
 //
-// Precedence (plan_first_filter): SPLIT_LAST acts only where SPLIT is on, SPLIT only where F32 is on and the model
+// Precedence (plan_first_filter): SPLIT_LAST and SPLIT3 act only where SPLIT is on, SPLIT only where F32 is on and the model
 // holds the split H, F32 and PF only on a solve that starts with the filter (STEP0 off, a warm start, degree >= 3,
 // maxit >= 2), F32 only under the eigenvalue rule (tol < 0) with H32, a finite hmax > 0 and T >= 16.
 // (1) The filter amplifies wanted eigenvalue lambda_1 over lambda_k by about T_d(x_1) / T_d(x_k) ~ (x_1 / x_k)^d,
@@ -80,11 +81,17 @@ constexpr int Q0G_PMAX = 32;   // the widest block q0_guards_kernel takes (eig_r
 //     -0.09: the pass is bound by its load latency, not its bytes) — 2.3 times the parent's run-to-run spread, short
 //     of the 3 times this project asks of a change, so the stored form stays the default.  The middle steps behind a
 //     first Rayleigh-Ritz step (PV = P'D (Q Bm), boot_pv_kernel) have no such identity and always read stored PF.
+// (7) The error of product sp is damped by every Horner step behind it, so the accuracy of (3) is needed only near the
+//     end of the filter: the split products sp <= d0 - 2 run as three terms, (m,h) (h,m) (h,h), on planes h and m
+//     alone (>= 16 significand bits; gemmh_zrm_split_kernel's TERMS), and the pass in front of each writes only those
+//     two planes.  The CPU model (tools/eig_proto.py, TERMS=) moves no replicate in 1 200 with them, nor with operands
+//     of 14 bits there; three terms in product d0 - 1 hold only down to 16 bits and in product d0 not at all, so
+//     those two keep six.
 struct FactSwitches {
   int d0_cap = kChebWarmD0;
   double beta = kChebWarmBeta;
   bool keep_step0 = false, f32_off = false, split_off = false, split_last_off = false, ap2_probe_off = false;
-  bool pf_stored = true;
+  bool pf_stored = true, split3_off = false;
 };
 inline FactSwitches read_fact_switches() {
   auto env = [](const char *name, const char *unset) { const char *e = getenv(name); return e ? e : unset; };
@@ -98,6 +105,7 @@ inline FactSwitches read_fact_switches() {
   s.f32_off = is_zero("DFM_FACT_F32");
   s.split_off = is_zero("DFM_FACT_SPLIT");
   s.split_last_off = is_zero("DFM_FACT_SPLIT_LAST");
+  s.split3_off = is_zero("DFM_FACT_SPLIT3");
   s.ap2_probe_off = is_zero("DFM_AP2_PROBE");
   s.pf_stored = !(*env("DFM_FACT_PF", "") && is_zero("DFM_FACT_PF"));   // (an empty value leaves it stored)
   return s;
@@ -138,10 +146,17 @@ struct FilterPlan {
   HzProduct product[kFilterDMax + 1] = {};   // [1 .. d0]
   HzFmt mid_in[kFilterDMax + 1] = {};        // [1 .. d0 - 1]: what middle step sp reads ...
   ZFmt mid_out[kFilterDMax + 1] = {};        // ... and the Z it writes
+  // The split products' refinement (7): the plane pairs product sp adds up (6, or 3 on planes h and m alone; 0 for a
+  // product that is not split) and the planes of the Split Z that prep (z0_planes) and middle step sp (mid_planes[sp])
+  // write for the product behind them (3 or 2; 0 where that Z is not split)
+  int terms[kFilterDMax + 1] = {};           // [1 .. d0]
+  int z0_planes = 0;
+  int mid_planes[kFilterDMax + 1] = {};      // [1 .. d0 - 1]
   int pad_rows = 0;              // round_up(T, 16) - T: the rows of Z's last chunk past T
   bool zero_zpad = false;        // ... which no pass of step 0 writes in the fp64 Z: zeroed behind product d0
   int products_f32 = 0;          // per replicate: products not run in fp64 (gemm_products_f32 / nb) ...
   int products_split_last = 0;   // ... and last products run split (gemm_products_split_last / nb)
+  int products_split3 = 0;       // ... and those of products_f32 run as three terms (gemm_products_split3 / nb)
 
   // does prep or a middle step write fp64 Z chunks (whole ones, their pad rows zero)?
   bool writes_z64() const {
@@ -151,18 +166,24 @@ struct FilterPlan {
   }
   // The chain: every product reads the format the pass before it wrote, every Horner step reads what its product
   // wrote, the last one fp64 rows; a middle step fed fp64 rows writes fp64 (the instances that exist); and somebody
-  // writes the fp64 Z's pad rows, which the later fp64 products read.
+  // writes the fp64 Z's pad rows, which the later fp64 products read.  A split product of three terms is fed exactly
+  // two planes and one of six terms three; nothing else has terms or planes.
+  static constexpr int planes_of(HzProduct k, int terms) {
+    return operand_of(k) != ZFmt::Split ? (terms == 0 ? 0 : -1) : terms == 6 ? 3 : terms == 3 ? 2 : -1;
+  }
   bool consistent() const {
     if (d0 < kChebD || d0 > kFilterDMax || mid != (d0 >= 3)) return false;
     ZFmt z = z0;
+    int planes = z0_planes;
     for (int sp = 1; sp < d0; ++sp) {
       const HzFmt hz = result_of(product[sp]);
-      if (operand_of(product[sp]) != z || mid_in[sp] != hz) return false;
+      if (operand_of(product[sp]) != z || mid_in[sp] != hz || planes_of(product[sp], terms[sp]) != planes) return false;
       if (hz == HzFmt::Rows64 && mid_out[sp] != ZFmt::F64) return false;
       z = mid_out[sp];
+      planes = mid_planes[sp];
     }
     return operand_of(product[d0]) == z && result_of(product[d0]) == HzFmt::Rows64 &&
-           (pad_rows == 0 || zero_zpad || writes_z64());
+           planes_of(product[d0], terms[d0]) == planes && (pad_rows == 0 || zero_zpad || writes_z64());
   }
 };
 
@@ -200,6 +221,13 @@ inline FilterPlan plan_first_filter(const FilterPlanIn &in, const FactSwitches &
   for (int sp = 1; sp < pl.d0; ++sp) {
     pl.mid_in[sp] = result_of(pl.product[sp]);
     pl.mid_out[sp] = operand_of(pl.product[sp + 1]);
+  }
+  // ... three terms in the split products two or more short of the last (7), and the planes each one is fed
+  for (int sp = 1; sp <= pl.d0; ++sp) {
+    if (operand_of(pl.product[sp]) != ZFmt::Split) continue;
+    pl.terms[sp] = pl.product[sp] == HzProduct::Split && sp <= pl.d0 - 2 && !sw.split3_off ? 3 : 6;
+    pl.products_split3 += pl.terms[sp] == 3;
+    (sp == 1 ? pl.z0_planes : pl.mid_planes[sp - 1]) = FilterPlan::planes_of(pl.product[sp], pl.terms[sp]);
   }
   pl.pad_rows = (16 - (in.T & 15)) & 15;
   pl.zero_zpad = pl.pad_rows != 0 && !pl.writes_z64();

@@ -19,7 +19,8 @@
 // one XCD so a B tile is fetched from HBM once and re-read from that XCD's L2.
 // Two kernels are not fp64, both for the middle products of a warm
 // eigenvalue-rule solve's first filter: gemmh_zrm_split_kernel (six bf16 terms
-// on v_mfma_f32_32x32x16_bf16, the default) and gemmh_zrm_f32_kernel
+// on v_mfma_f32_32x32x16_bf16, three in the products two or more short of the
+// filter's last: the default) and gemmh_zrm_f32_kernel
 // (v_mfma_f32_32x32x2_f32, DFM_FACT_SPLIT=0).
 #include "dfm_internal.h"
 #include "dfm_tile.h"
@@ -393,25 +394,36 @@ hipError_t launch_gemm_zrm_f32(const float *A, int64_t lda, const float *Z, int 
 // of the column-interleaved HZ (row stride ldc) that gemmh_zrm_kernel writes, instead of float chunk pieces;
 // everything before the epilogue is the same code.
 namespace {
-constexpr int SP_GT = 128, SP_KS = 16, SP_IMG = SP_GT * 16, SP_STAGE = 12 * SP_IMG;   // bytes
+constexpr int SP_GT = 128, SP_KS = 16, SP_IMG = SP_GT * 16;   // bytes
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-template <int NBUF>
-DFM_DEV void split_ring_wait(int s, int nst) {   // ring_wait at six DMA instructions per wave and stage
-  static_assert(NBUF == 3, "ring depth");
-  if (nst - 1 - s >= 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+template <int NBUF, int PER>
+DFM_DEV void split_ring_wait(int s, int nst) {   // ring_wait at PER DMA instructions per wave and stage
+  static_assert(NBUF == 3 || NBUF == 4, "ring depth");
+  if (NBUF == 4 && nst - 1 - s >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
+  else if (nst - 1 - s >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 }
 }  // namespace
 
-template <bool ROWS64>
-__global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__restrict__ Hs, int mrows,
-                                                                const char *__restrict__ Zs, int pz, int64_t zrs,
-                                                                std::conditional_t<ROWS64, double, float> *__restrict__ C,
-                                                                int M, int Nc, int K, int nrb, int ncb, int64_t ldc,
-                                                                double scale) {
-  constexpr int NBUF = 3;
+// TERMS = 3 (the warm filter's split products two or more short of its last, dfm_fact_plan.h note (7); float chunks
+// only): the pairs (m,h) (h,m) (h,h) on planes h and m alone.  A stage holds only the images of planes 0 and 1 of both
+// operands — 8 images, 16 KB, four DMA instructions per wave — and gives 8 fragment reads per 12 MFMAs.  Hs and Zs
+// are the six-term form's: plane l's pieces, a third of every k-stage of Hs and the last 32 pz bytes of every Zs
+// chunk, are never addressed, so whatever they hold (nothing, where the pass in front wrote two planes) is unread.
+// The ring is NBUF deep at WGS workgroups per CU; the library's instance is kSplit3Nbuf / kSplit3Wgs (tools/
+// gemm_bench.hip times both candidates, profiles/r21_c3_ab.txt).  The TERMS = 6 instances are what they were.
+template <bool ROWS64, int TERMS = 6, int NBUF = 3, int WGS = 2>
+__global__ __launch_bounds__(256, WGS) void gemmh_zrm_split_kernel(const char *__restrict__ Hs, int mrows,
+                                                                  const char *__restrict__ Zs, int pz, int64_t zrs,
+                                                                  std::conditional_t<ROWS64, double, float> *__restrict__ C,
+                                                                  int M, int Nc, int K, int nrb, int ncb, int64_t ldc,
+                                                                  double scale) {
+  static_assert(TERMS == 6 || (TERMS == 3 && !ROWS64), "three terms leave as float chunks only");
+  constexpr int NPL = TERMS == 6 ? 3 : 2;            // planes staged per operand
+  constexpr int OPB = 2 * NPL * SP_IMG;              // one operand's images of a stage (bytes)
+  constexpr int SP_STAGE = 2 * OPB;
   __shared__ __attribute__((aligned(16))) char lds[NBUF * SP_STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -420,26 +432,26 @@ __global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__r
   if (cb >= ncb) return;
   const int abase = rb * SP_GT, bbase = cb * SP_GT;
   const int nst = (K + SP_KS - 1) / SP_KS;
-  // The stage's 24 DMA instructions, (operand, image q = 2 pi + kh, row half):
-  // wave w issues numbers 3 w .. 3 w + 2 of each operand.  Rows past M are
+  // The stage's 8 NPL DMA instructions, (operand, image q = 2 pi + kh, row half):
+  // wave w issues numbers NPL w .. NPL w + NPL - 1 of each operand.  Rows past M are
   // zero in Hs (mrows = hsplit_rows(M) rows), columns past Nc read column
   // Nc - 1 (finite data, discarded outputs).
-  const char *pa[3], *pb[3];
-  int lo[3];
+  const char *pa[NPL], *pb[NPL];
+  int lo[NPL];
 #pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    const int n = 3 * wave + u, q = n >> 1, half = n & 1;
+  for (int u = 0; u < NPL; ++u) {
+    const int n = NPL * wave + u, q = n >> 1, half = n & 1;
     lo[u] = (q * SP_GT + 64 * half) * 16;
     pa[u] = Hs + ((int64_t)q * mrows + abase + 64 * half + lane) * 16;
     const int xc = min(bbase + 64 * half + lane, Nc - 1);
     const int rep = xc / pz, cc = xc - rep * pz;
     pb[u] = Zs + (int64_t)rep * zrs * 8 + ((int64_t)q * pz + cc) * 16;
   }
-  const int64_t astep = (int64_t)6 * mrows * 16, bstep = (int64_t)96 * pz;
+  const int64_t astep = (int64_t)6 * mrows * 16, bstep = (int64_t)96 * pz;   // (the layouts' k-stage, three planes)
   auto issue = [&](int s) {
-    char *la = lds + (s % NBUF) * SP_STAGE, *lb = la + 6 * SP_IMG;
+    char *la = lds + (s % NBUF) * SP_STAGE, *lb = la + OPB;
 #pragma unroll
-    for (int u = 0; u < 3; ++u) {
+    for (int u = 0; u < NPL; ++u) {
       __builtin_amdgcn_global_load_lds((gbl_void_t *)pa[u], (lds_void_t *)(la + lo[u]), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((gbl_void_t *)pb[u], (lds_void_t *)(lb + lo[u]), 16, 0, 0);
       pa[u] += astep; pb[u] += bstep;
@@ -458,29 +470,32 @@ __global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__r
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     fa[t] = (hh * SP_GT + wr * 64 + 32 * t + r32) * 16;
-    fb[t] = 6 * SP_IMG + (hh * SP_GT + wc * 64 + 32 * t + r32) * 16;
+    fb[t] = OPB + (hh * SP_GT + wc * 64 + 32 * t + r32) * 16;
   }
   for (int s = 0; s < NBUF - 1 && s < nst; ++s) issue(s);
   for (int s = 0; s < nst; ++s) {
-    split_ring_wait<NBUF>(s, nst);
+    split_ring_wait<NBUF, 2 * NPL>(s, nst);
     if (s + NBUF - 1 < nst) issue(s + NBUF - 1);
     const char *ls = lds + (s % NBUF) * SP_STAGE;
-    bf16x8 af[2][3], bf[2][3];   // [tile][plane]
+    bf16x8 af[2][NPL], bf[2][NPL];   // [tile][plane]
 #pragma unroll
-    for (int pi = 2; pi >= 0; --pi)
+    for (int pi = NPL - 1; pi >= 0; --pi)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         af[t][pi] = *reinterpret_cast<const bf16x8 *>(ls + fa[t] + 2 * pi * SP_IMG);
         bf[t][pi] = *reinterpret_cast<const bf16x8 *>(ls + fb[t] + 2 * pi * SP_IMG);
       }
-    constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};   // (H plane, Z plane), small terms first
+    // (H plane, Z plane), small terms first
+    constexpr int TA6[6] = {2, 0, 1, 1, 0, 0}, TB6[6] = {0, 2, 1, 0, 1, 0}, TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};
 #pragma unroll
-    for (int e = 0; e < 6; ++e)
+    for (int e = 0; e < TERMS; ++e) {
+      const int pa_ = TERMS == 6 ? TA6[e] : TA3[e % 3], pb_ = TERMS == 6 ? TB6[e] : TB3[e % 3];
 #pragma unroll
       for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
         for (int tj = 0; tj < 2; ++tj)
-          acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti][TA[e]], bf[tj][TB[e]], acc[ti][tj], 0, 0, 0);
+          acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti][pa_], bf[tj][pb_], acc[ti][tj], 0, 0, 0);
+    }
   }
   // accumulator register v of lane l: row 8 (v >> 2) + 4 (l >> 5) + (v & 3), column l & 31
 #pragma unroll
@@ -513,11 +528,13 @@ __global__ __launch_bounds__(256, 2) void gemmh_zrm_split_kernel(const char *__r
     }
   }
 }
+// the three-term instance the library launches: ring depth and workgroups per CU
+constexpr int kSplit3Nbuf = 3, kSplit3Wgs = 3;
 
 // Hs (hsplit_bytes(M), launch_fact_hsplit) times the split Z of nb = Nc / pz replicates (dfm_internal.h: Zs; zrs =
 // round_up(M, 16) pz, the fp64 Z's replicate stride): one checked launcher for both epilogues of
 // gemmh_zrm_split_kernel (ldc and scale are the fp64 rows' alone) ...
-template <bool ROWS64, class CT>
+template <bool ROWS64, int TERMS, int NBUF, int WGS, class CT>
 static hipError_t launch_split(const void *Hs, const void *Zs, int pz, int64_t zrs, CT *C, int64_t ldc, double scale,
                                int M, int Nc, int K, hipStream_t st) {
   const int64_t kpad = (K + SP_KS - 1) / SP_KS * SP_KS;
@@ -526,21 +543,23 @@ static hipError_t launch_split(const void *Hs, const void *Zs, int pz, int64_t z
     return hipErrorInvalidValue;
   const int nrb = (M + SP_GT - 1) / SP_GT, ncb = (Nc + SP_GT - 1) / SP_GT;
   const int ncb8 = (ncb + 7) / 8 * 8;
-  hipLaunchKernelGGL(gemmh_zrm_split_kernel<ROWS64>, dim3(nrb * ncb8), dim3(256), 0, st, (const char *)Hs,
-                     hsplit_rows(M), (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb, ldc, scale);
+  hipLaunchKernelGGL((gemmh_zrm_split_kernel<ROWS64, TERMS, NBUF, WGS>), dim3(nrb * ncb8), dim3(256), 0, st,
+                     (const char *)Hs, hsplit_rows(M), (const char *)Zs, pz, zrs, C, M, Nc, K, nrb, ncb, ldc, scale);
   return hipGetLastError();
 }
-// ... -> C32 in launch_gemm_zrm_f32's layout
+// ... -> C32 in launch_gemm_zrm_f32's layout, from terms = 6 plane pairs or from the 3 of planes h and m alone
 hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
-                                 hipStream_t st) {
-  return launch_split<false>(Hs, Zs, pz, zrs, C, 0, 1.0, M, Nc, K, st);
+                                 int terms, hipStream_t st) {
+  if (terms == 6) return launch_split<false, 6, 3, 2>(Hs, Zs, pz, zrs, C, 0, 1.0, M, Nc, K, st);
+  if (terms == 3) return launch_split<false, 3, kSplit3Nbuf, kSplit3Wgs>(Hs, Zs, pz, zrs, C, 0, 1.0, M, Nc, K, st);
+  return hipErrorInvalidValue;
 }
 // ... or delivered as fp64 rows, C (M x Nc, row stride ldc >= Nc) = scale C32 in launch_gemm_zrm's column-interleaved
 // layout: the last product of a warm filter (scale = hmax), whose rows the last Horner step gathers as it gathers an
 // fp64 product's.  Nothing outside rows < M and columns < Nc is written.
 hipError_t launch_gemm_zrm_split_rows(const void *Hs, const void *Zs, int pz, int64_t zrs, double *C, int64_t ldc,
                                       double scale, int M, int Nc, int K, hipStream_t st) {
-  return launch_split<true>(Hs, Zs, pz, zrs, C, ldc, scale, M, Nc, K, st);
+  return launch_split<true, 6, 3, 2>(Hs, Zs, pz, zrs, C, ldc, scale, M, Nc, K, st);
 }
 
 // ---------------------------------------------------------------------------

@@ -45,6 +45,7 @@ struct dfm_ctx {
   int64_t eig_batches = 0, eig_iters = 0, eig_iters_max = 0, rep_iters = 0, gemm_products = 0;
   int64_t gemm_products_f32 = 0;   // of the factored solver's replicate-products, those run in fp32 (host-counted)
   int64_t gemm_products_split_last = 0;   // the warm filter's last products run as six bf16 terms (0 or nb per solve)
+  int64_t gemm_products_split3 = 0;       // of gemm_products_f32, those run as three bf16 terms ((d0 - 2) nb per solve)
   // factored runs accumulate {replicate-iterations, GEMM replicate-products}
   // here on the device (no host sync after the eigen loop); read on query
   long long *cnt_dev = nullptr;

@@ -95,6 +95,12 @@ DFM_DEV void bf16_split3_pair(double x0, double x1, uint32_t &h, uint32_t &m, ui
   const double s0 = r0 - (double)__uint_as_float(m << 16), s1 = r1 - (double)__uint_as_float(m & 0xFFFF0000u);
   l = bf16_pack2((float)s0, (float)s1);
 }
+// ... and planes h and m alone: the same bits
+DFM_DEV void bf16_split2_pair(double x0, double x1, uint32_t &h, uint32_t &m) {
+  h = bf16_pack2((float)x0, (float)x1);
+  const double r0 = x0 - (double)__uint_as_float(h << 16), r1 = x1 - (double)__uint_as_float(h & 0xFFFF0000u);
+  m = bf16_pack2((float)r0, (float)r1);
+}
 // eight consecutive doubles -> the three planes' 16-B pieces
 DFM_DEV void bf16_split3_piece(const double *x, uint4 &ph, uint4 &pm, uint4 &pl) {
   bf16_split3_pair(x[0], x[1], ph.x, pm.x, pl.x);
@@ -110,16 +116,25 @@ DFM_DEV void bf16_split3_piece(const double *x, uint4 &ph, uint4 &pm, uint4 &pl)
 // dst must be wave-uniform (the chunk number through readfirstlane): the
 // three stores then take a scalar base and one 32-bit lane offset, and no
 // 64-bit per-lane address is carried through the caller's tile loop.
-template <bool ONE>
+// PLANES = 2, for a three-term product: plane l is neither formed nor stored —
+// its third of the chunk keeps whatever it held and the product does not
+// address it.
+template <bool ONE, int PLANES>
 DFM_DEV void zsplit_store_chunk(const double *st, int pz, int lane, char *__restrict__ dst) {
+  static_assert(PLANES == 2 || PLANES == 3, "planes h, m and perhaps l");
   auto part = [&](int e) {   // e = 4 c + 2 kh + half: doubles 4 e .. 4 e + 3
     uint2 h, m, l;
-    bf16_split3_pair(st[4 * e], st[4 * e + 1], h.x, m.x, l.x);
-    bf16_split3_pair(st[4 * e + 2], st[4 * e + 3], h.y, m.y, l.y);
+    if constexpr (PLANES == 3) {
+      bf16_split3_pair(st[4 * e], st[4 * e + 1], h.x, m.x, l.x);
+      bf16_split3_pair(st[4 * e + 2], st[4 * e + 3], h.y, m.y, l.y);
+    } else {
+      bf16_split2_pair(st[4 * e], st[4 * e + 1], h.x, m.x);
+      bf16_split2_pair(st[4 * e + 2], st[4 * e + 3], h.y, m.y);
+    }
     const uint32_t off = 8u * (uint32_t)(2 * (((e >> 1) & 1) * pz + (e >> 2)) + (e & 1));
     *reinterpret_cast<uint2 *>(dst + off) = h;
     *reinterpret_cast<uint2 *>(dst + 32 * pz + off) = m;
-    *reinterpret_cast<uint2 *>(dst + 64 * pz + off) = l;
+    if constexpr (PLANES == 3) *reinterpret_cast<uint2 *>(dst + 64 * pz + off) = l;
   };
   if constexpr (ONE) {
     // (the lane number is re-read here so that the addresses below are formed at the call, from one register: as
@@ -131,10 +146,17 @@ DFM_DEV void zsplit_store_chunk(const double *st, int pz, int lane, char *__rest
     for (int e = lane; e < 4 * pz; e += 64) part(e);
   }
 }
+// ... with the plane count (3 or 2: FilterPlan::z0_planes / mid_planes) a wave-uniform run-time value
+template <bool ONE>
+DFM_DEV void zsplit_store_chunk(const double *st, int pz, int lane, char *__restrict__ dst, int planes) {
+  if (planes == 3) zsplit_store_chunk<ONE, 3>(st, pz, lane, dst);
+  else zsplit_store_chunk<ONE, 2>(st, pz, lane, dst);
+}
 inline int hsplit_rows(int T) { return (T + 127) & ~127; }
 inline size_t hsplit_bytes(int T) { return (size_t)((T + 15) / 16) * 6 * hsplit_rows(T) * 16; }
+// (terms = 6, or 3: the pairs of planes h and m alone, which read no plane l of either operand)
 hipError_t launch_gemm_zrm_split(const void *Hs, const void *Zs, int pz, int64_t zrs, float *C, int M, int Nc, int K,
-                                 hipStream_t st);
+                                 int terms, hipStream_t st);
 // ... and C (M x Nc fp64, row stride ldc, launch_gemm_zrm's layout) = scale C32 from the same kernel's second epilogue
 hipError_t launch_gemm_zrm_split_rows(const void *Hs, const void *Zs, int pz, int64_t zrs, double *C, int64_t ldc,
                                       double scale, int M, int Nc, int K, hipStream_t st);
@@ -156,6 +178,7 @@ extern thread_local int64_t g_last_rep_iters;
 extern thread_local int64_t g_last_gemm_products;
 extern thread_local int64_t g_last_gemm_products_f32;   // of those, the fp32 ones (factored solver, host-counted)
 extern thread_local int64_t g_last_gemm_products_split_last;   // ... and the warm filter's last products run split
+extern thread_local int64_t g_last_gemm_products_split3;       // ... and the fp32 ones run as three bf16 terms
 int eig_block_p(int m, int k, int req);
 int fact_block_p(int m, int k, int req);
 // What both solvers take besides the matrix.  Callers fill the members by name.

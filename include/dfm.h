@@ -122,6 +122,11 @@ int dfm_ctx_gemm_products_f32(dfm_ctx *ctx, int64_t *products);
  * (nb per such solve; 0 under the strict rule, with DFM_FACT_F32=0,
  * DFM_FACT_SPLIT=0 or DFM_FACT_SPLIT_LAST=0).  Not part of the fp32 count. */
 int dfm_ctx_gemm_products_split_last(dfm_ctx *ctx, int64_t *products);
+/* Of the gemm_products_f32 products, those run as three bf16 terms on two
+ * planes: the split products two or more short of the filter's last
+ * ((d0 - 2) nb per such solve; 0 with DFM_FACT_SPLIT3=0, DFM_FACT_SPLIT=0 or
+ * DFM_FACT_F32=0, or under the strict rule). */
+int dfm_ctx_gemm_products_split3(dfm_ctx *ctx, int64_t *products);
 int dfm_ctx_rep_iters(dfm_ctx *ctx, int64_t *rep_iters);
 const char *dfm_kernel_class_name(int cls);
 

@@ -24,7 +24,13 @@ step 0 apply the idiosyncratic part E* E*' of G* = (G* - E* E*') + E* E*' as
 float32(E* E*') @ float32(S) (sgemm, fp32 accumulation) — the GPU's fp32
 middle products, which round H and Z and keep the factor part in fp64;
 NOISE=x: Gaussian noise of x 6e-8 ||column|| / sqrt(T) per entry added to that
-part (the margin over fp32 rounding)."""
+part (the margin over fp32 rounding); TERMS=t1,t2,... (with F32): how step 0's
+product 1, 2, ... applies that part instead of sgemm — 6, 3 or 1: as that many
+bf16 plane pairs of (E* E*' / hmax) and S, the GPU's split products
+(tests/test_bf16_split_model.py: split3 and split_matmul's fp32 accumulation
+per 16-deep stage; 3 = (m,h) (h,m) (h,h), 1 = (h,h)); M >= 8: both operands
+rounded to M significand bits, the product in fp64.  Products past the list
+stay sgemm.  NOISE applies on top as before."""
 import os
 import sys
 
@@ -32,7 +38,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dynamicfactormodels.jl_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import host  # noqa: E402
+from test_bf16_split_model import SIX, split_matmul  # noqa: E402
 
 T, N, R = 500, 2000, 8
 P = int(os.environ.get("P", "16"))
@@ -40,6 +48,8 @@ JACOBI = int(os.environ.get("JACOBI", "0"))
 JACOBI_FIRST = int(os.environ.get("JACOBI_FIRST", str(JACOBI)))   # f / g: sweeps of the first Rayleigh-Ritz step
 F32 = int(os.environ.get("F32", "0"))          # f / g: step 0's first F32 products with the E* E*' part in float32
 NOISE = float(os.environ.get("NOISE", "0"))    # ... plus this many times fp32's rounding noise
+TERMS = [int(v) for v in os.environ.get("TERMS", "").split(",") if v]   # ... per product: plane pairs, or bits
+PAIRS = {6: SIX, 3: ((1, 0), (0, 1), (0, 0)), 1: ((0, 0),)}
 
 
 def shifted_cheb(d):
@@ -94,9 +104,25 @@ def colcond(Q):
     return np.linalg.cond(Q / np.linalg.norm(Q, axis=0))
 
 
-def lowp_product(G, Hs, S, nrng):
-    """G S with the part Hs S (Hs = E* E*') in float32: rounded operands, fp32 accumulation, optional noise."""
-    W = (Hs.astype(np.float32) @ S.astype(np.float32)).astype(np.float64)
+def round_bits(x, m):
+    """x rounded to m significand bits (round to nearest even)."""
+    f, e = np.frexp(x)
+    return np.ldexp(np.rint(np.ldexp(f, m)), e - m)
+
+
+def lowp_product(G, Hs, S, nrng, sp=0):
+    """G S with the part Hs S (Hs = E* E*') in float32: rounded operands, fp32 accumulation, optional noise.
+    sp (1-based) picks the product's entry of TERMS, if it has one."""
+    t = TERMS[sp - 1] if 0 < sp <= len(TERMS) else 0
+    if t in PAIRS:
+        hmax = Hs.diagonal().max()
+        W = hmax * split_matmul(Hs / hmax, S, PAIRS[t])
+    elif t >= 8:
+        W = round_bits(Hs, t) @ round_bits(S, t)
+    elif t:
+        raise ValueError(f"TERMS: {t} (6, 3, 1 plane pairs or >= 8 bits)")
+    else:
+        W = (Hs.astype(np.float32) @ S.astype(np.float32)).astype(np.float64)
     if NOISE > 0.0:
         W = W + nrng.standard_normal(W.shape) * (NOISE * 6e-8 * np.linalg.norm(W, axis=0) / np.sqrt(W.shape[0]))
     return (G - Hs) @ S + W
@@ -116,7 +142,7 @@ def solve(G, Q0, degs, k=R, tol=1e-12, maxit=30, beta=0.0, strict=False, bfix=0.
         S = a[degs[0]] * Q0
         for i in range(degs[0] - 1, -1, -1):
             low = Hs is not None and prods < F32
-            S = (lowp_product(G, Hs, S, nrng) if low else G @ S) / bfix + a[i] * Q0
+            S = (lowp_product(G, Hs, S, nrng, prods + 1) if low else G @ S) / bfix + a[i] * Q0
             prods += 1
         Q = S
         it0 = 1

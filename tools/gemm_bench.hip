@@ -141,7 +141,9 @@ __global__ void fillbf(uint16_t *p, size_t n, float s) {
 // layout, every element set (pad rows included: timing only).  Round 15:
 // gemmh_zrm_split_kernel (the same products as six bf16 terms) beside them, on
 // random planes.  Round 19: the split kernel's fp64 epilogue (zrm_split64: the same
-// product stored as fp64 rows of the column-interleaved HZ, launch_gemm_zrm_split_rows).
+// product stored as fp64 rows of the column-interleaved HZ, launch_gemm_zrm_split_rows).  Round 21: the three-term
+// form on planes h and m (16 KB stages), as a 3-deep ring at 3 workgroups per CU (split3_r3w3) and a 4-deep ring at 2
+// (split3_r4w2); the library launches the one named by kSplit3Nbuf / kSplit3Wgs.
 static void bench_f32() {
   const int T = 500, pz = 12;
   const int64_t lda = (T + 15) / 16 * 16, zrs = lda * pz;
@@ -160,10 +162,12 @@ static void bench_f32() {
     fill<<<((size_t)T * lda + 255) / 256, 256>>>(A64, (size_t)T * lda, 1.0, lda, T);
     fill<<<((size_t)nb * zrs + 255) / 256, 256>>>(Z64, (size_t)nb * zrs, 2.0, 1, 1);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int v = 0; v < 4; ++v) {
+    for (int v = 0; v < 6; ++v) {
       auto run = [&]() {
-        if (v == 3) launch_gemm_zrm_split_rows(Hs, Zs, pz, zrs, C64, Nc, 3.0, T, Nc, T, 0);
-        else if (v == 2) launch_gemm_zrm_split(Hs, Zs, pz, zrs, C, T, Nc, T, 0);
+        if (v == 5) launch_split<false, 3, 4, 2>(Hs, Zs, pz, zrs, C, 0, 1.0, T, Nc, T, 0);
+        else if (v == 4) launch_split<false, 3, 3, 3>(Hs, Zs, pz, zrs, C, 0, 1.0, T, Nc, T, 0);
+        else if (v == 3) launch_gemm_zrm_split_rows(Hs, Zs, pz, zrs, C64, Nc, 3.0, T, Nc, T, 0);
+        else if (v == 2) launch_gemm_zrm_split(Hs, Zs, pz, zrs, C, T, Nc, T, 6, 0);
         else if (v == 0) launch_gemm_zrm_f32(A, lda, Z, pz, zrs, C, T, Nc, T, 0);
         else launch_gemm_zrm(A64, lda, Z64, pz, zrs, C64, Nc, T, Nc, T, 0, nullptr, nullptr, nullptr);
       };
@@ -174,9 +178,15 @@ static void bench_f32() {
       hipEventRecord(e1); hipEventSynchronize(e1);
       float ms; hipEventElapsedTime(&ms, e0, e1);
       const double t = ms / reps * 1e-3, fl = 2.0 * T * (double)Nc * T, peak = v == 1 ? 78.6 : 157.3;
-      // (zrm_split: the fp32-equivalent rate, one product's flops; it issues six times as many on the bf16 path)
+      // (zrm_split, split3: the fp32-equivalent rate, one product's flops; they issue six and three times as many on the bf16 path)
       printf("%s M=K=%d pz=%d nb=%5d : %8.3f ms  %6.2f TF/s (%.1f%% of %.1f)  [%s]\n",
-             v == 0 ? "zrm_f32    " : v == 1 ? "zrm_f64    " : v == 2 ? "zrm_split  " : "zrm_split64", T,
+             v == 0   ? "zrm_f32    "
+             : v == 1 ? "zrm_f64    "
+             : v == 2 ? "zrm_split  "
+             : v == 3 ? "zrm_split64"
+             : v == 4 ? "split3_r3w3"
+                      : "split3_r4w2",
+             T,
              pz, nb, t * 1e3, fl / t / 1e12, fl / t / 1e12 / peak * 100, peak, hipGetErrorString(hipGetLastError()));
     }
     hipFree(Hs); hipFree(Zs);
