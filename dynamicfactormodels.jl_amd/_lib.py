@@ -73,6 +73,10 @@ class dfm_ss_mf(C.Structure):
     _fields_ = [("n_w", C.c_int32), ("w", c_double_p), ("low", c_uint8_p)]
 
 
+class dfm_ss_blocks(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("block_r", C.POINTER(C.c_int32)), ("member", c_uint8_p)]
+
+
 class dfm_ss_fit_out(C.Structure):
     _fields_ = [(n, c_double_p) for n in
                 ("mu", "sd", "lambda_", "sigma2", "A", "Q", "P0", "filtered", "smoothed", "smoothed_cov", "loglik",
@@ -202,6 +206,13 @@ SIGNATURES = [
                                 C.c_int, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_mf), C.c_int,
                                 C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out), c_double_p, c_double_p,
                                 C.POINTER(dfm_ss_em_info), c_double_p]),
+    ("dfm_ss_em_blocks", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                   C.POINTER(dfm_ss_params), C.c_int64, C.POINTER(dfm_ss_mf), C.POINTER(dfm_ss_blocks),
+                                   C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_em_out), C.POINTER(dfm_ss_em_info)]),
+    ("dfm_ss_fit_blocks", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
+                                    C.c_int, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_mf), C.POINTER(dfm_ss_blocks),
+                                    C.c_int, C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out), c_double_p, c_double_p,
+                                    C.POINTER(dfm_ss_em_info), c_double_p]),
     ("dfm_ss_simulate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_ss_params),
                                   C.POINTER(dfm_ss_sim_spec), C.c_int64, C.c_void_p, C.c_int64, c_double_p,
                                   c_double_p, c_double_p, c_double_p]),

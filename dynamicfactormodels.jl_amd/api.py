@@ -1139,6 +1139,7 @@ class StateSpaceResult:
     ml_converged: bool = False
     ml_criterion: float = float("nan")
     smoothed_agg: Optional[np.ndarray] = None
+    factor_blocks: Optional[tuple] = None
 
 
 @dataclass
@@ -1151,7 +1152,8 @@ class StateSpaceEMResult:
     ``converged`` and the last ``criterion``.  A batch of M panels gives each
     with a leading axis M.  With low-frequency series ``a0`` and ``P0`` are
     those of the padded state and ``smoothed_agg`` (T + h, r) is the smoothed
-    aggregate they load on (None otherwise)."""
+    aggregate they load on (None otherwise).  ``factor_blocks`` is the tuple
+    of block sizes the call was given (None: no blocks)."""
     loadings: np.ndarray
     sigma2: np.ndarray
     A: np.ndarray
@@ -1168,6 +1170,7 @@ class StateSpaceEMResult:
     converged: Union[bool, np.ndarray]
     criterion: Union[float, np.ndarray]
     smoothed_agg: Optional[np.ndarray] = None
+    factor_blocks: Optional[tuple] = None
 
 
 def _ss_check(rc: int, what: str):
@@ -1234,6 +1237,42 @@ def _ss_mixed(low_freq, agg_weights, N):
     return low, w
 
 
+def _ss_blocks(factor_blocks, block_members, N, r=None):
+    """The checked (sizes, membership) of a call with factor blocks; None when
+    ``factor_blocks`` is None.  Sizes: int32, each >= 1, summing to ``r`` when
+    that is given; membership: N x n_b uint8 column-major, all ones for
+    ``block_members=None`` (every series in every block: only the VAR is
+    restricted)."""
+    if factor_blocks is None:
+        if block_members is not None:
+            raise ValueError("block_members needs factor_blocks, the sizes of the blocks")
+        return None
+    raw = np.asarray(factor_blocks)
+    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
+        raise ValueError("factor_blocks must be a sequence of integer block sizes")
+    sizes = np.ascontiguousarray(raw, dtype=np.int32)
+    if len(sizes) > 16 or (sizes < 1).any():
+        raise DFMError(-2, "factor_blocks: 1..16 blocks, each of size >= 1")
+    if r is not None and int(sizes.sum()) != int(r):
+        raise DFMError(-2, f"factor_blocks sum to {int(sizes.sum())}, the model has {int(r)} factors")
+    if block_members is None:
+        mem = np.ones((N, len(sizes)), dtype=np.uint8, order="F")
+    else:
+        bm = np.asarray(block_members)
+        if bm.dtype.kind not in "biu":
+            raise ValueError("block_members must be a boolean or integer N x n_blocks matrix")
+        if bm.shape != (N, len(sizes)):
+            raise DFMError(-2, f"block_members must be N x n_blocks = {(N, len(sizes))}, not {bm.shape}")
+        mem = np.asfortranarray((bm != 0).astype(np.uint8))
+    return sizes, mem
+
+
+def _ss_blocks_struct(blocks):
+    """The ``dfm_ss_blocks`` of ``_ss_blocks``'s (sizes, membership), which the caller keeps alive."""
+    sizes, mem = blocks
+    return _lib.dfm_ss_blocks(len(sizes), sizes.ctypes.data_as(C.POINTER(C.c_int32)), mem.ctypes.data_as(_lib.c_uint8_p))
+
+
 def _dptr(a):
     """The ``double *`` of a float64 array (None stays None: not given, or not wanted)."""
     return None if a is None else a.ctypes.data_as(_lib.c_double_p)
@@ -1282,7 +1321,9 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     ``agg_weights`` (a quarterly series among monthly ones has NaN in two
     months of three).  The state then keeps max(p, len(w)) lags: ``a0`` and
     ``P0`` are of that size, and the result carries ``smoothed_agg``.  A mask
-    without a marked series is the plain call, bit for bit."""
+    without a marked series is the plain call, bit for bit.  Parameters estimated with factor
+    blocks (``ss_em(factor_blocks=...)``) need nothing more here: Lambda, A and
+    Q are taken as given, zeros included."""
     mixed = _ss_mixed(low_freq, agg_weights, np.shape(loadings)[0])   # before anything touches the device
     ctx = ctx or default_context()
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
@@ -1342,7 +1383,9 @@ def simulation_smoother(x, loadings, sigma2, A, Q, *, draws: int, z=None, rng: O
     omitted ``rng`` draws it on the host.  ``z`` is not scanned: a NaN in draw
     d's row makes draw d NaN and touches no other draw.  ``pass_draws`` caps
     the draws per device pass (default: the library's workspace rule); the
-    result does not depend on it."""
+    result does not depend on it.  Parameters estimated with factor
+    blocks (``ss_em(factor_blocks=...)``) need nothing more here: Lambda, A and
+    Q are taken as given, zeros included."""
     ctx = ctx or default_context()
     single, (buf, _, T, N, ldx, _, dev) = _ss_panels(x)
     if not single:
@@ -1433,7 +1476,9 @@ def nowcast_news(x_old, x_new, loadings, sigma2, A, Q, *, targets, a0=None, P0=N
     returned for the rows from t_lo on.  ``releases``: a caller's own (J, 2)
     list of (t, i), which the library checks against the two vintages (it must
     be exactly the releases, sorted).  ``pass_releases`` caps the releases per
-    device pass; the result does not depend on it."""
+    device pass; the result does not depend on it.  Parameters estimated with factor
+    blocks (``ss_em(factor_blocks=...)``) need nothing more here: Lambda, A and
+    Q are taken as given, zeros included."""
     xo, xn = _f64(x_old, 2), _f64(x_new, 2)
     if xo.shape != xn.shape:
         raise ValueError("x_old and x_new must be two vintages of one (T, N) panel")
@@ -1505,8 +1550,8 @@ def _ss_start_axis(v, base_ndim, name):
 
 
 def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max_iter: int = 100,
-          update_init: bool = True, horizon: int = 0, low_freq=None, agg_weights=None,
-          ctx: Optional[Context] = None) -> StateSpaceEMResult:
+          update_init: bool = True, horizon: int = 0, low_freq=None, agg_weights=None, factor_blocks=None,
+          block_members=None, ctx: Optional[Context] = None) -> StateSpaceEMResult:
     """Quasi-maximum likelihood of the state-space factor model by EM
     (``dfm_ss_em``; the estimator is stated in ``include/dfm.h``), iterated on
     the device over one panel or M panels of one shape, each with its own
@@ -1521,8 +1566,17 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     Mixed frequency (``dfm_ss_em_mf``): ``low_freq`` and ``agg_weights`` as
     ``kalman_smoother`` takes them; a marked series' loading is then estimated
     against the aggregate of the factors.  ``a0`` and ``P0``, given and
-    returned, are those of the padded state; ``A`` stays r x rp."""
+    returned, are those of the padded state; ``A`` stays r x rp.
+
+    Factor blocks (``dfm_ss_em_blocks``): ``factor_blocks=(r_1, ...)`` splits
+    the r factors into contiguous blocks, ``block_members`` (N x n_blocks,
+    non-zero: the series loads on the block; None: every series on every
+    block) says who loads on which.  Loadings outside a series' blocks stay
+    exactly zero, every A_k and Q stay block-diagonal, and the start must hold
+    zeros there.  One block that every series is a member of is the
+    unrestricted call bit for bit."""
     mixed = _ss_mixed(low_freq, agg_weights, np.shape(loadings)[-2])   # before anything touches the device
+    blocks = _ss_blocks(factor_blocks, block_members, np.shape(loadings)[-2], np.shape(loadings)[-1])
     ctx = ctx or default_context()
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
     given = [("loadings", loadings, 2), ("sigma2", sigma2, 1), ("A", A, 2), ("Q", Q, 2)]
@@ -1564,7 +1618,13 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
                              nobs.ctypes.data_as(_lib.c_int64_p), _dptr(path), _dptr(agg))
     info = (_lib.dfm_ss_em_info * max(M, 1))()
     xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
-    if mixed is None:
+    if blocks is not None:
+        mf = None if mixed is None else _ss_mf_struct(mixed)
+        bs = _ss_blocks_struct(blocks)
+        ctx.check(ctx.lib.dfm_ss_em_blocks(ctx.h, xp, M, T, N, ldx, stride, starts, n_start,
+                                           None if mf is None else C.byref(mf), C.byref(bs), C.byref(spec),
+                                           C.byref(out), info))
+    elif mixed is None:
         ctx.check(ctx.lib.dfm_ss_em(ctx.h, xp, M, T, N, ldx, stride, starts, n_start, C.byref(spec), C.byref(out),
                                     info))
     else:
@@ -1580,8 +1640,10 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     res = StateSpaceEMResult(tr(Lo), so, tr(Ao), tr(Qo), a0o, tr(P0o), filt, sm, cov, ll, nobs, path, its, conv, crit,
                              agg)
     if single:
-        return StateSpaceEMResult(*(None if getattr(res, f.name) is None else getattr(res, f.name)[0]
-                                    for f in fields(res)))
+        res = StateSpaceEMResult(*(None if getattr(res, f.name) is None else getattr(res, f.name)[0]
+                                   for f in fields(res)))
+    if blocks is not None:
+        res.factor_blocks = tuple(int(v) for v in blocks[0])
     return res
 
 
@@ -1612,7 +1674,7 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
                           horizon: int = 0, *, kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50,
                           standardize: bool = True, method: str = "two-step", ml_tol: float = 1e-4,
                           ml_max_iter: int = 100, update_init: bool = True, low_freq=None, agg_weights=None,
-                          ctx: Optional[Context] = None) -> StateSpaceResult:
+                          factor_blocks=None, block_members=None, ctx: Optional[Context] = None) -> StateSpaceResult:
     """The two-step estimator of Doz, Giannone & Reichlin (2011) of a panel
     with missing entries (``dfm_ss_fit``): ``em_factors``, a VAR(``lags``) on
     its factors, then the Kalman smoother over the observed entries with
@@ -1628,9 +1690,20 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     are re-estimated on the aggregate of the EM's factors before the smoother
     (or the ML iteration) runs at the padded state; ``P0`` and ``a0`` are of
     that size, the fill and the forecast of a marked column come from the
-    smoothed aggregate, and the result carries ``smoothed_agg``."""
+    smoothed aggregate, and the result carries ``smoothed_agg``.
+
+    Factor blocks (``dfm_ss_fit_blocks``): ``factor_blocks`` and
+    ``block_members`` as ``ss_em`` takes them; ``number_of_factors`` is None
+    or their sum.  After ``em_factors`` at that many factors, every block in
+    order takes the principal components of its members' columns of what the
+    blocks before it left unexplained; those are the start's factors
+    (``em.factors``) and loadings, each block gets its own VAR, and the ML
+    iteration keeps the restrictions."""
     if method not in ("two-step", "ml"):
         raise ValueError('method must be "two-step" or "ml"')
+    blocks = _ss_blocks(factor_blocks, block_members, np.shape(x)[-1], number_of_factors)
+    if blocks is not None:
+        number_of_factors = int(blocks[0].sum())
     mixed = None if low_freq is None and agg_weights is None else \
         _ss_mixed(low_freq, agg_weights, np.shape(x)[-1])   # before anything touches the device
     ctx = ctx or default_context()
@@ -1652,11 +1725,23 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
                                                    ev)))
     info = _lib.dfm_em_info()
     ml = {}
-    if method == "ml" or mixed is not None:
+    if blocks is not None:
+        ml["factor_blocks"] = tuple(int(v) for v in blocks[0])
+    if method == "ml" or mixed is not None or blocks is not None:
         mi = int(ml_max_iter) if int(ml_max_iter) >= 0 else 100
         a0, path, minfo = np.zeros(sc), np.full(mi + 1, np.nan), _lib.dfm_ss_em_info()
         mspec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, 0, float(ml_tol))
-        if mixed is None:
+        if blocks is not None:
+            agg = np.zeros((T + h) * cap)
+            mf = None if mixed is None else _ss_mf_struct(mixed)
+            bs = _ss_blocks_struct(blocks)
+            ctx.check(ctx.lib.dfm_ss_fit_blocks(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec),
+                                                None if mf is None else C.byref(mf), C.byref(bs), int(method == "ml"),
+                                                C.byref(info), C.byref(out), _dptr(a0), _dptr(path), C.byref(minfo),
+                                                _dptr(agg)))
+            if any_low:
+                ml["smoothed_agg"] = agg[:(T + h) * int(info.r)].reshape(T + h, int(info.r)).copy()
+        elif mixed is None:
             ctx.check(ctx.lib.dfm_ss_fit_ml(ctx.h, xp, T, N, ldx, C.byref(spec), p, C.byref(mspec), C.byref(info),
                                             C.byref(out), _dptr(a0), _dptr(path), C.byref(minfo)))
         else:

@@ -12,6 +12,7 @@ struct dfm_ss_mf;   // include/dfm.h
 struct dfm_ss_params;
 struct dfm_ss_em_out;
 struct dfm_ss_em_info;
+struct dfm_ss_blocks;
 
 namespace dfm {
 
@@ -463,9 +464,24 @@ hipError_t launch_ss_transpose(const double *in, int64_t rows, int64_t n, double
 // mf: the mixed-frequency model (checked): the starts are then the padded
 // state's (p = max(p_var, n_w), A = [A 0]), p_var the VAR's own lag count
 // (out.A is r x r p_var); null: the plain model.
+// blocks: the factor blocks (checked, the starts too: dfm_ss_em_blocks); null:
+// no restriction.
+struct SsBlockOff {   // the kernels' view: block g owns the factors off[g] .. off[g + 1] - 1
+  int nb;
+  uint8_t off[17];
+};
+struct SsBlocks {
+  SsBlockOff o;
+  const uint16_t *free;   // host, N: bit j set when the series loads on factor j
+};
 int ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx,
                int64_t stride, bool dev, const dfm_ss_params *starts, int64_t n_start, int max_iter, double tol,
                bool update_init, int h, const dfm_ss_em_out &out, dfm_ss_em_info *info, const dfm_ss_mf *mf = nullptr,
-               int p_var = 0);
+               int p_var = 0, const SsBlocks *blocks = nullptr);
+// The checked blocks of the entry point `who` (r = the sum the sizes must have):
+// 0 with *trivial set when there is no restriction, else with bl and the mask
+// it points to filled; -2 / -7 with the message otherwise.
+int ss_blocks_args(dfm_ctx *ctx, const char *who, const dfm_ss_blocks *blocks, int64_t N, int r, bool *trivial,
+                   SsBlocks *bl, std::vector<uint16_t> &free);
 
 }  // namespace dfm

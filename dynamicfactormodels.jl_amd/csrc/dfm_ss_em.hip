@@ -1,5 +1,5 @@
 // dfm_ss_em.hip — the quasi-ML EM of the state-space factor model (dfm_ss_em,
-// dfm_ss_em_mf; stated in include/dfm.h).  Every panel of the batch has its own
+// dfm_ss_em_mf, dfm_ss_em_blocks; stated in include/dfm.h).  Every panel of the batch has its own
 // parameter block and an `active` flag; an iteration is the E-step (ss_estep of
 // dfm_ss.hip, which also leaves S11, S10, S00 and the M-step's operand rows), then
 //   ss_mstep_kernel      the transpose of the collapse: [mask | zero-filled
@@ -12,6 +12,8 @@
 // of a device-resident panel without an observed entry.
 // Mixed frequency: the <true> instantiations read and write a series' own
 // class's columns and regress the VAR on its own lags.
+// Factor blocks (dfm_ss_em_blocks): the <., true> instantiations of the last two
+// keep Lambda's restricted entries at zero and A, Q block-diagonal.
 // No kernel uses an atomic, and the K split depends on T alone: panel b of a
 // batch is bit-identical to a call on panel b alone.
 #include "dfm_host.h"
@@ -130,11 +132,17 @@ __global__ __launch_bounds__(256) void ss_empty_column_kernel(const double *__re
 // parameters of such a series are left as they were.
 // MF: low[i] names the series' class; it reads that class's group of its row
 // and writes the collapse operands at that class's columns.
-template <bool MF>
+// R (factor blocks): bit j of free[i] says that the series loads on factor j.
+// Row and column j of S_i become e_j and g_ij zero for the others, so every
+// lane keeps the trip counts of the r x r system: the solve leaves the free
+// sub-system's solution and lambda_ij = 0 there, which is written as 0.0
+// into Lambda and the collapse operands.
+template <bool MF, bool R>
 __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__restrict__ pm, int N, int Nr, int r, int NCP,
                                                             int KS, const int *__restrict__ active, SsBlock L,
                                                             double *__restrict__ par, int *__restrict__ status,
-                                                            const uint8_t *__restrict__ low) {
+                                                            const uint8_t *__restrict__ low,
+                                                            const uint16_t *__restrict__ free) {
   __shared__ double w[(SS_RMAX * (SS_RMAX + 1) / 2 + 2 * SS_RMAX) * SS_LB];
   const int tid = threadIdx.x, i = blockIdx.x * SS_LB + tid, b = blockIdx.y;
   if (!active[b] || i >= N) return;
@@ -150,6 +158,16 @@ __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__rest
   };
   for (int c = 0; c < cn; ++c) W(c) = chunks(co + c);
   const double n = chunks(ccn), q = chunks(cq);
+  unsigned fm = 0xffffu;
+  if constexpr (R) {
+    fm = free[i];
+    for (int a = 0; a < r; ++a) {
+      const bool fa = (fm >> a) & 1;
+      if (!fa) W(nC + a) = 0.0;
+      for (int c = 0; c <= a; ++c)
+        if (!fa || !((fm >> c) & 1)) W(ss_tri(a, c)) = a == c ? 1.0 : 0.0;
+    }
+  }
   bool bad = false;
   for (int j = 0; j < r; ++j) {
     double d = W(ss_tri(j, j));
@@ -186,9 +204,10 @@ __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__rest
   double *P = par + (int64_t)b * L.stride;
   double *wm = P + L.oWm + (int64_t)i * NCP, *wv = P + L.oWv + (int64_t)i * NCP;
   for (int a = 0; a < r; ++a) {
-    const double la = W(y + a);
-    for (int c = 0; c <= a; ++c) wm[co + ss_tri(a, c)] = la * W(y + c) / v;
-    wv[co + nC + a] = la / v;
+    const bool fa = !R || ((fm >> a) & 1);
+    const double la = fa ? W(y + a) : 0.0;
+    for (int c = 0; c <= a; ++c) wm[co + ss_tri(a, c)] = (fa && (!R || ((fm >> c) & 1))) ? la * W(y + c) / v : 0.0;
+    wv[co + nC + a] = fa ? la / v : 0.0;
     P[L.oL + (int64_t)a * N + i] = la;
   }
   wm[ccn + 2] = log(v);
@@ -202,12 +221,16 @@ __global__ __launch_bounds__(SS_LB) void ss_loadings_kernel(const double *__rest
 // (1 an S_i, 2 a sigma^2_i, 4 an empty column, 8 S00) and the first such column.
 // MF: the regression runs on the leading rp block of S00 and S10 (the VAR's
 // own lags); the companion matrix's columns beyond stay zero.
-template <bool MF>
+// R (factor blocks, bo): one block after the other, rows G = its factors and
+// columns c = its factors at every lag of the VAR: S00[c, c] and S10[G, c]
+// gathered into the LDS matrices, A[G, c] = S10[G, c] S00[c, c]^-1 and Q[G, G]
+// as above; the rest of A's rows and of Q is written as zero.
+template <bool MF, bool R>
 __global__ __launch_bounds__(256) void ss_transition_kernel(const double *__restrict__ mom, int T, int N, int r, int s, int rp,
                                                             int update_init, const int *__restrict__ active, SsBlock L,
                                                             double *__restrict__ par, const int *__restrict__ status,
-                                                            int *__restrict__ mflag, int *__restrict__ mcol) {
-  __shared__ double lds[6 * SS_MAT];
+                                                            int *__restrict__ mflag, int *__restrict__ mcol, SsBlockOff bo) {
+  __shared__ double lds[6 * SS_MAT + (R ? 2 * SS_RMAX * SS_LS : 0)];
   __shared__ int first[256];
   __shared__ int ibad;
   double *S00 = lds, *Si = S00 + SS_MAT, *Lw = Si + SS_MAT, *Tw = Lw + SS_MAT, *S10 = Tw + SS_MAT, *Am = S10 + SS_MAT;
@@ -216,35 +239,78 @@ __global__ __launch_bounds__(256) void ss_transition_kernel(const double *__rest
   const double *m = mom + (int64_t)b * SS_MOM;
   double *P = par + (int64_t)b * L.stride;
   const int n = MF ? rp : s;
-  for (int e = tid; e < n * n; e += 256) S00[(e / n) * SS_LS + e % n] = m[SS_M00 + (e / n) * s + e % n];
-  for (int e = tid; e < r * n; e += 256) S10[(e / n) * SS_LS + e % n] = m[SS_M10 + (e / n) * s + e % n];
+  if constexpr (!R) {
+    for (int e = tid; e < n * n; e += 256) S00[(e / n) * SS_LS + e % n] = m[SS_M00 + (e / n) * s + e % n];
+    for (int e = tid; e < r * n; e += 256) S10[(e / n) * SS_LS + e % n] = m[SS_M10 + (e / n) * s + e % n];
+  }
   int f = N;
   for (int i = tid; i < N; i += 256)
     if (status[(int64_t)b * N + i] && i < f) f = i;
   first[tid] = f;
   if (tid == 0) ibad = 0;
-  __syncthreads();
-  dfm::block_spd_inverse(S00, Si, Lw, Tw, n, SS_LS, &ibad);
-  for (int e = tid; e < r * n; e += 256) {
-    const int i = e / n, j = e % n;
-    double v = 0.0;
-    for (int k = 0; k < n; ++k) v = fma(S10[i * SS_LS + k], Si[k * SS_LS + j], v);
-    Am[i * SS_LS + j] = v;
-  }
-  __syncthreads();
-  for (int e = tid; e < r * r; e += 256) {
-    const int i = e / r, j = e % r;
-    double v = m[SS_M11 + e];
-    for (int k = 0; k < n; ++k) v = fma(-Am[i * SS_LS + k], S10[j * SS_LS + k], v);
-    Lw[i * SS_LS + j] = v / (double)(T - 1);
-  }
-  __syncthreads();
-  if (!ibad) {
+  if constexpr (R) {
+    double *AF = lds + 6 * SS_MAT, *QF = AF + SS_RMAX * SS_LS;   // A's rows and Q of all blocks, zero outside them
+    for (int e = tid; e < 2 * SS_RMAX * SS_LS; e += 256) AF[e] = 0.0;
+    const int pv = n / r;   // the VAR's own lags
+    for (int g = 0; g < bo.nb; ++g) {
+      const int o = bo.off[g], rg = bo.off[g + 1] - o, ng = rg * pv;
+      auto col = [&](int c) { return (c / rg) * r + o + c % rg; };   // the block's column c among the state's
+      __syncthreads();   // the previous block's matrices are read
+      for (int e = tid; e < ng * ng; e += 256) S00[(e / ng) * SS_LS + e % ng] = m[SS_M00 + col(e / ng) * s + col(e % ng)];
+      for (int e = tid; e < rg * ng; e += 256) S10[(e / ng) * SS_LS + e % ng] = m[SS_M10 + (o + e / ng) * s + col(e % ng)];
+      __syncthreads();
+      dfm::block_spd_inverse(S00, Si, Lw, Tw, ng, SS_LS, &ibad);
+      for (int e = tid; e < rg * ng; e += 256) {
+        const int i = e / ng, j = e % ng;
+        double v = 0.0;
+        for (int k = 0; k < ng; ++k) v = fma(S10[i * SS_LS + k], Si[k * SS_LS + j], v);
+        Am[i * SS_LS + j] = v;
+        AF[(o + i) * SS_LS + col(j)] = v;
+      }
+      __syncthreads();
+      for (int e = tid; e < rg * rg; e += 256) {
+        const int i = e / rg, j = e % rg;
+        double v = m[SS_M11 + (o + i) * r + o + j];
+        for (int k = 0; k < ng; ++k) v = fma(-Am[i * SS_LS + k], S10[j * SS_LS + k], v);
+        Lw[i * SS_LS + j] = v / (double)(T - 1);
+      }
+      __syncthreads();
+      for (int e = tid; e < rg * rg; e += 256) {
+        const int i = e / rg, j = e % rg;
+        QF[(o + i) * SS_LS + o + j] = 0.5 * (Lw[i * SS_LS + j] + Lw[j * SS_LS + i]);
+      }
+    }
+    __syncthreads();
+    if (!ibad) {
+      for (int e = tid; e < r * r; e += 256) P[L.oQ + e] = QF[(e / r) * SS_LS + e % r];
+      for (int e = tid; e < r * n; e += 256) P[L.oTm + (e / n) * s + e % n] = AF[(e / n) * SS_LS + e % n];
+    }
+  } else {
+    __syncthreads();
+    dfm::block_spd_inverse(S00, Si, Lw, Tw, n, SS_LS, &ibad);
+    for (int e = tid; e < r * n; e += 256) {
+      const int i = e / n, j = e % n;
+      double v = 0.0;
+      for (int k = 0; k < n; ++k) v = fma(S10[i * SS_LS + k], Si[k * SS_LS + j], v);
+      Am[i * SS_LS + j] = v;
+    }
+    __syncthreads();
     for (int e = tid; e < r * r; e += 256) {
       const int i = e / r, j = e % r;
-      P[L.oQ + e] = 0.5 * (Lw[i * SS_LS + j] + Lw[j * SS_LS + i]);
+      double v = m[SS_M11 + e];
+      for (int k = 0; k < n; ++k) v = fma(-Am[i * SS_LS + k], S10[j * SS_LS + k], v);
+      Lw[i * SS_LS + j] = v / (double)(T - 1);
     }
-    for (int e = tid; e < r * n; e += 256) P[L.oTm + (e / n) * s + e % n] = Am[(e / n) * SS_LS + e % n];
+    __syncthreads();
+    if (!ibad) {
+      for (int e = tid; e < r * r; e += 256) {
+        const int i = e / r, j = e % r;
+        P[L.oQ + e] = 0.5 * (Lw[i * SS_LS + j] + Lw[j * SS_LS + i]);
+      }
+      for (int e = tid; e < r * n; e += 256) P[L.oTm + (e / n) * s + e % n] = Am[(e / n) * SS_LS + e % n];
+    }
+  }
+  if (!ibad) {
     if (update_init) {
       for (int e = tid; e < ss; e += 256) P[L.oP0 + e] = m[SS_MP1 + e];
       if (tid < s) P[L.oa0 + tid] = m[SS_MA1 + tid];
@@ -265,12 +331,44 @@ __global__ __launch_bounds__(256) void ss_transition_kernel(const double *__rest
 
 }  // namespace
 
+int dfm::ss_blocks_args(dfm_ctx *ctx, const char *who, const dfm_ss_blocks *blocks, int64_t N, int r, bool *trivial,
+                        SsBlocks *bl, std::vector<uint16_t> &free) {
+  *trivial = false;
+  if (!blocks) return fail(ctx, -2, "%s: the factor blocks are missing", who);
+  int64_t where = -1;
+  switch (ss_blocks_check(blocks->n_blocks, blocks->block_r, blocks->member, N, r, &where)) {
+    case SS_BLK_OK: break;
+    case SS_BLK_NULL: return fail(ctx, -2, "%s: the blocks' sizes or their membership matrix are missing", who);
+    case SS_BLK_COUNT: return fail(ctx, -2, "%s: n_blocks = %d is outside 1..16", who, (int)blocks->n_blocks);
+    case SS_BLK_SIZE: return fail(ctx, -2, "%s: block %lld (0-based) has a size < 1", who, (long long)where);
+    case SS_BLK_SUM:
+      return fail(ctx, -2, "%s: the blocks' sizes sum to %lld, the model has r = %d factors", who, (long long)where, r);
+    case SS_BLK_SERIES:
+      return fail(ctx, -2, "%s: column %lld (0-based) is a member of no block", who, (long long)where);
+    case SS_BLK_EMPTY: return fail(ctx, -2, "%s: block %lld (0-based) has no member", who, (long long)where);
+  }
+  if (ss_blocks_trivial(blocks->n_blocks, blocks->member, N)) {
+    *trivial = true;
+    return 0;
+  }
+  if (r > SS_RMAX) return ss_param_error(ctx, who, SS_E_LIMIT, -1);
+  int off[SS_BMAX + 1];
+  ss_blocks_offsets(blocks->n_blocks, blocks->block_r, off);
+  bl->o.nb = blocks->n_blocks;
+  for (int g = 0; g <= blocks->n_blocks; ++g) bl->o.off[g] = (uint8_t)off[g];
+  free.resize((size_t)N);
+  ss_blocks_free_mask(blocks->n_blocks, off, blocks->member, N, free.data());
+  bl->free = free.data();
+  return 0;
+}
+
 // The EM over M panels (include/dfm.h).  The panel and the starts go up once;
 // per iteration one read-back (logliks and flags) decides which panels stop,
 // and the `active` flags go back; the rest crosses the bus at the end.
 int dfm::ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx,
                     int64_t stride, bool dev, const dfm_ss_params *starts, int64_t n_start, int max_iter, double tol, bool update_init,
-                    int h, const dfm_ss_em_out &out, dfm_ss_em_info *info, const dfm_ss_mf *mf, int p_var) {
+                    int h, const dfm_ss_em_out &out, dfm_ss_em_info *info, const dfm_ss_mf *mf, int p_var,
+                    const SsBlocks *blocks) {
   if (ss_em_check_args(X != nullptr, M, T64, N64, ldx, stride, starts != nullptr, n_start))
     return fail(ctx, -2, "%s: bad arguments (T >= 2, n_start 1 or M)", who);
   if (M == 0) return 0;
@@ -315,6 +413,14 @@ int dfm::ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, i
     HIPCHK(ctx, hipMemcpyAsync((void *)dlow, mf->low, (size_t)N, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // hw leaves scope
   }
+  StreamBuf dfree;   // factor blocks: the series' free masks
+  SsBlockOff bo{};
+  if (blocks) {
+    bo = blocks->o;
+    HIPCHK(ctx, dfree.alloc((size_t)N * 2, st));
+    HIPCHK(ctx, hipMemcpyAsync(dfree.p, blocks->free, (size_t)N * 2, hipMemcpyHostToDevice, st));
+  }
+  const uint16_t *dfree_mask = (const uint16_t *)dfree.p;
   // ---- panels per pass: everything a panel keeps on the device — the work doubles, its block and its flags
   const size_t per_part = (size_t)G.KS * G.Tpad * G.NCP, per_ws = (size_t)Tt * (2 * (size_t)s + 2 * (size_t)ss),
                per_pm = (size_t)G.KT * G.Nr * G.NCP, per_op = (size_t)T * G.NCP, per_filt = (size_t)T * r,
@@ -385,7 +491,7 @@ int dfm::ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, i
                       "column %d (0-based) is not positive", who, pb, j, mcl);
         if (mfl)
           return fail(ctx, SS_E_SINGULAR, "%s: panel %lld, the M-step giving iteration %d: %s not invertible", who, pb, j,
-                      (mfl & 8) ? "S00 is" : "an S_i is");
+                      (mfl & 8) ? (blocks ? "a block of S00 is" : "S00 is") : "an S_i is");
         if (efl) return ss_estep_error(ctx, who, pb, efl, j);
         const double ll = hll[i];
         if (out.loglik_path) out.loglik_path[(size_t)(c0 + i) * path_ld + j] = ll;
@@ -409,12 +515,14 @@ int dfm::ss_em_core(dfm_ctx *ctx, const char *who, const double *X, int64_t M, i
       HIPCHK(ctx, hipGetLastError());
       {
         Scope sc(ctx, DFM_KC_OLS);
-        hipLaunchKernelGGL(mf ? ss_loadings_kernel<true> : ss_loadings_kernel<false>,
-                           dim3((N + SS_LB - 1) / SS_LB, (unsigned)n), dim3(SS_LB), 0, st, (const double *)pm, N, G.Nr, r,
-                           G.NCP, G.KT, (const int *)dact, B, dp, status, dlow);
-        hipLaunchKernelGGL(mf ? ss_transition_kernel<true> : ss_transition_kernel<false>, dim3((unsigned)n), dim3(256), 0,
-                           st, (const double *)mom, T, N, r, s, rp, update_init ? 1 : 0, (const int *)dact, B, dp,
-                           (const int *)status, mflag, mcol);
+        auto *loadings = blocks ? (mf ? ss_loadings_kernel<true, true> : ss_loadings_kernel<false, true>)
+                                : (mf ? ss_loadings_kernel<true, false> : ss_loadings_kernel<false, false>);
+        auto *transition = blocks ? (mf ? ss_transition_kernel<true, true> : ss_transition_kernel<false, true>)
+                                  : (mf ? ss_transition_kernel<true, false> : ss_transition_kernel<false, false>);
+        hipLaunchKernelGGL(loadings, dim3((N + SS_LB - 1) / SS_LB, (unsigned)n), dim3(SS_LB), 0, st, (const double *)pm, N,
+                           G.Nr, r, G.NCP, G.KT, (const int *)dact, B, dp, status, dlow, dfree_mask);
+        hipLaunchKernelGGL(transition, dim3((unsigned)n), dim3(256), 0, st, (const double *)mom, T, N, r, s, rp,
+                           update_init ? 1 : 0, (const int *)dact, B, dp, (const int *)status, mflag, mcol, bo);
       }
       HIPCHK(ctx, hipGetLastError());
     }
@@ -485,6 +593,46 @@ int dfm_ss_em_mf(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N,
   DeviceShare gate(ctx->device);
   return ss_em_core(ctx, who, X, M, T, N, ldx, stride, spec->dev != 0, padded.data(), n_start, max_iter, tol,
                     spec->update_init != 0, spec->horizon, *out, info, mf, p);
+}
+
+int dfm_ss_em_blocks(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                     const dfm_ss_params *starts, int64_t n_start, const dfm_ss_mf *mf, const dfm_ss_blocks *blocks,
+                     const dfm_ss_em_spec *spec, const dfm_ss_em_out *out, dfm_ss_em_info *info) {
+  const char *who = "dfm_ss_em_blocks";
+  if (!ctx) return -1;
+  int max_iter = 0, L = 0;
+  double tol = 0.0;
+  if (!spec || !out || !starts || n_start < 1 || N < 1 ||
+      ss_em_defaults(spec->max_iter, spec->tol, spec->horizon, &max_iter, &tol))
+    return fail(ctx, -2, "%s: bad arguments", who);
+  const int r = starts[0].r, p = starts[0].p;
+  bool trivial = false;
+  SsBlocks bl{};
+  std::vector<uint16_t> free;
+  if (int rc = ss_blocks_args(ctx, who, blocks, N, r, &trivial, &bl, free)) return rc;
+  if (trivial)
+    return mf ? dfm_ss_em_mf(ctx, X, M, T, N, ldx, stride, starts, n_start, mf, spec, out, info)
+              : dfm_ss_em(ctx, X, M, T, N, ldx, stride, starts, n_start, spec, out, info);
+  if (mf)
+    if (int rc = ss_mf_args(ctx, who, mf, N, true, r, p, "r, p, n_w", &L)) return rc;
+  if (int rc = ss_check_dims(r, L ? L : p)) return ss_param_error(ctx, who, rc, -1);
+  int off[SS_BMAX + 1];
+  for (int g = 0; g <= bl.o.nb; ++g) off[g] = bl.o.off[g];
+  for (int64_t k = 0; k < n_start; ++k) {
+    const dfm_ss_params &q = starts[k];
+    if (q.r != r || q.p != p) return fail(ctx, -2, "%s: start %lld has another (r, p)", who, (long long)k);
+    if (!q.lambda || !q.A || !q.Q) return fail(ctx, -2, "%s: bad arguments", who);
+    int64_t i = -1, j = -1;
+    if (const int which = ss_blocks_check_start(N, r, p, q.lambda, q.A, q.Q, bl.o.nb, off, bl.free, &i, &j))
+      return fail(ctx, -2, "%s: start %lld: %s[%lld, %lld] (0-based) is not zero where the blocks restrict it", who,
+                  (long long)k, which == 1 ? "lambda" : which == 2 ? "A" : "Q", (long long)i, (long long)j);
+  }
+  std::vector<dfm_ss_params> padded;
+  std::vector<double> Apad;
+  if (L && ss_mf_pad_params(starts, n_start, r, p, L, padded, Apad) >= 0) return fail(ctx, -2, "%s: bad arguments", who);
+  DeviceShare gate(ctx->device);
+  return ss_em_core(ctx, who, X, M, T, N, ldx, stride, spec->dev != 0, L ? padded.data() : starts, n_start, max_iter, tol,
+                    spec->update_init != 0, spec->horizon, *out, info, L ? mf : nullptr, L ? p : 0, &bl);
 }
 
 }  // extern "C"

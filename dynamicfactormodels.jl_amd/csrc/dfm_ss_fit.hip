@@ -2,7 +2,8 @@
 // the two-step estimator of Doz, Giannone & Reichlin (2011) (dfm_ss_fit: dfm_em,
 // ss_estimate of dfm_ss_host.h, then ss_smooth_core of dfm_ss.hip), its iteration
 // to the quasi-maximum likelihood (dfm_ss_fit_ml: ss_em_core of dfm_ss_em.hip in
-// the smoother's place) and both with mixed frequencies (dfm_ss_fit_mf).  The
+// the smoother's place), both with mixed frequencies (dfm_ss_fit_mf) and all of
+// them with factor blocks (dfm_ss_fit_blocks: the block-wise start).  The
 // steps and the return codes are stated in include/dfm.h.
 #include "dfm_host.h"
 #include "dfm_ss_host.h"
@@ -13,9 +14,12 @@ namespace {
 // takes the place of step 5's smoother.
 // mf (with a marked series): dfm_ss_fit_mf — the low series' start values by
 // ss_mf_start, the padded state, and Lambda ft_t|T for the low columns.
+// blocks with bl (checked, a restriction): dfm_ss_fit_blocks — the block-wise
+// start in the place of the EM's F and L, and the EM with the blocks.
 int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                 int horizon, dfm_em_info *info, const dfm_ss_fit_out *out, const dfm_ss_em_spec *ml, double *a0_out,
-                double *loglik_path, dfm_ss_em_info *ml_info, const dfm_ss_mf *mf = nullptr, double *agg_out = nullptr) {
+                double *loglik_path, dfm_ss_em_info *ml_info, const dfm_ss_mf *mf = nullptr, double *agg_out = nullptr,
+                const dfm_ss_blocks *blocks = nullptr, const SsBlocks *bl = nullptr) {
   if (!X || !em_spec || !out || T < 2 || N < 1 || ldx < T || horizon < 0) return fail(ctx, -2, "%s: bad arguments", who);
   int ml_iter = 0;
   double ml_tol = 0.0;
@@ -50,15 +54,38 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
       Zm[(size_t)i * T + t] = std::isnan(Xs[(size_t)i * lds + t]) ? NAN : Z[(size_t)i * T + t];
   std::vector<double> sig((size_t)N), A((size_t)r * s), Q((size_t)r * r), P0((size_t)s * s);
   int64_t where = -1;
-  rc = ss_estimate(Zm.data(), T, N, T, F.data(), L.data(), r, p, sig.data(), A.data(), Q.data(), P0.data(), &where);
+  if (bl) {   // the block-wise start: every block's principal components of what the blocks before it left
+    std::vector<double> R(Z), Rg(tn), Fg((size_t)T * r), Lg((size_t)N * r), evg((size_t)r);
+    std::fill(L.begin(), L.begin() + (size_t)N * r, 0.0);
+    int off[SS_BMAX + 1];
+    for (int g = 0; g <= bl->o.nb; ++g) off[g] = bl->o.off[g];
+    for (int g = 0; g < bl->o.nb; ++g) {
+      const uint8_t *mem = blocks->member + (size_t)g * N;
+      const int rg = off[g + 1] - off[g];
+      const int64_t ng = ss_blocks_gather(R.data(), T, N, mem, Rg.data());
+      if (ng < rg)
+        return fail(ctx, SS_E_VAR, "%s: block %d (0-based) has %lld members, fewer than its %d factors", who, g,
+                    (long long)ng, rg);
+      if ((rc = dfm_pca(ctx, Rg.data(), T, ng, T, rg, evg.data(), Fg.data(), Lg.data(), nullptr))) return rc;
+      ss_blocks_deflate(R.data(), T, N, mem, off[g], rg, Fg.data(), Lg.data(), ng, F.data(), L.data());
+    }
+    rc = ss_blocks_estimate(Zm.data(), T, N, T, F.data(), L.data(), r, p, bl->o.nb, off, sig.data(), A.data(), Q.data(),
+                            P0.data(), &where);
+    if (rc == SS_E_VAR)
+      return fail(ctx, rc, "%s: block %lld (0-based): the VAR needs T - p > r_g p rows and a non-singular Xl'Xl", who,
+                  (long long)where);
+  } else {
+    rc = ss_estimate(Zm.data(), T, N, T, F.data(), L.data(), r, p, sig.data(), A.data(), Q.data(), P0.data(), &where);
+  }
   if (rc) return ss_param_error(ctx, who, rc, where);
   const int64_t Tt = T + h;
   std::vector<double> sm((size_t)Tt * r), agg, Apad;
   if (mf) {
-    rc = ss_mf_start(Zm.data(), T, N, T, F.data(), r, mf->w, mf->n_w, mf->low, L.data(), sig.data(), &where);
+    rc = ss_mf_start(Zm.data(), T, N, T, F.data(), r, mf->w, mf->n_w, mf->low, L.data(), sig.data(), &where,
+                     bl ? bl->free : nullptr);
     if (rc == SS_E_VAR)
-      return fail(ctx, rc, "%s: low-frequency column %lld (0-based) has fewer than r + 1 observed rows t >= n_w - 1", who,
-                  (long long)where);
+      return fail(ctx, rc, "%s: low-frequency column %lld (0-based) has fewer than %s + 1 observed rows t >= n_w - 1", who,
+                  (long long)where, bl ? "its free factors" : "r");
     if (rc) return ss_param_error(ctx, who, rc, where);
     agg.resize((size_t)Tt * r);
     Apad.resize((size_t)r * sp);
@@ -80,7 +107,7 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
                            sm.data(), out->smoothed_cov, nullptr, loglik_path, mf ? agg.data() : nullptr};
     dfm_ss_em_info mi{};
     rc = ss_em_core(ctx, who, Zm.data(), 1, T, N, T, (int64_t)tn, false, &start, 1, ml_iter, ml_tol, ml->update_init != 0, h,
-                    eo, &mi, mf, p);
+                    eo, &mi, mf, p, bl);
     if (rc) return rc;
     L = L2, sig = sig2, A = A2, Q = Q2, P0 = P02;
     if (out->loglik) *out->loglik = mi.loglik;
@@ -159,6 +186,31 @@ int dfm_ss_fit_mf(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t l
                   : dfm_ss_fit(ctx, X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out);
   return ss_fit_impl(ctx, who, X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out, method ? ml_spec : nullptr, a0_out,
                      loglik_path, ml_info, mf, smoothed_agg);
+}
+
+int dfm_ss_fit_blocks(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec,
+                      int p, const dfm_ss_em_spec *ml_spec, const dfm_ss_mf *mf, const dfm_ss_blocks *blocks, int method,
+                      dfm_em_info *info, const dfm_ss_fit_out *out, double *a0_out, double *loglik_path,
+                      dfm_ss_em_info *ml_info, double *smoothed_agg) {
+  const char *who = "dfm_ss_fit_blocks";
+  if (!ctx) return -1;
+  if (!ml_spec || !em_spec || N < 1 || (method != 0 && method != 1)) return fail(ctx, -2, "%s: bad arguments", who);
+  if (em_spec->r <= 0) return fail(ctx, -3, "%s: the number of factors must be fixed at the sum of the blocks' sizes", who);
+  bool trivial = false;
+  SsBlocks bl{};
+  std::vector<uint16_t> free;
+  if (int rc = ss_blocks_args(ctx, who, blocks, N, em_spec->r, &trivial, &bl, free)) return rc;
+  if (trivial) {
+    if (mf) return dfm_ss_fit_mf(ctx, X, T, N, ldx, em_spec, p, ml_spec, mf, method, info, out, a0_out, loglik_path, ml_info,
+                                 smoothed_agg);
+    return method ? dfm_ss_fit_ml(ctx, X, T, N, ldx, em_spec, p, ml_spec, info, out, a0_out, loglik_path, ml_info)
+                  : dfm_ss_fit(ctx, X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out);
+  }
+  int L = 0;
+  if (mf)
+    if (int rc = ss_mf_args(ctx, who, mf, N, true, em_spec->r, p, "p, n_w", &L)) return rc;
+  return ss_fit_impl(ctx, who, X, T, N, ldx, em_spec, p, ml_spec->horizon, info, out, method ? ml_spec : nullptr, a0_out,
+                     loglik_path, ml_info, L ? mf : nullptr, L ? smoothed_agg : nullptr, blocks, &bl);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // steps 2-3 of the two-step fit (dfm_ss_fit.hip: idiosyncratic variances,
 // VAR(p) by OLS), and of the quasi-ML EM (dfm_ss_em.hip) the spec's defaults,
 // the stopping rule and the checks; of the mixed-frequency model the limits,
-// [A 0], Z_l and the fit's start values of the low series; the panels per
+// [A 0], Z_l and the fit's start values of the low series; of the factor
+// blocks the checks, the free mask and the fit's block-wise start; the panels per
 // pass of both drivers; of the simulation smoother (dfm_ss_sim.hip) the
 // factor of a positive semi-definite matrix, the count of normals, the
 // argument checks and the draws per pass; of the news decomposition
@@ -145,24 +146,12 @@ inline int ss_check_params(int64_t N, int r, int p, const double *L, const doubl
   return 0;
 }
 
-// Steps 2-4 of the two-step fit.  Zm: T x N column-major (ldz >= T), NaN =
-// missing; F: T x r column-major (ld T); L: N x r column-major (ld N).
-//   sigma2_i = sum_t m_ti (Z_ti - f_t' lambda_i)^2 / n_i
-//   VAR(p) by OLS without intercept: Y = F[p:], Xl = [F[p-1:T-1], ..., F[0:T-p]],
-//   A' = (Xl'Xl)^-1 Xl'Y, U = Y - Xl A', Q = U'U / (T - p)
-//   P0 = ss_stationary_cov(A, Q)
-// Outputs column-major: sigma2 (N), A (r x rp), Q (r x r), P0 (s x s); *where
-// names the column of a failed variance.
-inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
-                       int p, double *sigma2, double *A, double *Q, double *P0, int64_t *where) {
-  int rc = ss_check_dims(r, p);
-  if (rc) return rc;
-  if (!Zm || !F || !L || !sigma2 || !A || !Q || !P0 || T < 2 || N < 1 || ldz < T) return -2;
-  const int s = r * p;
-  for (size_t e = 0; e < (size_t)T * r; ++e)
-    if (isnan(F[e])) return SS_E_NAN;
-  for (size_t e = 0; e < (size_t)N * r; ++e)
-    if (isnan(L[e])) return SS_E_NAN;
+// Step 2 of the two-step fit: sigma2_i = sum_t m_ti (Z_ti - f_t' lambda_i)^2 / n_i.
+// Zm: T x N column-major (ldz >= T), NaN = missing; F: T x r column-major
+// (ld T); L: N x r column-major (ld N).  *where names the column of a failed
+// variance (SS_E_SIGMA).
+inline int ss_idio_var(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                       double *sigma2, int64_t *where) {
   for (int64_t i = 0; i < N; ++i) {
     double ss = 0.0;
     int64_t n = 0;
@@ -181,6 +170,16 @@ inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
       return SS_E_SIGMA;
     }
   }
+  return 0;
+}
+
+// Step 3: VAR(p) by OLS without intercept on F (T x r column-major, ld T):
+//   Y = F[p:], Xl = [F[p-1:T-1], ..., F[0:T-p]],
+//   A' = (Xl'Xl)^-1 Xl'Y, U = Y - Xl A', Q = U'U / (T - p)
+// A (r x rp) and Q (r x r) column-major.  SS_E_VAR for T - p <= r p or a
+// singular Xl'Xl, SS_E_SINGULAR for a Q that is not positive definite.
+inline int ss_var_ols(const double *F, int64_t T, int r, int p, double *A, double *Q) {
+  const int s = r * p;
   const int64_t n = T - p;
   if (n <= s) return SS_E_VAR;
   // Xl[t][k r + j] = F[p - 1 - k + t][j]
@@ -229,7 +228,32 @@ inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
       Q[(size_t)j * r + i] = Q[(size_t)i * r + j] = v;
       Qc[i * r + j] = Qc[j * r + i] = v;
     }
-  if (!ss_cholesky(Qc.data(), r)) return SS_E_SINGULAR;
+  return ss_cholesky(Qc.data(), r) ? 0 : SS_E_SINGULAR;
+}
+
+// The arguments of steps 2-4: dims, pointers, NaN in F or L.
+inline int ss_estimate_args(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                            int p, const double *sigma2, const double *A, const double *Q, const double *P0) {
+  const int rc = ss_check_dims(r, p);
+  if (rc) return rc;
+  if (!Zm || !F || !L || !sigma2 || !A || !Q || !P0 || T < 2 || N < 1 || ldz < T) return -2;
+  for (size_t e = 0; e < (size_t)T * r; ++e)
+    if (isnan(F[e])) return SS_E_NAN;
+  for (size_t e = 0; e < (size_t)N * r; ++e)
+    if (isnan(L[e])) return SS_E_NAN;
+  return 0;
+}
+
+// Steps 2-4 of the two-step fit: ss_idio_var, ss_var_ols, then
+//   P0 = ss_stationary_cov(A, Q)
+// Outputs column-major: sigma2 (N), A (r x rp), Q (r x r), P0 (s x s); *where
+// names the column of a failed variance.
+inline int ss_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                       int p, double *sigma2, double *A, double *Q, double *P0, int64_t *where) {
+  int rc = ss_estimate_args(Zm, T, N, ldz, F, L, r, p, sigma2, A, Q, P0);
+  if (rc) return rc;
+  if ((rc = ss_idio_var(Zm, T, N, ldz, F, L, r, sigma2, where))) return rc;
+  if ((rc = ss_var_ols(F, T, r, p, A, Q))) return rc;
   return ss_stationary_cov(A, Q, r, p, P0);
 }
 
@@ -279,8 +303,14 @@ inline void ss_mf_zl(const double *w, int n_w, int r, int s, double *Zl) {
 // rewritten for the marked series only.  SS_E_VAR with fewer than r + 1 such
 // rows or a singular ft'ft, SS_E_SIGMA for a non-positive variance; *where
 // names the column.
+// free (factor blocks; null: every factor): bit j of free[i] says that series
+// i loads on factor j.  The regression is then on the aggregate of its free
+// factors only: row and column j of ft'ft become e_j and ft'z_j zero for the
+// others, which leaves lambda_ij = 0 there and the free sub-system's solution
+// (r + 1 becomes the count of its free factors + 1).
 inline int ss_mf_start(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, int r, const double *w,
-                       int n_w, const uint8_t *low, double *L, double *sigma2, int64_t *where) {
+                       int n_w, const uint8_t *low, double *L, double *sigma2, int64_t *where,
+                       const uint16_t *free = nullptr) {
   if (!Zm || !F || !w || !low || !L || !sigma2 || r < 1 || r > SS_RMAX || n_w < 1 || n_w > SS_WMAX || T < 1 || ldz < T)
     return -2;
   std::vector<double> ft((size_t)T * r, 0.0), G((size_t)r * r), g((size_t)r);
@@ -305,7 +335,15 @@ inline int ss_mf_start(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
         for (int b = 0; b <= a; ++b) G[a * r + b] += ft[(size_t)t * r + a] * ft[(size_t)t * r + b];
       }
     }
-    if (n < r + 1 || !ss_cholesky(G.data(), r)) return SS_E_VAR;
+    int nfree = r;
+    if (free)
+      for (int a = 0; a < r; ++a) {
+        if ((free[i] >> a) & 1) continue;
+        --nfree;
+        g[a] = 0.0;
+        for (int b = 0; b < r; ++b) G[a * r + b] = G[b * r + a] = a == b ? 1.0 : 0.0;
+      }
+    if (n < nfree + 1 || !ss_cholesky(G.data(), r)) return SS_E_VAR;
     for (int a = 0; a < r; ++a) {
       double v = g[a];
       for (int k = 0; k < a; ++k) v -= G[a * r + k] * g[k];
@@ -325,7 +363,7 @@ inline int ss_mf_start(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
     }
     const double v = rss / (double)n;
     if (!(v > 0.0) || isinf(v)) return SS_E_SIGMA;
-    for (int a = 0; a < r; ++a) L[(size_t)a * N + i] = g[a];
+    for (int a = 0; a < r; ++a) L[(size_t)a * N + i] = (!free || ((free[i] >> a) & 1)) ? g[a] : 0.0;
     sigma2[i] = v;
   }
   return 0;
@@ -391,6 +429,165 @@ inline bool ss_em_empty_column(const double *X, int64_t M, int64_t T, int64_t N,
       }
     }
   return false;
+}
+
+// ------------------------------------------ factor blocks (dfm_ss_em_blocks)
+// Block g of n_blocks owns the contiguous factors off[g] .. off[g + 1] - 1;
+// member (N x n_blocks column-major, ld N) says which series load on it.
+// Lambda_ij = 0 where series i is no member of factor j's block; every A_k
+// and Q are block-diagonal.
+constexpr int SS_BMAX = 16;
+
+// Why a block specification is refused (ss_blocks_check), in the order it is looked for.
+enum SsBlocksBad {
+  SS_BLK_OK = 0,
+  SS_BLK_NULL,     // a null struct field
+  SS_BLK_COUNT,    // n_blocks outside 1..16
+  SS_BLK_SIZE,     // a block of size < 1 (*where: the block)
+  SS_BLK_SUM,      // the sizes do not sum to r (*where: their sum)
+  SS_BLK_SERIES,   // a series that is a member of no block (*where: the column)
+  SS_BLK_EMPTY     // a block without a member (*where: the block)
+};
+
+inline SsBlocksBad ss_blocks_check(int n_blocks, const int32_t *block_r, const uint8_t *member, int64_t N, int r,
+                                   int64_t *where) {
+  if (!block_r || !member) return SS_BLK_NULL;
+  if (n_blocks < 1 || n_blocks > SS_BMAX) return SS_BLK_COUNT;
+  int64_t sum = 0;
+  for (int g = 0; g < n_blocks; ++g) {
+    *where = g;
+    if (block_r[g] < 1) return SS_BLK_SIZE;
+    sum += block_r[g];
+  }
+  *where = sum;
+  if (sum != r) return SS_BLK_SUM;
+  for (int64_t i = 0; i < N; ++i) {
+    bool any = false;
+    for (int g = 0; g < n_blocks; ++g) any = any || member[(size_t)g * N + i];
+    *where = i;
+    if (!any) return SS_BLK_SERIES;
+  }
+  for (int g = 0; g < n_blocks; ++g) {
+    bool any = false;
+    for (int64_t i = 0; i < N; ++i) any = any || member[(size_t)g * N + i];
+    *where = g;
+    if (!any) return SS_BLK_EMPTY;
+  }
+  return SS_BLK_OK;
+}
+
+// One block that every series is a member of: no restriction.
+inline bool ss_blocks_trivial(int n_blocks, const uint8_t *member, int64_t N) {
+  if (n_blocks != 1) return false;
+  for (int64_t i = 0; i < N; ++i)
+    if (!member[i]) return false;
+  return true;
+}
+
+// off[0 .. n_blocks]: the first factor of every block, then r.
+inline void ss_blocks_offsets(int n_blocks, const int32_t *block_r, int *off) {
+  off[0] = 0;
+  for (int g = 0; g < n_blocks; ++g) off[g + 1] = off[g] + block_r[g];
+}
+
+// free[i]: bit j set when series i loads on factor j (r <= 16 factors).
+inline void ss_blocks_free_mask(int n_blocks, const int *off, const uint8_t *member, int64_t N, uint16_t *free) {
+  for (int64_t i = 0; i < N; ++i) {
+    unsigned m = 0;
+    for (int g = 0; g < n_blocks; ++g)
+      if (member[(size_t)g * N + i])
+        for (int j = off[g]; j < off[g + 1]; ++j) m |= 1u << j;
+    free[i] = (uint16_t)m;
+  }
+}
+
+// A start must hold zeros where the restriction does.  0, or the first
+// offender: 1 Lambda[*row, *col], 2 A[*row, *col] (r x rp), 3 Q[*row, *col].
+// L (ld N), A, Q column-major.
+inline int ss_blocks_check_start(int64_t N, int r, int p, const double *L, const double *A, const double *Q,
+                                 int n_blocks, const int *off, const uint16_t *free, int64_t *row, int64_t *col) {
+  int of[SS_RMAX];   // the block of a factor
+  for (int g = 0; g < n_blocks; ++g)
+    for (int j = off[g]; j < off[g + 1]; ++j) of[j] = g;
+  auto at = [&](int which, int64_t i, int64_t j) {
+    *row = i, *col = j;
+    return which;
+  };
+  for (int j = 0; j < r; ++j)
+    for (int64_t i = 0; i < N; ++i)
+      if (!((free[i] >> j) & 1) && L[(size_t)j * N + i] != 0.0) return at(1, i, j);
+  for (int c = 0; c < r * p; ++c)
+    for (int i = 0; i < r; ++i)
+      if (of[i] != of[c % r] && A[(size_t)c * r + i] != 0.0) return at(2, i, c);
+  for (int c = 0; c < r; ++c)
+    for (int i = 0; i < r; ++i)
+      if (of[i] != of[c] && Q[(size_t)c * r + i] != 0.0) return at(3, i, c);
+  return 0;
+}
+
+// The block-wise start of the fit, its host steps.  R (T x N column-major, ld
+// T) starts as the completed standardised panel; for every block in order the
+// caller takes the principal components of the block's member columns
+// (ss_blocks_gather), and ss_blocks_deflate stores them and subtracts their
+// common component from those columns.
+// The member columns of R side by side into Rg (T x the count, ld T); returns the count.
+inline int64_t ss_blocks_gather(const double *R, int64_t T, int64_t N, const uint8_t *member_g, double *Rg) {
+  int64_t n = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    if (!member_g[i]) continue;
+    for (int64_t t = 0; t < T; ++t) Rg[(size_t)n * T + t] = R[(size_t)i * T + t];
+    ++n;
+  }
+  return n;
+}
+
+// Fg (T x rg, ld T) into columns o .. o + rg - 1 of F (ld T), Lg (ng x rg, ld
+// ng) into the members' rows of those columns of L (N x r, ld N; the other
+// rows are not touched), and R[:, members] -= Fg Lg'.
+inline void ss_blocks_deflate(double *R, int64_t T, int64_t N, const uint8_t *member_g, int o, int rg, const double *Fg,
+                              const double *Lg, int64_t ng, double *F, double *L) {
+  for (int j = 0; j < rg; ++j)
+    for (int64_t t = 0; t < T; ++t) F[(size_t)(o + j) * T + t] = Fg[(size_t)j * T + t];
+  int64_t n = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    if (!member_g[i]) continue;
+    for (int j = 0; j < rg; ++j) L[(size_t)(o + j) * N + i] = Lg[(size_t)j * ng + n];
+    for (int64_t t = 0; t < T; ++t) {
+      double c = 0.0;
+      for (int j = 0; j < rg; ++j) c = fma(Fg[(size_t)j * T + t], Lg[(size_t)j * ng + n], c);
+      R[(size_t)i * T + t] -= c;
+    }
+    ++n;
+  }
+}
+
+// Steps 2-4 of the fit with blocks: ss_idio_var on the whole of F and L, then
+// ss_var_ols per block on its own columns of F into the block of A_k and Q
+// (zero elsewhere), then the stationary covariance.  Arguments and outputs as
+// ss_estimate; *where names the column of a failed variance, or the block of
+// a failed VAR.
+inline int ss_blocks_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                              int p, int n_blocks, const int *off, double *sigma2, double *A, double *Q, double *P0,
+                              int64_t *where) {
+  int rc = ss_estimate_args(Zm, T, N, ldz, F, L, r, p, sigma2, A, Q, P0);
+  if (rc) return rc;
+  if ((rc = ss_idio_var(Zm, T, N, ldz, F, L, r, sigma2, where))) return rc;
+  for (int e = 0; e < r * r * p; ++e) A[e] = 0.0;
+  for (int e = 0; e < r * r; ++e) Q[e] = 0.0;
+  std::vector<double> Ag, Qg;
+  for (int g = 0; g < n_blocks; ++g) {
+    const int o = off[g], rg = off[g + 1] - o;
+    Ag.assign((size_t)rg * rg * p, 0.0);
+    Qg.assign((size_t)rg * rg, 0.0);
+    if (where) *where = g;
+    if ((rc = ss_var_ols(F + (size_t)o * T, T, rg, p, Ag.data(), Qg.data()))) return rc;
+    for (int k = 0; k < p; ++k)
+      for (int j = 0; j < rg; ++j)
+        for (int i = 0; i < rg; ++i) A[(size_t)(k * r + o + j) * r + o + i] = Ag[(size_t)(k * rg + j) * rg + i];
+    for (int j = 0; j < rg; ++j)
+      for (int i = 0; i < rg; ++i) Q[(size_t)(o + j) * r + o + i] = Qg[(size_t)j * rg + i];
+  }
+  return ss_stationary_cov(A, Q, r, p, P0);
 }
 
 // ------------------------------------------------- panels per pass (both drivers)

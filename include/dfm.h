@@ -718,6 +718,70 @@ int dfm_ss_fit_mf(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t l
                   const dfm_ss_fit_out *out, double *a0_out, double *loglik_path, dfm_ss_em_info *ml_info,
                   double *smoothed_agg);
 
+/* Factor blocks (Banbura, Giannone & Reichlin 2011; Banbura & Modugno 2014,
+ * section 2.3): a global factor that every series loads on beside group
+ * factors that only their own series load on, each block with its own VAR.
+ *   blocks g = 1..n_b of sizes r_g >= 1, sum r_g = r; block g owns the
+ *   contiguous factors o_g .. o_g + r_g - 1 (o_1 = 0)
+ *   member: N x n_b, != 0: the series loads on the block;
+ *   free_ij = member[i, g(j)], g(j) the block that owns factor j
+ *   Lambda_ij = 0 wherever free_ij = 0
+ *   A_k (k = 1..p) and Q are block-diagonal with the blocks' sizes
+ *   P0 and a0 are unrestricted; everything else is the model above, plain
+ *   or mixed-frequency.
+ * The E-step is unchanged (a zero is a zero to the collapse and the
+ * recursion).  M-step, with the sums above (S_i, g_i those of the series'
+ * class in the mixed-frequency model):
+ *   per series i, J = {j : free_ij}: lambda_i[J] = S_i[J,J]^-1 g_i[J], zero
+ *   elsewhere; sigma^2_i = (q_i - lambda_i' g_i) / n_i
+ *   per block g, rows G = its factors, columns c = {k r + o_g + j : k < p,
+ *   j < r_g}: A[G, c] = S10[G, c] S00[c, c]^-1, zero elsewhere;
+ *   Q[G, G] = (S11[G, G] - A[G, c] S10[G, c]') / (T - 1), symmetrised, zero
+ *   elsewhere (mixed frequency: k runs over the VAR's own p lags).
+ * This is the exact maximiser under the restrictions.  The stopping rule,
+ * freezing, update_init, return codes and messages are dfm_ss_em's.
+ * -2 also, with a message naming the offender: a NULL struct or field,
+ * n_blocks outside 1..16, a size < 1, sum r_g != the starts' r, a series that
+ * is a member of no block (the column), a block without a member (the block),
+ * a start whose Lambda, A or Q is not zero at a restricted position (the
+ * parameter and the entry).  One block of size r that every series is a
+ * member of is no restriction: the call is then dfm_ss_em / dfm_ss_em_mf /
+ * dfm_ss_fit / dfm_ss_fit_ml / dfm_ss_fit_mf bit for bit. */
+typedef struct dfm_ss_blocks {
+  int32_t n_blocks;          /* 1..16 */
+  const int32_t *block_r;    /* n_blocks sizes, each >= 1, sum = r */
+  const uint8_t *member;     /* N x n_blocks column-major (ld N), != 0: the series loads on the block */
+} dfm_ss_blocks;
+
+/* dfm_ss_em (mf NULL) or dfm_ss_em_mf with the blocks; every other argument
+ * as theirs. */
+int dfm_ss_em_blocks(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                     const dfm_ss_params *starts, int64_t n_start, const dfm_ss_mf *mf /* NULL: plain */,
+                     const dfm_ss_blocks *blocks, const dfm_ss_em_spec *spec, const dfm_ss_em_out *out,
+                     dfm_ss_em_info *info);
+
+/* dfm_ss_fit_mf (mf NULL: dfm_ss_fit for method 0, dfm_ss_fit_ml for method 1)
+ * with the blocks:
+ *   1. dfm_em on the panel at r = sum r_g (em_spec->r must be that sum: a
+ *      selected r is -3): Z, mu, sd and the completed standardised panel
+ *   2. R <- Z; for g = 1..n_b in order: (F_g, L_g) = dfm_pca of the member
+ *      columns of R at k = r_g (-11 when the block has fewer than r_g
+ *      members, the message names the block); F_g into the block's factor
+ *      columns, L_g into its members' rows of Lambda (zero elsewhere); F_g L_g'
+ *      is subtracted from those columns of R
+ *   3. sigma^2_i over the observed entries of Z - F Lambda'; a VAR(p) by OLS
+ *      per block on its own F_g (the arithmetic of dfm_ss_estimate): A and Q
+ *      block-diagonal; with mf, a low series' lambda_i, sigma^2_i by OLS on
+ *      the aggregate of its free factors only (as dfm_ss_fit_mf otherwise;
+ *      -11 with fewer observed rows than its free factors + 1)
+ *   4. P0 = the stationary covariance
+ *   5. the smoother (method 0) or the EM with the blocks (method 1).
+ * `out` as dfm_ss_fit_mf fills it; em_factors holds step 2's F. */
+int dfm_ss_fit_blocks(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec,
+                      int p, const dfm_ss_em_spec *ml_spec, const dfm_ss_mf *mf /* NULL */,
+                      const dfm_ss_blocks *blocks, int method, dfm_em_info *info, const dfm_ss_fit_out *out,
+                      double *a0_out, double *loglik_path, dfm_ss_em_info *ml_info, double *smoothed_agg);
+
 /* Simulation smoother (Durbin & Koopman 2002), dfm_ss_simulate (dfm_ss_sim.hip):
  * D joint draws of f_1..f_{T+h} given the observed entries of one panel, for
  * the plain model of dfm_ss_smooth, Tt = T + h rows, s = r p.  The smoother's

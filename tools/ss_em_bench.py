@@ -15,7 +15,9 @@ one kalman_smoother call at the same shape (the smoother without the moments),
 so the table shows what the moments add to a pass.  For the batch it times
 --singles single-panel calls against the one batched call.  --numpy times the
 NumPy reference (tests/ss_em_reference.py) on the host for --numpy-iters
-iterations of one panel.
+iterations of one panel.  --blocks B runs the EM with B equal factor blocks
+(dfm_ss_em_blocks): block 0 global, series i a member of block 1 + i % (B - 1),
+the loadings drawn with the restriction's zeros.
 
 One JSON line per configuration on stdout; --out appends them to a file."""
 import argparse
@@ -38,6 +40,16 @@ def parameters(N, r, p, rng):
     sigma2 = rng.uniform(0.5, 2.0, size=N)
     A = np.hstack([0.5 * np.eye(r)] + [0.2 / k * np.eye(r) for k in range(1, p)])
     return L, sigma2, A, np.eye(r)
+
+
+def blocks_of(N, r, B):
+    """(sizes, N x B membership, N x r free mask) of B equal blocks, the first global."""
+    if B < 2 or r % B:
+        raise SystemExit(f"--blocks must divide r = {r} into at least two blocks")
+    member = np.zeros((N, B), dtype=bool)
+    member[:, 0] = True
+    member[np.arange(N), 1 + np.arange(N) % (B - 1)] = True
+    return (r // B,) * B, member, np.repeat(member, r // B, axis=1)
 
 
 def panels(M, T, N, L, sigma2, A, seed):
@@ -99,6 +111,7 @@ def main():
     ap.add_argument("--shapes", type=int, nargs="*", default=[0, 1])
     ap.add_argument("--numpy", action="store_true", help="time the NumPy reference instead of the device")
     ap.add_argument("--numpy-iters", type=int, nargs="*", default=[20, 1])
+    ap.add_argument("--blocks", type=int, default=0, help="B > 1: the EM with B equal factor blocks")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rng = np.random.default_rng(1)
@@ -119,6 +132,11 @@ def main():
         for k in args.shapes:
             T, N, r, p = SHAPES[k]
             L, sigma2, A, Q = parameters(N, r, p, rng)
+            kw.pop("factor_blocks", None), kw.pop("block_members", None)
+            if args.blocks:
+                sizes, member, free = blocks_of(N, r, args.blocks)
+                L = L * free
+                kw.update(factor_blocks=sizes, block_members=member)
             x = panels(args.batch, T, N, L, sigma2, A, seed=T)
             for M in (1, args.batch):
                 xs = x[:M]
@@ -138,7 +156,8 @@ def main():
                 ks = classes(ctx.read_timing())
                 ctx.enable_timing(False)
                 gain = res.loglik_path[:, -1] - res.loglik_path[:, 0]
-                line = {"T": T, "N": N, "r": r, "p": p, "M": M, "iters": args.iters, "wall_ms_best": min(wall),
+                line = {"T": T, "N": N, "r": r, "p": p, "M": M, "blocks": args.blocks, "iters": args.iters,
+                        "wall_ms_best": min(wall),
                         "wall_ms_median": statistics.median(wall),
                         "wall_ms_per_iteration": statistics.median(wall) / args.iters, "em": em,
                         "kalman_smoother": {k2: v for k2, v in ks.items() if k2.startswith(("stats", "misc"))},
