@@ -5,6 +5,7 @@
 #pragma once
 #include "dfm_common.h"
 #include "dfm_criteria.h"
+#include <functional>
 #include <vector>
 
 struct dfm_ctx;   // dfm_host.h
@@ -456,9 +457,35 @@ int ss_mf_args(dfm_ctx *ctx, const char *who, const dfm_ss_mf *mf, int64_t N, bo
 int64_t ss_mf_pad_params(const dfm_ss_params *sets, int64_t n, int r, int p, int L, std::vector<dfm_ss_params> &padded,
                          std::vector<double> &Apad);
 
-// ---- dfm_ss_sim.hip
-// in: rows x n (n fastest, as the lanes of ss_sim_kernel / ss_news_kernel store) -> out: n x rows.
-hipError_t launch_ss_transpose(const double *in, int64_t rows, int64_t n, double *out, hipStream_t st);
+// ---- dfm_ss_lane.hip
+// What follows a one-panel smooth in dfm_ss_simulate and dfm_ss_news (their
+// SsAfter::run): ss_gain_kernel once, one record per row (dfm_ss_lane.h), then
+// the feature's lane kernel over its columns (draws, releases) in passes, a
+// wave of 64 columns per workgroup.  A job states the feature's side.
+struct SsLaneJob {
+  bool sim;                  // the record carries b_t and R_t
+  int nw, w_at;              // the mixed model's weights: their count and where they start in cst
+  std::vector<double> cst;   // the lane kernel's constants (host; the driver uploads them)
+  const void *kernel;        // the lane kernel; it takes one struct by value
+  void *args;                // that struct, on the host: the inputs callback must assign it before it returns
+  size_t lds;                // the kernel's dynamic LDS bytes (beyond 64 KB the driver raises the kernel's cap)
+  int64_t count, per_pass;   // the columns, and how many a pass takes
+  size_t per_out;            // doubles of a column in one output plane
+  int planes;                // output planes a lane writes, one after the other ([per_out][n] each)
+  double *host[2];           // where plane q leaves for ([count][per_out]; null: not wanted)
+};
+struct SsLaneBufs {
+  const double *cst, *rec;   // the constants and the records on the device
+  double *cf, *out;          // the pass's c_t|t [Tt][s][n] and its planes
+  hipStream_t st;
+};
+// Columns c0 .. c0 + n - 1: stage what the lane kernel reads of them, then assign *job.args (the driver launches
+// job.kernel with it as soon as this returns); non-zero: the error.
+using SsLaneInputs = std::function<int(int64_t c0, int64_t n, const SsLaneBufs &b)>;
+// Per pass: inputs, the lane kernel (DFM_KC_FACTORS), the wanted planes
+// transposed to [column][per_out] (DFM_KC_GEMM) and copied out, one stream
+// synchronise.  The gains report as DFM_KC_OLS.
+int ss_lane_run(dfm_ctx *ctx, const SsKept &k, const SsLaneJob &job, const SsLaneInputs &inputs);
 
 // ---- dfm_ss_em.hip
 // mf: the mixed-frequency model (checked): the starts are then the padded

@@ -3,7 +3,10 @@ against route (a) of tests/ss_news_reference.py, which conditions the joint
 Gaussian densely and uses no Kalman recursion.
 
 Shapes: the six ss_mf_reference.CASES (s = 1, odd s, s = 32, r = 16, two K
-chunks of the collapse) and two plain panels, two forecast rows.  Releases:
+chunks of the collapse) and three plain panels (one at r = 16, p = 2, where
+the lane kernel's LDS passes 64 KB and its staging registers are exactly
+filled; 120 releases, so a second wave starts at a later row, 36), two
+forecast rows.  Releases:
 every second observed entry of the last six rows (J from 12 to 492: partial
 waves, several waves, low-frequency releases), a release at row 0, one that is
 the only observed entry of its row, one in the row that holds low-frequency
@@ -179,14 +182,63 @@ def test_weights_depend_on_the_new_mask_only(dfm, ctx, base, i):
     assert np.array_equal(sub.smoothed_new, res.smoothed_new)
 
 
-def test_simulation_smoother_is_unchanged_by_the_shared_code(dfm, ctx):
-    """Its own suite pins its values; here only that two runs still repeat."""
+def test_simulation_smoother_repeats_beside_the_news(dfm, ctx):
+    """The two features run one gain kernel, one lane core and one pass driver
+    (dfm_ss_lane.h / .hip).  The simulation smoother's own suite pins its
+    values; this guards that in a process that has run the news on the same
+    context (its records, its constants, its raised LDS cap) the draws still
+    repeat whatever the pass."""
     X, L, sigma2, A, Q, a0, _, _ = SIM.moment_case(*SIM.GPU_SHAPES[0])
     T, N, r, p, h = SIM.GPU_SHAPES[0]
     z = np.random.default_rng(1).standard_normal((70, SIM.nz(T + h, r, r * p)))
     a = dfm.simulation_smoother(X, L, sigma2, A, Q, draws=70, z=z, a0=a0, horizon=h, ctx=ctx)
     b = dfm.simulation_smoother(X, L, sigma2, A, Q, draws=70, z=z, a0=a0, horizon=h, pass_draws=64, ctx=ctx)
     assert np.array_equal(a.draws, b.draws) and np.isfinite(a.draws).all()
+
+
+def _smallest_sim_shape():
+    X, L, sigma2, A, Q, a0, _, _ = SIM.moment_case(*SIM.GPU_SHAPES[0])   # 9 x 7: a one-entry row, an empty row
+    return X, L, sigma2, A, Q, a0, SIM.GPU_SHAPES[0][4]
+
+
+def _smallest_mixed_case():
+    _, Xn, L, sigma2, A, Q, _, _ = R.inputs(4)   # 30 x 6
+    return Xn, L, sigma2, A, Q, None, R.HORIZON
+
+
+@pytest.mark.parametrize("make", (_smallest_sim_shape, _smallest_mixed_case), ids=("sim9x7", "mixed30x6"))
+def test_both_features_take_over_the_same_smoother(dfm, ctx, make):
+    """Both features start from the same smoother's launches, which the shared
+    driver takes over.  This checks the smoothed paths only, which exist
+    before the driver runs; the gain record itself is checked by the parity
+    tests of both suites.  On the same parameters and the same (new-vintage)
+    panel the simulation smoother's smoothed path, the news' smoothed_new and
+    kalman_smoother's are the same bits, and both features' own outputs are
+    finite.  The simulation smoother has no mixed-frequency model, so on
+    the mixed case's parameters and panel the three run the plain model, and
+    the mixed model's hand-over is the news' against kalman_smoother's."""
+    Xn, L, sigma2, A, Q, a0, h = make()
+    T, N = Xn.shape
+    r, s = np.atleast_2d(L).shape[1], np.atleast_2d(A).shape[1]
+    Xo = Xn.copy()
+    seen = np.argwhere(~np.isnan(Xn))
+    for t, i in seen[seen[:, 0] >= T - 2][::2]:   # releases on the ragged edge ...
+        Xo[t, i] = np.nan
+    t1, i1 = seen[seen[:, 0] > 0][0]              # ... and the first observed entry after row 0
+    Xo[t1, i1] = np.nan
+    tg = np.array([(T - 1, 0), (T + h - 1, N - 1)], dtype=np.int64)
+    ks = dfm.kalman_smoother(Xn, L, sigma2, A, Q, a0=a0, horizon=h, ctx=ctx)
+    sim = dfm.simulation_smoother(Xn, L, sigma2, A, Q, draws=2, z=np.zeros((2, SIM.nz(T + h, r, s))), a0=a0, horizon=h,
+                                  ctx=ctx)
+    news = dfm.nowcast_news(Xo, Xn, L, sigma2, A, Q, targets=tg, a0=a0, horizon=h, ctx=ctx)
+    assert len(news.releases) >= 2 and np.isfinite(sim.draws).all() and np.isfinite(news.weights_f).all()
+    assert np.array_equal(sim.smoothed, ks.smoothed) and np.array_equal(news.smoothed_new, ks.smoothed)
+    assert np.array_equal(sim.smoothed, news.smoothed_new)
+    if make is _smallest_mixed_case:
+        low, w = R.inputs(4)[6:]
+        ksm = dfm.kalman_smoother(Xn, L, sigma2, A, Q, horizon=h, low_freq=low, agg_weights=w, ctx=ctx)
+        mixed = dfm.nowcast_news(Xo, Xn, L, sigma2, A, Q, targets=tg, horizon=h, low_freq=low, agg_weights=w, ctx=ctx)
+        assert np.array_equal(mixed.smoothed_new, ksm.smoothed) and np.array_equal(mixed.smoothed_agg_new, ksm.smoothed_agg)
 
 
 # ------------------------------------------------------------------ refusals

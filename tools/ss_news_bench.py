@@ -12,7 +12,7 @@ the call; best and median of --reps) and, from one further call, the HIP-event
 time of each kernel class through Context.read_timing.
 
   --route news    nowcast_news on the two host vintages: three smooths (collapse
-                  `stats`, filter + smoother `misc`), ss_news_gain_kernel
+                  `stats`, filter + smoother `misc`), ss_gain_kernel
                   (`ols`), ss_news_kernel (`factors`), the transposes (`gemm`)
   --route panels  kalman_smoother on J panels resident on the device, zero on
                   the new mask but for a one at release j, a0 = 0: panel j's

@@ -12,7 +12,7 @@ HIP-event time of each kernel through Context.read_timing.
 
   --route sim     simulation_smoother: collapse (class `stats`), filter +
                   smoother (`misc`), ss_gain_kernel (`ols`), ss_sim_kernel
-                  (`factors`), ss_sim_transpose_kernel (`gemm`)
+                  (`factors`), ss_transpose_kernel (`gemm`)
   --route panels  kalman_smoother on the D pseudo-panels: collapse (`stats`),
                   filter + smoother (`misc`).  Building the pseudo-panels is
                   not timed.  DFM_LIB_PATH may name an earlier build of the
