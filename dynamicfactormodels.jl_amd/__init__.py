@@ -22,7 +22,7 @@ from .api import (Context, DFMError, Stat, DynamicFactorModel, DynamicFactorMode
                   MonteCarloResult, em_factors, DynamicFactorModel_em, EMResult, stationary_covariance,
                   kalman_smoother, ss_parameters, DynamicFactorModel_ss, KalmanResult, StateSpaceResult,
                   ss_em, StateSpaceEMResult, AGG_FLOW, AGG_MEAN, simulation_smoother, SimulationResult,
-                  nowcast_news, NewsResult)
+                  nowcast_news, NewsResult, idio_fill)
 from .api import (criterion_PCp1, criterion_PCp2, criterion_PCp3, criterion_ICp1,  # noqa: F401
                   criterion_ICp2, criterion_ICp3, criterion_BIC)
 from . import _lib
@@ -42,5 +42,5 @@ __all__ = [
     "em_factors", "DynamicFactorModel_em", "EMResult",
     "stationary_covariance", "kalman_smoother", "ss_parameters", "DynamicFactorModel_ss", "KalmanResult",
     "StateSpaceResult", "ss_em", "StateSpaceEMResult", "AGG_FLOW", "AGG_MEAN",
-    "simulation_smoother", "SimulationResult", "nowcast_news", "NewsResult",
+    "simulation_smoother", "SimulationResult", "nowcast_news", "NewsResult", "idio_fill",
 ]

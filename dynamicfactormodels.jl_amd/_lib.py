@@ -193,6 +193,16 @@ SIGNATURES = [
                                   c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("dfm_ss_fit", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
                              C.c_int, C.c_int, C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out)]),
+    ("dfm_ss_smooth_ar", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                   C.POINTER(dfm_ss_params), c_double_p, C.POINTER(dfm_ss_spec), c_double_p,
+                                   c_double_p, c_double_p, c_double_p, c_int64_p]),
+    ("dfm_ss_estimate_ar", C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                     c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                     c_double_p]),
+    ("dfm_ss_ar_fill", C.c_int, [c_double_p, C.c_int64, C.c_int64, C.c_int64, c_double_p, C.c_int, c_double_p,
+                                 c_double_p, C.c_int64, c_double_p]),
+    ("dfm_ss_fit_ar", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(dfm_em_spec),
+                                C.c_int, C.c_int, C.POINTER(dfm_em_info), C.POINTER(dfm_ss_fit_out), c_double_p]),
     ("dfm_ss_em", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                             C.POINTER(dfm_ss_params), C.c_int64, C.POINTER(dfm_ss_em_spec), C.POINTER(dfm_ss_em_out),
                             C.POINTER(dfm_ss_em_info)]),

@@ -1140,6 +1140,7 @@ class StateSpaceResult:
     ml_criterion: float = float("nan")
     smoothed_agg: Optional[np.ndarray] = None
     factor_blocks: Optional[tuple] = None
+    idio_ar: Optional[np.ndarray] = None   # idiosyncratic_ar1: rho (N); sigma2 is then the innovation variance
 
 
 @dataclass
@@ -1306,8 +1307,16 @@ def _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, n_w=0):
         (Lc, sg, Ac, Qc, a0c, P0c)
 
 
+def _ss_idio_ar(idio_ar, N):
+    """The checked rho of a call with AR(1) idiosyncratic terms: N float64 entries."""
+    rho = np.ascontiguousarray(_f64(idio_ar).ravel())
+    if len(rho) != N:
+        raise ValueError(f"idio_ar must have one entry per series ({N}), not {len(rho)}")
+    return rho
+
+
 def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int = 0, low_freq=None,
-                    agg_weights=None, ctx: Optional[Context] = None) -> KalmanResult:
+                    agg_weights=None, idio_ar=None, ctx: Optional[Context] = None) -> KalmanResult:
     """Kalman filter and Rauch-Tung-Striebel smoother over the observed entries
     (NaN = missing) of one panel or of M panels of one shape that share the
     parameters (``dfm_ss_smooth``; the model is stated in ``include/dfm.h``).
@@ -1323,12 +1332,21 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     ``P0`` are of that size, and the result carries ``smoothed_agg``.  A mask
     without a marked series is the plain call, bit for bit.  Parameters estimated with factor
     blocks (``ss_em(factor_blocks=...)``) need nothing more here: Lambda, A and
-    Q are taken as given, zeros included."""
+    Q are taken as given, zeros included.
+
+    AR(1) idiosyncratic terms (``dfm_ss_smooth_ar``): ``idio_ar``, N values
+    rho_i inside (-1, 1); ``sigma2`` is then the innovation variance.  The
+    state keeps max(p, 2) lags: ``a0`` and ``P0`` are of that size.  An
+    all-zero ``idio_ar`` runs this path too."""
+    if idio_ar is not None and (low_freq is not None or agg_weights is not None):
+        raise ValueError("idio_ar with low_freq: AR(1) idiosyncratic terms with mixed frequency are not built yet")
     mixed = _ss_mixed(low_freq, agg_weights, np.shape(loadings)[0])   # before anything touches the device
+    rho = None if idio_ar is None else _ss_idio_ar(idio_ar, np.shape(loadings)[0])
     ctx = ctx or default_context()
     single, (buf, M, T, N, ldx, stride, dev) = _ss_panels(x)
     any_low = mixed is not None and bool(mixed[0].any())
-    params, r, _keep = _ss_param_block(N, loadings, sigma2, A, Q, a0, P0, len(mixed[1]) if any_low else 0)
+    params, r, _keep = _ss_param_block(N, loadings, sigma2, A, Q, a0, P0,
+                                       2 if rho is not None else (len(mixed[1]) if any_low else 0))
     h = int(horizon)
     spec = _lib.dfm_ss_spec(h, int(dev))
     filt = np.zeros((M, T, r))
@@ -1338,7 +1356,11 @@ def kalman_smoother(x, loadings, sigma2, A, Q, *, a0=None, P0=None, horizon: int
     nobs = np.zeros(M, dtype=np.int64)
     xp = C.c_void_p(buf.data_ptr() if dev else buf.ctypes.data) if M else None
     agg = None
-    if mixed is None:
+    if rho is not None:
+        ctx.check(ctx.lib.dfm_ss_smooth_ar(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), _dptr(rho), C.byref(spec),
+                                           _lib.ptr(filt), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll),
+                                           nobs.ctypes.data_as(_lib.c_int64_p)))
+    elif mixed is None:
         ctx.check(ctx.lib.dfm_ss_smooth(ctx.h, xp, M, T, N, ldx, stride, C.byref(params), C.byref(spec),
                                         _lib.ptr(filt), _lib.ptr(sm), _lib.ptr(cov), _lib.ptr(ll),
                                         nobs.ctypes.data_as(_lib.c_int64_p)))
@@ -1647,11 +1669,15 @@ def ss_em(x, loadings, sigma2, A, Q, *, a0=None, P0=None, tol: float = 1e-4, max
     return res
 
 
-def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context] = None):
+def ss_parameters(zm, factors, loadings, lags: int = 1, *, idio_ar1: bool = False, ctx: Optional[Context] = None):
     """Steps 2-4 of the two-step fit (``dfm_ss_estimate``) from the
     standardised panel ``zm`` (NaN = missing), the T x r ``factors`` and N x r
     ``loadings``: the idiosyncratic variances, the VAR(``lags``) of the factors
-    by OLS and the stationary covariance.  Returns (sigma2, A, Q, P0)."""
+    by OLS and the stationary covariance.  Returns (sigma2, A, Q, P0).
+    ``idio_ar1=True`` (``dfm_ss_estimate_ar``) also estimates the AR(1)
+    coefficients of the idiosyncratic terms and returns (sigma2, A, Q, P0,
+    rho): sigma2 the innovation variances, P0 of the state with max(lags, 2)
+    lags."""
     ctx = ctx or default_context()
     Zc = _colmajor(_f64(zm, 2))
     Fc = _colmajor(_f64(factors, 2))
@@ -1664,17 +1690,47 @@ def ss_parameters(zm, factors, loadings, lags: int = 1, *, ctx: Optional[Context
     sg = np.zeros(N)
     A = np.zeros((r, s), order="F")
     Q = np.zeros((r, r), order="F")
+    if idio_ar1:
+        sp = max(r * max(p, 2), 1)
+        P0, rho = np.zeros((sp, sp), order="F"), np.zeros(N)
+        ctx.check(ctx.lib.dfm_ss_estimate_ar(ctx.h, _dptr(Zc), T, N, T, _dptr(Fc), _dptr(Lc), r, p, _lib.ptr(sg),
+                                             _dptr(A), _dptr(Q), _dptr(P0), _lib.ptr(rho)))
+        return sg, np.ascontiguousarray(A), np.ascontiguousarray(Q), np.ascontiguousarray(P0), rho
     P0 = np.zeros((s, s), order="F")
     ctx.check(ctx.lib.dfm_ss_estimate(ctx.h, _dptr(Zc), T, N, T, _dptr(Fc), _dptr(Lc), r, p, _lib.ptr(sg), _dptr(A),
                                       _dptr(Q), _dptr(P0)))
     return sg, np.ascontiguousarray(A), np.ascontiguousarray(Q), np.ascontiguousarray(P0)
 
 
+def idio_fill(x, loadings, idio_ar, smoothed) -> np.ndarray:
+    """The fill rule of the model with AR(1) idiosyncratic terms
+    (``dfm_ss_ar_fill``; host arithmetic, stated in ``include/dfm.h``): the
+    (T, N) panel ``x`` (NaN = missing) completed over the (T + h, r)
+    ``smoothed`` factors of ``kalman_smoother(..., idio_ar=)``.  Returns
+    (T + h, N): observed entries as they are, a missing one Lambda f_t|T plus
+    the idiosyncratic term carried over from the nearest observed rows."""
+    Xc = _colmajor(_f64(x, 2))
+    Lc = _colmajor(_f64(loadings, 2))
+    S = np.ascontiguousarray(_f64(smoothed, 2))
+    T, N = Xc.shape
+    r = Lc.shape[1]
+    if Lc.shape[0] != N or S.shape[1] != r or S.shape[0] < T:
+        raise ValueError("loadings must be N x r and smoothed (T + h) x r")
+    rho = _ss_idio_ar(idio_ar, N)
+    out = np.zeros((S.shape[0], N), order="F")
+    rc = _lib.load().dfm_ss_ar_fill(_dptr(Xc), T, N, T, _dptr(Lc), r, _dptr(rho), _dptr(S), S.shape[0] - T, _dptr(out))
+    if rc:
+        raise DFMError(rc, {-7: "idio_fill: 1 <= r <= 8", -12: "idio_fill: NaN in idio_ar"}
+                       .get(rc, "idio_fill: bad arguments (every idio_ar must be inside (-1, 1))"))
+    return np.ascontiguousarray(out)
+
+
 def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion: str = "ICp2", lags: int = 1,
                           horizon: int = 0, *, kmax: Optional[int] = None, tol: float = 1e-6, max_iter: int = 50,
                           standardize: bool = True, method: str = "two-step", ml_tol: float = 1e-4,
                           ml_max_iter: int = 100, update_init: bool = True, low_freq=None, agg_weights=None,
-                          factor_blocks=None, block_members=None, ctx: Optional[Context] = None) -> StateSpaceResult:
+                          factor_blocks=None, block_members=None, idiosyncratic_ar1: bool = False,
+                          ctx: Optional[Context] = None) -> StateSpaceResult:
     """The two-step estimator of Doz, Giannone & Reichlin (2011) of a panel
     with missing entries (``dfm_ss_fit``): ``em_factors``, a VAR(``lags``) on
     its factors, then the Kalman smoother over the observed entries with
@@ -1698,9 +1754,22 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     order takes the principal components of its members' columns of what the
     blocks before it left unexplained; those are the start's factors
     (``em.factors``) and loadings, each block gets its own VAR, and the ML
-    iteration keeps the restrictions."""
+    iteration keeps the restrictions.
+
+    AR(1) idiosyncratic terms (``dfm_ss_fit_ar``): ``idiosyncratic_ar1=True``
+    gives each series' idiosyncratic term an AR(1) coefficient, estimated from
+    the EM's residuals — ``em_factors`` -> ``ss_parameters(idio_ar1=True)`` ->
+    ``kalman_smoother(idio_ar=)`` -> ``idio_fill`` in one call, bit for bit.
+    The result carries ``idio_ar``, ``sigma2`` is the innovation variance and
+    ``P0`` is that of the state with max(lags, 2) lags."""
     if method not in ("two-step", "ml"):
         raise ValueError('method must be "two-step" or "ml"')
+    if idiosyncratic_ar1:   # before anything touches the device
+        for given, what in ((low_freq is not None or agg_weights is not None, "low_freq"),
+                            (factor_blocks is not None or block_members is not None, "factor_blocks"),
+                            (method == "ml", 'method="ml"')):
+            if given:
+                raise ValueError(f"idiosyncratic_ar1 with {what} is not built yet")
     blocks = _ss_blocks(factor_blocks, block_members, np.shape(x)[-1], number_of_factors)
     if blocks is not None:
         number_of_factors = int(blocks[0].sum())
@@ -1715,6 +1784,8 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     cap = min(int(number_of_factors), 32) if number_of_factors is not None else 32
     any_low = mixed is not None and bool(mixed[0].any())
     lg = max(p, len(mixed[1])) if any_low else p   # lags of the state
+    if idiosyncratic_ar1:
+        lg = max(p, 2)
     sc = max(cap * max(lg, 1), 1)
     col = lambda m, n: np.zeros((m, n), order="F")   # noqa: E731
     Z, X2, xs, xc, fc = col(T, N), col(T, N), col(T, N), col(T, N), col(h, N)
@@ -1727,7 +1798,12 @@ def DynamicFactorModel_ss(x, number_of_factors: Optional[int] = None, criterion:
     ml = {}
     if blocks is not None:
         ml["factor_blocks"] = tuple(int(v) for v in blocks[0])
-    if method == "ml" or mixed is not None or blocks is not None:
+    if idiosyncratic_ar1:
+        rho = np.zeros(N)
+        ctx.check(ctx.lib.dfm_ss_fit_ar(ctx.h, xp, T, N, ldx, C.byref(spec), p, h, C.byref(info), C.byref(out),
+                                        _lib.ptr(rho)))
+        ml["idio_ar"] = rho
+    elif method == "ml" or mixed is not None or blocks is not None:
         mi = int(ml_max_iter) if int(ml_max_iter) >= 0 else 100
         a0, path, minfo = np.zeros(sc), np.full(mi + 1, np.nan), _lib.dfm_ss_em_info()
         mspec = _lib.dfm_ss_em_spec(mi, int(bool(update_init)), h, 0, float(ml_tol))

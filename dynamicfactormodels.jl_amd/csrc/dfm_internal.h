@@ -361,20 +361,26 @@ struct SsParams {   // checked, host
 // The launch geometry of a pass over panels of one shape, stated once (ss_geom).
 // mixed: the mixed-frequency model, whose collapsed row holds a tri(C) | b
 // group per class and the low class's count after l_t.
+// ar: AR(1) idiosyncratic terms, whose collapsed row is the plain one at the
+// update's size ru = 2r (ru = r otherwise).
 struct SsGeom {
   int T, Tt, N, r, s;              // Tt = T + horizon rows, s the state
-  bool mixed;
+  bool mixed, ar;
+  int ru;                          // the size of the update block
   int cq, ncols, nct, NCP, Npad;   // q_t's column, a collapsed row's columns, their 64-wide tiles and 64 nct; N to 16
   int nrt, Tpad, KS;               // the collapse: 64-row tiles, 64 nrt, K chunks of SS_KC columns
   int nrn, Nr, KT;                 // the M-step (its transpose): 64-series tiles, 64 nrn, K chunks of SS_KC rows
 };
-SsGeom ss_geom(int T, int h, int N, int r, int s, bool mixed);
-// Panel b's parameter block (ss_block), as the kernels address it.
+SsGeom ss_geom(int T, int h, int N, int r, int s, bool mixed, bool ar = false);
+// Panel b's parameter block (ss_block), as the kernels address it.  With AR(1)
+// terms Wm, Wv are the pair entries' operands, Wsm, Wsv the start entries' and
+// rho follows winv (all three absent otherwise).
 struct SsBlock {
-  int64_t stride, oWm, oWv, owi, oTm, oQ, oa0, oP0, oL, osig;
+  int64_t stride, oWm, oWv, oWsm, oWsv, owi, orho, oTm, oQ, oa0, oP0, oL, osig;
 };
 SsBlock ss_block(const SsGeom &G);
-int ss_fill_block(const SsParams &pr, const SsGeom &G, const SsBlock &B, double *hp, const uint8_t *low = nullptr);
+int ss_fill_block(const SsParams &pr, const SsGeom &G, const SsBlock &B, double *hp, const uint8_t *low = nullptr,
+                  const double *rho = nullptr);
 // What a one-panel ss_smooth_core call holds when its launches are done and
 // checked, handed to `after` before it is freed: the geometry they ran at, the
 // collapsed rows, the recursion's workspace, and the parameters on both sides
@@ -390,10 +396,13 @@ struct SsAfter {
   virtual ~SsAfter() = default;
 };
 int ss_param_error(dfm_ctx *ctx, const char *who, int rc, int64_t where);
+// The same for the entry points with AR(1) idiosyncratic terms: their limits,
+// and -2 with `where` >= 0 names the column of rho that is not inside (-1, 1).
+int ss_ar_error(dfm_ctx *ctx, const char *who, int rc, int64_t where);
 int ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx, int64_t stride,
                    bool dev, const SsParams &pr, int h, double *filt, double *smooth, double *cov, double *loglik,
                    int64_t *nobs, const dfm_ss_mf *mf = nullptr, double *agg = nullptr, SsAfter *after = nullptr,
-                   const char *who_plain = "dfm_ss_smooth");
+                   const char *who_plain = "dfm_ss_smooth", const double *rho = nullptr);
 // One device block from the stream's pool, freed on the stream on every return path.
 struct StreamBuf {
   void *p = nullptr;

@@ -27,6 +27,11 @@
 // wider operands (a tri(C) | b group per class), ss_filter_kernel<true>, which
 // updates once per class, and ss_smoother_kernel<., true>, which also emits
 // Z_l a_t|T and the low class's moments.
+// With AR(1) idiosyncratic terms (dfm_ss_smooth_ar, dfm_ss_fit_ar) the state is
+// padded to max(p, 2) lags: ss_collapse_ar_kernel forms the quasi-differenced
+// pair entries and the start entries from rows t and t - 1 of the panel and
+// collapses them to 2r x 2r moments, ss_filter_kernel<false, true> updates at
+// that size, and ss_smoother_kernel<false, false> runs unchanged.
 //
 // The host code states once, for the smoother here and for the EM, the launch
 // geometry (ss_geom), a parameter block (ss_block, ss_fill_block), the three
@@ -122,6 +127,99 @@ __global__ __launch_bounds__(256) void ss_collapse_kernel(const double *__restri
   }
 }
 
+// The collapse with AR(1) idiosyncratic terms (include/dfm.h): the same tile,
+// chunks and output row as ss_collapse_kernel, at the update's size ru = 2r.
+// An observed entry whose predecessor is observed is a pair entry, y = x_t -
+// rho x_{t-1} against (Wm, Wv); any other observed entry is a start entry, y =
+// x_t against (Wsm, Wsv).  The predecessor of a tile's first row is the row
+// before it in the panel, that of row 0 is missing.  rho: Npad, zero past N.
+// q_t = sum_pair y^2 / sigma^2 + sum_start x^2 (1 - rho^2) / sigma^2.
+// A stage is two half-stages through the same four LDS images, the masks with
+// their operands and then the values with theirs: the panel is read once and
+// the kernel keeps ss_collapse_kernel's 32 KB.
+__global__ __launch_bounds__(256) void ss_collapse_ar_kernel(const double *__restrict__ X, int64_t ldx, int64_t stride,
+                                                             int T, int N, const double *__restrict__ Wm,
+                                                             const double *__restrict__ Wv,
+                                                             const double *__restrict__ Wsm,
+                                                             const double *__restrict__ Wsv,
+                                                             const double *__restrict__ winv,
+                                                             const double *__restrict__ rho, int NCP, int nct, int KS,
+                                                             int Tpad, int cq, double *__restrict__ part) {
+  __shared__ __attribute__((aligned(16))) double lds[4 * 1024];   // two A and two operand images of one half-stage
+  double *la0 = lds, *la1 = lds + 1024, *lb0 = lds + 2048, *lb1 = lds + 3072;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int rb = blockIdx.x, cb = blockIdx.y % nct, ks = blockIdx.y / nct, b = blockIdx.z;
+  const int abase = rb * 64, bbase = cb * 64;
+  const int Npad = (N + 15) & ~15;
+  const int k0 = ks * SS_KC, k1 = min(Npad, k0 + SS_KC);
+  const bool own_q = cq >= bbase && cq < bbase + 64;
+  const double *Xb = X + (int64_t)b * stride;
+  const int kk = tid >> 4, g4 = (tid & 15) * 4;
+  double acc[8][8];
+  tile_zero(acc);
+  double qs[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int kb = k0; kb < k1; kb += 16) {
+    const int n = kb + kk;
+    double x[5];   // rows abase + g4 - 1 .. abase + g4 + 3
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const int row = abase + g4 + i - 1;
+      x[i] = (n < N && row >= 0 && row < T) ? Xb[(int64_t)n * ldx + row] : NAN;
+    }
+    const int64_t o = (int64_t)n * NCP + bbase + g4;
+    const double2 pm0 = *reinterpret_cast<const double2 *>(Wm + o), pm1 = *reinterpret_cast<const double2 *>(Wm + o + 2);
+    const double2 sm0 = *reinterpret_cast<const double2 *>(Wsm + o), sm1 = *reinterpret_cast<const double2 *>(Wsm + o + 2);
+    const double2 pv0 = *reinterpret_cast<const double2 *>(Wv + o), pv1 = *reinterpret_cast<const double2 *>(Wv + o + 2);
+    const double2 sv0 = *reinterpret_cast<const double2 *>(Wsv + o), sv1 = *reinterpret_cast<const double2 *>(Wsv + o + 2);
+    const double wi = winv[n], rh = rho[n];
+    const double w0 = wi * (1.0 - rh * rh);
+    double yp[4], ys[4];   // the pair and the start value of this thread's four rows (0: not of that kind)
+    const int ob = ss_offB(g4, kk);
+    __syncthreads();   // the previous stage's fragments are read
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool obs = !isnan(x[i + 1]), pair = obs && !isnan(x[i]), start = obs && !pair;
+      yp[i] = pair ? fma(-rh, x[i], x[i + 1]) : 0.0;
+      ys[i] = start ? x[i + 1] : 0.0;
+      la0[ss_offA(g4 + i, kk)] = pair ? 1.0 : 0.0;
+      la1[ss_offA(g4 + i, kk)] = start ? 1.0 : 0.0;
+      if (own_q) qs[i] = fma(yp[i] * yp[i], wi, fma(ys[i] * ys[i], w0, qs[i]));
+    }
+    lb0[ob] = pm0.x; lb0[ob + 1] = pm0.y; lb0[ob + 2] = pm1.x; lb0[ob + 3] = pm1.y;
+    lb1[ob] = sm0.x; lb1[ob + 1] = sm0.y; lb1[ob + 2] = sm1.x; lb1[ob + 3] = sm1.y;
+    __syncthreads();
+    tile_step<ss_offA, ss_offB>(acc, la0, lb0, wr, wc, lane);
+    tile_step<ss_offA, ss_offB>(acc, la1, lb1, wr, wc, lane);
+    __syncthreads();   // the masks' fragments are read
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      la0[ss_offA(g4 + i, kk)] = yp[i];
+      la1[ss_offA(g4 + i, kk)] = ys[i];
+    }
+    lb0[ob] = pv0.x; lb0[ob + 1] = pv0.y; lb0[ob + 2] = pv1.x; lb0[ob + 3] = pv1.y;
+    lb1[ob] = sv0.x; lb1[ob + 1] = sv0.y; lb1[ob + 2] = sv1.x; lb1[ob + 3] = sv1.y;
+    __syncthreads();
+    tile_step<ss_offA, ss_offB>(acc, la0, lb0, wr, wc, lane);
+    tile_step<ss_offA, ss_offB>(acc, la1, lb1, wr, wc, lane);
+  }
+  double *out = part + ((int64_t)b * KS + ks) * (int64_t)Tpad * NCP;
+  tile_epilogue(acc, abase, bbase, wr, wc, lane, [&](int row, int col, double v) {
+    if (col != cq) out[(int64_t)row * NCP + col] = v;
+  });
+  if (own_q) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lds[kk * 64 + g4 + i] = qs[i];
+    __syncthreads();
+    if (tid < 64) {
+      double s = 0.0;
+      for (int k = 0; k < 16; ++k) s += lds[k * 64 + tid];
+      out[(int64_t)(abase + tid) * NCP + cq] = s;
+    }
+  }
+}
+
 struct SsArgs {
   int T, Tt, r, s, ncols, KS, Tpad, NCP;
   const double *part;                  // [panel][chunk][Tpad][NCP]
@@ -149,7 +247,12 @@ struct SsArgs {
 // MF: the mixed-frequency model (include/dfm.h).  A collapsed row then holds
 // one tri(C) | b group per class (high, low), then q_t, n_t, l_t and the low
 // class's count; the update runs once per class with an observed entry.
-template <bool MF>
+//
+// AR: AR(1) idiosyncratic terms (include/dfm.h).  The collapsed row is the
+// plain one at ru = 2r, and the update runs on the first ru columns of P and
+// entries of a, (f_t, f_{t-1}); r still sizes the companion matrix's dot-product
+// rows, Q and the filtered output.  Without AR, ru = r.
+template <bool MF, bool AR>
 __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
   __shared__ double lds[7 * SS_MAT + 7 * 32 + (MF ? 320 : 160) + 4 + (MF ? 24 : 0)];
   __shared__ int ibad, ipiv;
@@ -162,7 +265,8 @@ __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
   const int tid = threadIdx.x, b = blockIdx.x;
   if (g.active && !g.active[b]) return;
   const int T = g.T, Tt = g.Tt, r = g.r, s = g.s, ss = s * s;
-  const int nC = r * (r + 1) / 2, nG = nC + r, cq = MF ? 2 * nG : nG, cn = cq + 1, cl = cq + 2;
+  const int ru = AR ? 2 * r : r;   // the size of the update block
+  const int nC = ru * (ru + 1) / 2, nG = nC + ru, cq = MF ? 2 * nG : nG, cn = cq + 1, cl = cq + 2;
   const double *gTm = g.Tm + (int64_t)b * g.pstride, *gQ = g.Q + (int64_t)b * g.pstride,
                *ga0 = g.a0 + (int64_t)b * g.pstride, *gP0 = g.P0 + (int64_t)b * g.pstride;
   double *au = g.ws + (int64_t)b * Tt * (2 * s + 2 * ss), *ap = au + (int64_t)Tt * s, *Pu = ap + (int64_t)Tt * s,
@@ -187,52 +291,52 @@ __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
   auto update = [&](const double *PZc, const double *Vc, const double *zc, int co, double nt, bool first) {
     const double *PZ = MF ? PZc : P, *V = MF ? Vc : P, *z = MF ? zc : a, *cr = MF ? crow + co : crow;
     auto C = [&](int i, int j) { return cr[ss_tri(i, j)]; };
-    for (int e = tid; e < r * r + r; e += 256) {
-      if (e < r * r) {   // G = I + C V beside the identity
-        const int i = e / r, j = e % r;
+    for (int e = tid; e < ru * ru + ru; e += 256) {
+      if (e < ru * ru) {   // G = I + C V beside the identity
+        const int i = e / ru, j = e % ru;
         double v = i == j ? 1.0 : 0.0;
-        for (int k = 0; k < r; ++k) v = fma(C(i, k), V[k * SS_LS + j], v);
+        for (int k = 0; k < ru; ++k) v = fma(C(i, k), V[k * SS_LS + j], v);
         GA[i * SS_LS + j] = v;
-        GA[i * SS_LS + r + j] = i == j ? 1.0 : 0.0;
+        GA[i * SS_LS + ru + j] = i == j ? 1.0 : 0.0;
       } else {           // d = b - C z
-        const int i = e - r * r;
+        const int i = e - ru * ru;
         double v = cr[nC + i];
-        for (int k = 0; k < r; ++k) v = fma(-C(i, k), z[k], v);
+        for (int k = 0; k < ru; ++k) v = fma(-C(i, k), z[k], v);
         d[i] = v;
       }
     }
     __syncthreads();
-    dfm::block_gj_inverse(GA, r, SS_LS, colj, rowj, sc + 1, &ipiv, &ibad);
-    for (int e = tid; e < s * r + r; e += 256) {
-      if (e < s * r) {   // K = PZ G^-1
-        const int i = e / r, j = e % r;
+    dfm::block_gj_inverse(GA, ru, SS_LS, colj, rowj, sc + 1, &ipiv, &ibad);
+    for (int e = tid; e < s * ru + ru; e += 256) {
+      if (e < s * ru) {   // K = PZ G^-1
+        const int i = e / ru, j = e % ru;
         double v = 0.0;
-        for (int k = 0; k < r; ++k) v = fma(PZ[i * SS_LS + k], GA[k * SS_LS + r + j], v);
+        for (int k = 0; k < ru; ++k) v = fma(PZ[i * SS_LS + k], GA[k * SS_LS + ru + j], v);
         K[i * SS_LS + j] = v;
       } else {           // G^-1 d
-        const int i = e - s * r;
+        const int i = e - s * ru;
         double v = 0.0;
-        for (int k = 0; k < r; ++k) v = fma(GA[i * SS_LS + r + k], d[k], v);
+        for (int k = 0; k < ru; ++k) v = fma(GA[i * SS_LS + ru + k], d[k], v);
         gv[i] = v;
       }
     }
     __syncthreads();
-    for (int e = tid; e < s * r + s + 1; e += 256) {
-      if (e < s * r) {            // K C
-        const int i = e / r, j = e % r;
+    for (int e = tid; e < s * ru + s + 1; e += 256) {
+      if (e < s * ru) {            // K C
+        const int i = e / ru, j = e % ru;
         double v = 0.0;
-        for (int k = 0; k < r; ++k) v = fma(K[i * SS_LS + k], C(k, j), v);
+        for (int k = 0; k < ru; ++k) v = fma(K[i * SS_LS + k], C(k, j), v);
         KC[i * SS_LS + j] = v;
-      } else if (e < s * r + s) {   // a + K d
-        const int i = e - s * r;
+      } else if (e < s * ru + s) {   // a + K d
+        const int i = e - s * ru;
         double v = a[i];
-        for (int k = 0; k < r; ++k) v = fma(K[i * SS_LS + k], d[k], v);
+        for (int k = 0; k < ru; ++k) v = fma(K[i * SS_LS + k], d[k], v);
         an[i] = v;
       } else {                    // the class's term of the log-likelihood, with z and V from before the update
         double ba = 0.0, aCa = 0.0, dPg = 0.0;
-        for (int i = 0; i < r; ++i) {
+        for (int i = 0; i < ru; ++i) {
           double ca = 0.0, pg = 0.0;
-          for (int k = 0; k < r; ++k) {
+          for (int k = 0; k < ru; ++k) {
             ca = fma(C(i, k), z[k], ca);
             pg = fma(V[i * SS_LS + k], gv[k], pg);
           }
@@ -253,7 +357,7 @@ __global__ __launch_bounds__(256) void ss_filter_kernel(SsArgs g) {
       if (e < ss) {   // P - K C PZ'
         const int i = e / s, j = e % s;
         double v = P[i * SS_LS + j];
-        for (int k = 0; k < r; ++k) v = fma(-KC[i * SS_LS + k], PZ[j * SS_LS + k], v);
+        for (int k = 0; k < ru; ++k) v = fma(-KC[i * SS_LS + k], PZ[j * SS_LS + k], v);
         W[i * SS_LS + j] = v;
       } else {
         a[e - ss] = an[e - ss];
@@ -561,16 +665,25 @@ int dfm::ss_param_error(dfm_ctx *ctx, const char *who, int rc, int64_t where) {
   return fail(ctx, rc, "%s: bad arguments", who);
 }
 
+int dfm::ss_ar_error(dfm_ctx *ctx, const char *who, int rc, int64_t where) {
+  if (rc == SS_E_LIMIT)
+    return fail(ctx, rc, "%s: AR(1) idiosyncratic terms serve 1 <= r <= 8, 1 <= p <= 8, r max(p, 2) <= 32", who);
+  if (rc == -2 && where >= 0)
+    return fail(ctx, rc, "%s: rho of column %lld (0-based) is not inside (-1, 1)", who, (long long)where);
+  if (rc == SS_E_NAN) return fail(ctx, rc, "%s: NaN in rho, F or Lambda", who);
+  return ss_param_error(ctx, who, rc, where);
+}
+
 int dfm::ss_estep_error(dfm_ctx *ctx, const char *who, long long panel, int flag, int iteration) {
   const char *what = (flag & 2) ? "a G = I + C_t Pff is" : "a P_{t+1|t} is";
   if (iteration < 0) return fail(ctx, SS_E_SINGULAR, "%s: panel %lld: %s not invertible", who, panel, what);
   return fail(ctx, SS_E_SINGULAR, "%s: panel %lld, the E-step of iteration %d: %s not invertible", who, panel, iteration, what);
 }
 
-SsGeom dfm::ss_geom(int T, int h, int N, int r, int s, bool mixed) {
+SsGeom dfm::ss_geom(int T, int h, int N, int r, int s, bool mixed, bool ar) {
   SsGeom G;
-  G.T = T, G.Tt = T + h, G.N = N, G.r = r, G.s = s, G.mixed = mixed;
-  G.cq = (mixed ? 2 : 1) * (r * (r + 1) / 2 + r), G.ncols = mixed ? G.cq + 4 : ss_ncols(r);
+  G.T = T, G.Tt = T + h, G.N = N, G.r = r, G.s = s, G.mixed = mixed, G.ar = ar, G.ru = ar ? 2 * r : r;
+  G.cq = (mixed ? 2 : 1) * (G.ru * (G.ru + 1) / 2 + G.ru), G.ncols = mixed ? G.cq + 4 : ss_ncols(G.ru);
   G.nct = (G.ncols + 63) / 64, G.NCP = G.nct * 64, G.Npad = (N + 15) & ~15;
   G.nrt = (T + 63) / 64, G.Tpad = G.nrt * 64, G.KS = (G.Npad + SS_KC - 1) / SS_KC;
   G.nrn = (N + 63) / 64, G.Nr = G.nrn * 64, G.KT = (((T + 15) & ~15) + SS_KC - 1) / SS_KC;
@@ -584,9 +697,12 @@ SsGeom dfm::ss_geom(int T, int h, int N, int r, int s, bool mixed) {
 SsBlock dfm::ss_block(const SsGeom &G) {
   const int64_t ss = (int64_t)G.s * G.s;
   SsBlock B;
-  B.oWm = 0, B.oWv = B.oWm + (int64_t)G.Npad * G.NCP;
-  B.owi = B.oWv + (int64_t)G.Npad * G.NCP;
-  B.oTm = B.owi + G.Npad;
+  const int64_t img = (int64_t)G.Npad * G.NCP;
+  B.oWm = 0, B.oWv = B.oWm + img;
+  B.oWsm = B.oWv + img, B.oWsv = B.oWsm + (G.ar ? img : 0);   // the start entries' images: AR(1) terms only
+  B.owi = B.oWsv + (G.ar ? img : 0);
+  B.orho = B.owi + G.Npad;
+  B.oTm = B.orho + (G.ar ? G.Npad : 0);
   B.oQ = B.oTm + ss;
   B.oa0 = B.oQ + (int64_t)G.r * G.r;
   B.oP0 = B.oa0 + 32;
@@ -601,10 +717,33 @@ SsBlock dfm::ss_block(const SsGeom &G) {
 // low (mixed frequency): a series' tri(C) | b columns are its class's group
 // (the low class's follows the high class's), and the column after l_t counts
 // the low class.
-int dfm::ss_fill_block(const SsParams &pr, const SsGeom &G, const SsBlock &B, double *hp, const uint8_t *low) {
+// rho (AR(1) terms; G.ar): with z = (lambda, -rho lambda) and z0 = (lambda, 0)
+// of size ru, the pair entries' images are tri(z z') / v | 1 | log v and z / v,
+// the start entries' those of z0 at the stationary variance v / (1 - rho^2).
+int dfm::ss_fill_block(const SsParams &pr, const SsGeom &G, const SsBlock &B, double *hp, const uint8_t *low,
+                       const double *rho) {
   const int N = G.N, NCP = G.NCP, r = pr.r, p = pr.p, s = r * p, nC = r * (r + 1) / 2, nG = nC + r, cq = G.cq;
   std::fill(hp, hp + B.stride, 0.0);
-  for (int i = 0; i < N; ++i) {
+  for (int i = 0; i < N && rho; ++i) {
+    const double v = pr.sigma2[i], rh = rho[i], c0 = (1.0 - rh * rh) / v;
+    const int ru = G.ru, nCu = ru * (ru + 1) / 2;
+    double *wm = &hp[B.oWm + (size_t)i * NCP], *wv = &hp[B.oWv + (size_t)i * NCP];
+    double *wsm = &hp[B.oWsm + (size_t)i * NCP], *wsv = &hp[B.oWsv + (size_t)i * NCP];
+    auto z = [&](int a) { return a < r ? pr.L[(size_t)a * N + i] : -rh * pr.L[(size_t)(a - r) * N + i]; };
+    for (int a = 0; a < ru; ++a) {
+      for (int c = 0; c <= a; ++c) wm[ss_tri(a, c)] = z(a) * z(c) / v;
+      wv[nCu + a] = z(a) / v;
+      if (a >= r) continue;
+      for (int c = 0; c <= a; ++c) wsm[ss_tri(a, c)] = z(a) * z(c) * c0;
+      wsv[nCu + a] = z(a) * c0;
+    }
+    wm[cq + 1] = wsm[cq + 1] = 1.0;
+    wm[cq + 2] = log(v);
+    wsm[cq + 2] = log(v / (1.0 - rh * rh));
+    hp[B.owi + i] = 1.0 / v;
+    hp[B.orho + i] = rh;
+  }
+  for (int i = 0; i < N && !rho; ++i) {
     const double v = pr.sigma2[i];
     const int co = low && low[i] ? nG : 0;
     double *wm = &hp[B.oWm + (size_t)i * NCP], *wv = &hp[B.oWv + (size_t)i * NCP];
@@ -637,9 +776,14 @@ int dfm::ss_estep(dfm_ctx *ctx, const SsGeom &G, const SsBlock &B, const SsEstep
   hipStream_t st = ctx->stream;
   {
     Scope sc(ctx, DFM_KC_STATS);
-    hipLaunchKernelGGL(ss_collapse_kernel, dim3(G.nrt, G.nct * G.KS, (unsigned)n), dim3(256), 0, st, e.X, e.ldx, e.stride,
-                       G.T, G.N, e.par + B.oWm, e.par + B.oWv, e.par + B.owi, e.pstride, e.active, G.NCP, G.nct, G.KS,
-                       G.Tpad, G.cq, e.part);
+    if (G.ar)   // one shared block, every panel active (ss_smooth_core)
+      hipLaunchKernelGGL(ss_collapse_ar_kernel, dim3(G.nrt, G.nct * G.KS, (unsigned)n), dim3(256), 0, st, e.X, e.ldx,
+                         e.stride, G.T, G.N, e.par + B.oWm, e.par + B.oWv, e.par + B.oWsm, e.par + B.oWsv, e.par + B.owi,
+                         e.par + B.orho, G.NCP, G.nct, G.KS, G.Tpad, G.cq, e.part);
+    else
+      hipLaunchKernelGGL(ss_collapse_kernel, dim3(G.nrt, G.nct * G.KS, (unsigned)n), dim3(256), 0, st, e.X, e.ldx,
+                         e.stride, G.T, G.N, e.par + B.oWm, e.par + B.oWv, e.par + B.owi, e.pstride, e.active, G.NCP,
+                         G.nct, G.KS, G.Tpad, G.cq, e.part);
   }
   HIPCHK(ctx, hipGetLastError());
   {
@@ -650,7 +794,8 @@ int dfm::ss_estep(dfm_ctx *ctx, const SsGeom &G, const SsBlock &B, const SsEstep
     g.pstride = e.pstride, g.active = e.active, g.part = e.part, g.ws = e.ws;
     g.filt = e.filt, g.smooth = e.smooth, g.cov = e.cov, g.ll = e.ll, g.nobs = e.nobs, g.flag = e.flag;
     g.opnd = e.opnd, g.mom = e.mom, g.nw = e.nw, g.w = e.w, g.agg = e.agg;
-    auto *filter = G.mixed ? ss_filter_kernel<true> : ss_filter_kernel<false>;
+    auto *filter = G.ar ? ss_filter_kernel<false, true>
+                        : (G.mixed ? ss_filter_kernel<true, false> : ss_filter_kernel<false, false>);
     auto *smoother = e.opnd ? (G.mixed ? ss_smoother_kernel<true, true> : ss_smoother_kernel<true, false>)
                             : (G.mixed ? ss_smoother_kernel<false, true> : ss_smoother_kernel<false, false>);
     hipLaunchKernelGGL(filter, dim3((unsigned)n), dim3(256), 0, st, g);
@@ -697,8 +842,10 @@ int64_t dfm::ss_mf_pad_params(const dfm_ss_params *sets, int64_t n, int r, int p
 // the plain model's caller in the messages.
 int dfm::ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, int64_t N64, int64_t ldx, int64_t stride,
                         bool dev, const SsParams &pr, int h, double *filt, double *smooth, double *cov, double *loglik,
-                        int64_t *nobs, const dfm_ss_mf *mf, double *agg, SsAfter *after, const char *who_plain) {
+                        int64_t *nobs, const dfm_ss_mf *mf, double *agg, SsAfter *after, const char *who_plain,
+                        const double *rho) {
   const char *who = mf ? "dfm_ss_smooth_mf" : who_plain;
+  if (rho && (mf || after)) return fail(ctx, -2, "%s: bad arguments", who);
   if (M < 0 || h < 0 || h > (1 << 20)) return fail(ctx, -2, "%s: bad arguments", who);
   int64_t where = -1;
   int rc = ss_check_params(N64, pr.r, pr.p, pr.L, pr.sigma2, pr.A, pr.Q, pr.a0, pr.P0, &where);
@@ -706,13 +853,13 @@ int dfm::ss_smooth_core(dfm_ctx *ctx, const double *X, int64_t M, int64_t T64, i
   if (M == 0) return 0;
   if (!X || T64 < 1 || N64 < 1 || ldx < T64 || stride < ldx * N64) return fail(ctx, -2, "%s: bad panel layout", who);
   if (T64 + h > (1 << 24) || N64 > (1 << 24)) return fail(ctx, -2, "panel too large");
-  const SsGeom G = ss_geom((int)T64, h, (int)N64, pr.r, pr.r * pr.p, mf != nullptr);
+  const SsGeom G = ss_geom((int)T64, h, (int)N64, pr.r, pr.r * pr.p, mf != nullptr, rho != nullptr);
   const int T = G.T, Tt = G.Tt, r = G.r, s = G.s, ss = s * s;
   // ---- the shared parameters: operands of the collapse, companion form, Q, a0, P0, then the weights
   const SsBlock B = ss_block(G);
   const size_t ow = (size_t)B.stride, total = ow + (mf ? SS_WMAX : 0);
   std::vector<double> hp(total);
-  if ((rc = ss_fill_block(pr, G, B, hp.data(), mf ? mf->low : nullptr))) return ss_param_error(ctx, who, rc, -1);
+  if ((rc = ss_fill_block(pr, G, B, hp.data(), mf ? mf->low : nullptr, rho))) return ss_param_error(ctx, who, rc, -1);
   if (mf) std::copy(mf->w, mf->w + mf->n_w, &hp[ow]);
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
@@ -814,6 +961,42 @@ int dfm_ss_estimate(dfm_ctx *ctx, const double *Zm, int64_t T, int64_t N, int64_
   int64_t where = -1;
   const int rc = ss_estimate(Zm, T, N, ldx, F, L, r, p, sigma_out, A_out, Q_out, P0_out, &where);
   return rc ? ss_param_error(ctx, "dfm_ss_estimate", rc, where) : 0;
+}
+
+int dfm_ss_smooth_ar(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                     const dfm_ss_params *params, const double *rho, const dfm_ss_spec *spec, double *filtered,
+                     double *smoothed, double *smoothed_cov, double *loglik, int64_t *n_observed) {
+  const char *who = "dfm_ss_smooth_ar";
+  if (!ctx) return -1;
+  if (!params || !spec) return fail(ctx, -2, "%s: bad arguments", who);
+  int64_t where = -1;
+  if (int rc = ss_ar_check(params->r, params->p, N, rho, &where)) return ss_ar_error(ctx, who, rc, where);
+  const int L = ss_ar_lags(params->p);
+  std::vector<dfm_ss_params> padded;
+  std::vector<double> Apad;
+  if (ss_mf_pad_params(params, 1, params->r, params->p, L, padded, Apad) >= 0) return fail(ctx, -2, "%s: bad arguments", who);
+  const dfm_ss_params &q = padded[0];
+  DeviceShare gate(ctx->device);
+  const SsParams pr{q.r, q.p, q.lambda, q.sigma2, q.A, q.Q, q.a0, q.P0};
+  return ss_smooth_core(ctx, X, M, T, N, ldx, stride, spec->dev != 0, pr, spec->horizon, filtered, smoothed,
+                        smoothed_cov, loglik, n_observed, nullptr, nullptr, nullptr, who, rho);
+}
+
+int dfm_ss_estimate_ar(dfm_ctx *ctx, const double *Zm, int64_t T, int64_t N, int64_t ldx, const double *F,
+                       const double *L, int r, int p, double *sigma_out, double *A_out, double *Q_out, double *P0_out,
+                       double *rho_out) {
+  if (!ctx) return -1;
+  int64_t where = -1;
+  const int rc = ss_estimate_ar(Zm, T, N, ldx, F, L, r, p, sigma_out, A_out, Q_out, P0_out, rho_out, &where);
+  return rc ? ss_ar_error(ctx, "dfm_ss_estimate_ar", rc, where) : 0;
+}
+
+int dfm_ss_ar_fill(const double *X, int64_t T, int64_t N, int64_t ldx, const double *L, int r, const double *rho,
+                   const double *smoothed, int64_t horizon, double *completed) {
+  if (!X || !L || !smoothed || !completed || T < 1 || ldx < T || horizon < 0 || horizon > (1 << 20)) return -2;
+  if (int rc = ss_ar_check(r, 1, N, rho, nullptr)) return rc;
+  ss_ar_fill(X, T, N, ldx, L, r, rho, smoothed, horizon, completed);
+  return 0;
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // ss_estimate of dfm_ss_host.h, then ss_smooth_core of dfm_ss.hip), its iteration
 // to the quasi-maximum likelihood (dfm_ss_fit_ml: ss_em_core of dfm_ss_em.hip in
 // the smoother's place), both with mixed frequencies (dfm_ss_fit_mf) and all of
-// them with factor blocks (dfm_ss_fit_blocks: the block-wise start).  The
+// them with factor blocks (dfm_ss_fit_blocks: the block-wise start), and the
+// two-step estimator with AR(1) idiosyncratic terms (dfm_ss_fit_ar).  The
 // steps and the return codes are stated in include/dfm.h.
 #include "dfm_host.h"
 #include "dfm_ss_host.h"
@@ -153,9 +154,93 @@ int ss_fit_impl(dfm_ctx *ctx, const char *who, const double *X, int64_t T, int64
   return 0;
 }
 
+// dfm_ss_fit_ar: the two-step fit with AR(1) idiosyncratic terms — dfm_em,
+// ss_estimate_ar, the smoother at the padded state, then the fill rule
+// (ss_ar_fill) on the standardised panel for all three panels.
+int ss_fit_ar_impl(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+                   int horizon, dfm_em_info *info, const dfm_ss_fit_out *out, double *rho_out) {
+  const char *who = "dfm_ss_fit_ar";
+  if (!X || !em_spec || !out || T < 2 || N < 1 || ldx < T || horizon < 0 || horizon > (1 << 20))
+    return fail(ctx, -2, "%s: bad arguments", who);
+  if (p < 1 || p > SS_PMAX) return ss_ar_error(ctx, who, p < 1 ? -2 : SS_E_LIMIT, -1);
+  const int Lg = ss_ar_lags(p);
+  if (em_spec->r > SS_AR_RMAX || (em_spec->r > 0 && em_spec->r * Lg > SS_SMAX)) return ss_ar_error(ctx, who, SS_E_LIMIT, -1);
+  DeviceShare gate(ctx->device);
+  const size_t tn = (size_t)T * N;
+  const int cap = 32;
+  std::vector<double> Z(tn), mu((size_t)N), sd((size_t)N), F((size_t)T * cap), L((size_t)N * cap), ev(cap), Xh;
+  dfm_em_info inf{};
+  int rc = dfm_em(ctx, X, T, N, ldx, em_spec, Z.data(), out->em_completed, mu.data(), sd.data(), F.data(), L.data(),
+                  ev.data(), &inf);
+  if (rc) return rc;
+  const int r = inf.r, s = r * p, sp = r * Lg, h = horizon;   // s: the VAR's columns; sp: the state
+  if (r > SS_AR_RMAX || ss_check_dims(r, Lg)) return ss_ar_error(ctx, who, SS_E_LIMIT, -1);
+  const double *Xs = X;   // the raw panel on the host: its NaN pattern is the mask
+  int64_t lds = ldx;
+  if (em_spec->dev) {
+    Xh.resize(tn);
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipMemcpy2DAsync(Xh.data(), (size_t)T * 8, X, (size_t)ldx * 8, (size_t)T * 8, (size_t)N,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    Xs = Xh.data();
+    lds = T;
+  }
+  std::vector<double> Zm(tn);
+  for (int64_t i = 0; i < N; ++i)
+    for (int64_t t = 0; t < T; ++t)
+      Zm[(size_t)i * T + t] = std::isnan(Xs[(size_t)i * lds + t]) ? NAN : Z[(size_t)i * T + t];
+  std::vector<double> sig((size_t)N), rho((size_t)N), A((size_t)r * s), Apad((size_t)r * sp), Q((size_t)r * r),
+      P0((size_t)sp * sp);
+  int64_t where = -1;
+  rc = ss_estimate_ar(Zm.data(), T, N, T, F.data(), L.data(), r, p, sig.data(), A.data(), Q.data(), P0.data(), rho.data(),
+                      &where);
+  if (rc) return ss_ar_error(ctx, who, rc, where);
+  ss_mf_pad_A(A.data(), r, p, Lg, Apad.data());
+  const int64_t Tt = T + h;
+  std::vector<double> sm((size_t)Tt * r), fill((size_t)Tt * N);
+  const SsParams pr{r, Lg, L.data(), sig.data(), Apad.data(), Q.data(), nullptr, P0.data()};
+  rc = ss_smooth_core(ctx, Zm.data(), 1, T, N, T, (int64_t)tn, false, pr, h, out->filtered, sm.data(), out->smoothed_cov,
+                      out->loglik, nullptr, nullptr, nullptr, nullptr, who, rho.data());
+  if (rc) return rc;
+  ss_ar_fill(Zm.data(), T, N, T, L.data(), r, rho.data(), sm.data(), h, fill.data());
+  auto put = [](double *dst, const std::vector<double> &v, size_t n) {
+    if (dst) std::copy(v.begin(), v.begin() + n, dst);
+  };
+  put(out->em_standardized, Z, tn);
+  put(out->mu, mu, (size_t)N);
+  put(out->sd, sd, (size_t)N);
+  put(out->em_factors, F, (size_t)T * r);
+  put(out->lambda, L, (size_t)N * r);
+  put(out->eigvals, ev, (size_t)r);
+  put(out->sigma2, sig, (size_t)N);
+  put(out->A, A, (size_t)r * s);
+  put(out->Q, Q, (size_t)r * r);
+  put(out->P0, P0, (size_t)sp * sp);
+  put(out->smoothed, sm, (size_t)Tt * r);
+  put(rho_out, rho, (size_t)N);
+  for (int64_t i = 0; i < N; ++i) {
+    for (int64_t t = 0; t < T; ++t) {
+      const double x = Xs[(size_t)i * lds + t], z = fill[(size_t)i * Tt + t];
+      if (out->x_smoothed) out->x_smoothed[(size_t)i * T + t] = z;
+      if (out->x_completed) out->x_completed[(size_t)i * T + t] = std::isnan(x) ? fma(z, sd[i], mu[i]) : x;
+    }
+    for (int64_t k = 0; k < h && out->forecast; ++k)
+      out->forecast[(size_t)i * h + k] = fma(fill[(size_t)i * Tt + T + k], sd[i], mu[i]);
+  }
+  if (info) *info = inf;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dfm_ss_fit_ar(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+                  int horizon, dfm_em_info *info, const dfm_ss_fit_out *out, double *rho_out) {
+  if (!ctx) return -1;
+  return ss_fit_ar_impl(ctx, X, T, N, ldx, em_spec, p, horizon, info, out, rho_out);
+}
 
 int dfm_ss_fit(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                int horizon, dfm_em_info *info, const dfm_ss_fit_out *out) {

@@ -5,7 +5,9 @@
 // VAR(p) by OLS), and of the quasi-ML EM (dfm_ss_em.hip) the spec's defaults,
 // the stopping rule and the checks; of the mixed-frequency model the limits,
 // [A 0], Z_l and the fit's start values of the low series; of the factor
-// blocks the checks, the free mask and the fit's block-wise start; the panels per
+// blocks the checks, the free mask and the fit's block-wise start; of the AR(1)
+// idiosyncratic terms the limits, the checks of rho, its two-step estimate and
+// the fill rule; the panels per
 // pass of both drivers; of the simulation smoother (dfm_ss_sim.hip) the
 // factor of a positive semi-definite matrix, the count of normals, the
 // argument checks and the draws per pass; of the news decomposition
@@ -367,6 +369,151 @@ inline int ss_mf_start(const double *Zm, int64_t T, int64_t N, int64_t ldz, cons
     sigma2[i] = v;
   }
   return 0;
+}
+
+// ------------------------------- AR(1) idiosyncratic terms (dfm_ss_smooth_ar)
+// e_ti = rho_i e_{t-1,i} + u_ti: an observed entry whose predecessor is
+// observed enters quasi-differenced and loads on (f_t, f_{t-1}), so the update
+// has size 2r and the state keeps L = max(p, 2) lags, s = r L (include/dfm.h).
+constexpr int SS_AR_RMAX = 8;            // 2r <= 16: what the filter's update block holds
+constexpr double SS_AR_RHO_MAX = 0.99;   // the clamp of the two-step estimate
+
+inline int ss_ar_lags(int p) { return p > 2 ? p : 2; }
+
+// The limits at the padded state, then rho: null or |rho_i| >= 1 is -2 (*where:
+// the column, -1 for a null rho), NaN is SS_E_NAN.
+inline int ss_ar_check(int r, int p, int64_t N, const double *rho, int64_t *where) {
+  if (where) *where = -1;
+  if (r < 1 || p < 1 || N < 1) return -2;
+  if (r > SS_AR_RMAX) return SS_E_LIMIT;
+  const int rc = ss_check_dims(r, ss_ar_lags(p));
+  if (rc) return rc;
+  if (!rho) return -2;
+  for (int64_t i = 0; i < N; ++i)
+    if (isnan(rho[i])) return SS_E_NAN;
+  for (int64_t i = 0; i < N; ++i)
+    if (!(fabs(rho[i]) < 1.0)) {
+      if (where) *where = i;
+      return -2;
+    }
+  return 0;
+}
+
+// The two-step estimate of rho after step 2: eps_ti = Zm_ti - f_t' lambda_i at
+// the observed entries, P_i the rows t whose entry and predecessor are both
+// observed,
+//   rho_i = sum_P eps_t eps_{t-1} / sum_P eps_{t-1}^2, clamped to +-SS_AR_RHO_MAX,
+//   sigma2_i = sum_P (eps_t - rho_i eps_{t-1})^2 / |P_i|   (the innovation variance).
+// |P_i| < 3 or a zero denominator: rho_i = 0 and sigma2_i stays as it came
+// (step 2's).  Layouts as ss_idio_var; *where names the column of a
+// non-positive variance (SS_E_SIGMA).
+inline int ss_ar_estimate(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                          double *sigma2, double *rho, int64_t *where) {
+  std::vector<double> eps((size_t)T);
+  for (int64_t i = 0; i < N; ++i) {
+    for (int64_t t = 0; t < T; ++t) {
+      const double z = Zm[(size_t)i * ldz + t];
+      double c = 0.0;
+      for (int j = 0; j < r; ++j) c = fma(F[(size_t)j * T + t], L[(size_t)j * N + i], c);
+      eps[(size_t)t] = z - c;   // NaN where z is
+    }
+    double num = 0.0, den = 0.0;
+    int64_t n = 0;
+    for (int64_t t = 1; t < T; ++t) {
+      if (isnan(eps[(size_t)t]) || isnan(eps[(size_t)t - 1])) continue;
+      num += eps[(size_t)t] * eps[(size_t)t - 1];
+      den += eps[(size_t)t - 1] * eps[(size_t)t - 1];
+      ++n;
+    }
+    rho[i] = 0.0;
+    if (n >= 3 && den > 0.0) {
+      double rh = num / den;
+      if (rh > SS_AR_RHO_MAX) rh = SS_AR_RHO_MAX;
+      if (rh < -SS_AR_RHO_MAX) rh = -SS_AR_RHO_MAX;
+      double ss = 0.0;
+      for (int64_t t = 1; t < T; ++t) {
+        if (isnan(eps[(size_t)t]) || isnan(eps[(size_t)t - 1])) continue;
+        const double u = eps[(size_t)t] - rh * eps[(size_t)t - 1];
+        ss += u * u;
+      }
+      rho[i] = rh;
+      sigma2[i] = ss / (double)n;
+    }
+    if (!(sigma2[i] > 0.0) || isinf(sigma2[i])) {
+      if (where) *where = i;
+      return SS_E_SIGMA;
+    }
+  }
+  return 0;
+}
+
+// Steps 2-4 of the two-step fit with AR(1) terms: ss_idio_var, ss_ar_estimate,
+// ss_var_ols, then the stationary covariance of the padded form [A 0] at L =
+// max(p, 2) lags.  As ss_estimate, but P0 is s x s at s = r L and rho (N) is
+// written too.
+inline int ss_estimate_ar(const double *Zm, int64_t T, int64_t N, int64_t ldz, const double *F, const double *L, int r,
+                          int p, double *sigma2, double *A, double *Q, double *P0, double *rho, int64_t *where) {
+  if (r < 1 || p < 1) return -2;
+  if (r > SS_AR_RMAX) return SS_E_LIMIT;
+  const int Lg = ss_ar_lags(p);
+  int rc = ss_check_dims(r, Lg);
+  if (rc) return rc;
+  if ((rc = ss_estimate_args(Zm, T, N, ldz, F, L, r, p, sigma2, A, Q, P0))) return rc;
+  if (!rho) return -2;
+  if ((rc = ss_idio_var(Zm, T, N, ldz, F, L, r, sigma2, where))) return rc;
+  if ((rc = ss_ar_estimate(Zm, T, N, ldz, F, L, r, sigma2, rho, where))) return rc;
+  if ((rc = ss_var_ols(F, T, r, p, A, Q))) return rc;
+  std::vector<double> Apad((size_t)r * r * Lg);
+  ss_mf_pad_A(A, r, p, Lg, Apad.data());
+  return ss_stationary_cov(Apad.data(), Q, r, Lg, P0);
+}
+
+// The fill of the AR(1) model.  X: T x N column-major (ldx), NaN = missing; L:
+// N x r column-major; S: the smoothed factors, (T + h) x r row-major as the
+// smoother returns them; out: (T + h) x N column-major (ld T + h).  An
+// observed entry is copied.  A missing (t, i), t < T + h, becomes lambda_i'
+// f_t|T + e, where with ehat_u = x_ui - lambda_i' f_u|T, u the last observed
+// row before t, v the first after it, d1 = t - u, d2 = v - t:
+//   only u:  e = rho^d1 ehat_u          only v:  e = rho^d2 ehat_v
+//   both:    e = [rho^d1 (1 - rho^(2 d2)) ehat_u + rho^d2 (1 - rho^(2 d1)) ehat_v] / (1 - rho^(2 (d1 + d2)))
+//   neither: e = 0
+inline void ss_ar_fill(const double *X, int64_t T, int64_t N, int64_t ldx, const double *L, int r, const double *rho,
+                       const double *S, int64_t h, double *out) {
+  const int64_t Tt = T + h;
+  std::vector<double> c((size_t)Tt);
+  for (int64_t i = 0; i < N; ++i) {
+    const double *x = X + (size_t)i * ldx, rh = rho[i];
+    double *o = out + (size_t)i * Tt;
+    for (int64_t t = 0; t < Tt; ++t) {
+      double v = 0.0;
+      for (int j = 0; j < r; ++j) v = fma(S[(size_t)t * r + j], L[(size_t)j * N + i], v);
+      c[(size_t)t] = v;
+    }
+    int64_t u = -1, v = 0;   // the last observed row before t, the first after it (T: none; found once per gap)
+    for (int64_t t = 0; t < Tt; ++t) {
+      if (t < T && !isnan(x[t])) {
+        o[t] = x[t];
+        u = t;
+        continue;
+      }
+      if (v <= t) {
+        v = t + 1;
+        while (v < T && isnan(x[v])) ++v;
+      }
+      const bool hu = u >= 0, hv = v < T;
+      const double eu = hu ? x[u] - c[(size_t)u] : 0.0, ev = hv ? x[v] - c[(size_t)v] : 0.0;
+      const double d1 = (double)(t - u), d2 = (double)(v - t);
+      double e = 0.0;
+      if (hu && hv)
+        e = (pow(rh, d1) * (1.0 - pow(rh, 2.0 * d2)) * eu + pow(rh, d2) * (1.0 - pow(rh, 2.0 * d1)) * ev) /
+            (1.0 - pow(rh, 2.0 * (d1 + d2)));
+      else if (hu)
+        e = pow(rh, d1) * eu;
+      else if (hv)
+        e = pow(rh, d2) * ev;
+      o[t] = c[(size_t)t] + e;
+    }
+  }
 }
 
 // ------------------------------------------------ the quasi-ML EM (dfm_ss_em)

@@ -601,6 +601,84 @@ typedef struct dfm_ss_fit_out {
 int dfm_ss_fit(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
                int horizon, dfm_em_info *info, const dfm_ss_fit_out *out);
 
+/* AR(1) idiosyncratic terms (Banbura & Modugno 2014), by quasi-differencing:
+ *   x_ti = lambda_i' f_t + e_ti,  e_ti = rho_i e_{t-1,i} + u_ti,
+ *   u_ti ~ N(0, sigma^2_i),  |rho_i| < 1
+ *   f_t as above: VAR(p).  State alpha_t = (f_t, ..., f_{t-L+1}), L = max(p, 2),
+ *   s = r L; the companion matrix holds [A 0] over the shift (the padded form
+ *   of the mixed-frequency model); a0 has s entries and P0 is s x s; a NULL P0
+ *   is the stationary covariance of the padded form.
+ * sigma^2_i is the innovation variance; the stationary variance of e_ti is
+ * sigma^2_i / (1 - rho_i^2).
+ * Limits: 1 <= r <= 8 (the update has size ru = 2r <= 16), 1 <= p <= 8,
+ * r max(p, 2) <= 32 (-7 beyond).  A NULL rho or |rho_i| >= 1 is -2 (the message
+ * names the column, 0-based), NaN in rho -12.
+ *
+ * Run-wise likelihood.  With m_{-1,i} = 0, an observed entry is one of two
+ * kinds.  A pair entry, m_ti m_{t-1,i} = 1:
+ *   y = x_ti - rho_i x_{t-1,i},  z_i = (lambda_i, -rho_i lambda_i) on alpha[:2r],
+ *   v = sigma^2_i
+ * A start entry, m_ti = 1 and m_{t-1,i} = 0:
+ *   y = x_ti,  z_i = (lambda_i, 0),  v = sigma^2_i / (1 - rho_i^2)
+ * Either way the noise of y is independent across series and, within a run of
+ * observed entries, across rows, so a row still collapses: with ru = 2r
+ *   C_t = sum_i z_i z_i' / v  (ru x ru),  b_t = sum_i z_i y / v  (ru),
+ *   q_t = sum_i y^2 / v,  n_t = sum_i m_ti,  l_t = sum_i log v
+ * and the recursion is the one above with r replaced by ru in the update only:
+ * Pff = P[:ru,:ru], Pf = P[:, :ru], a_f = a[:ru], G = I_ru + C_t Pff.  The
+ * prediction step, the backward pass and the outputs are unchanged at the
+ * padded state; filtered, smoothed and smoothed_cov stay r-sized.
+ * A run that begins after a hole starts from the stationary distribution of
+ * e_ti: for a series observed on one consecutive run (late starters and ragged
+ * edges included) this is the exact likelihood of the model, and with interior
+ * holes it is a composite likelihood that ignores the dependence of e across
+ * the hole.
+ *
+ * Fill (host arithmetic) of a missing (t, i), t < T + h: with ehat_u = x_ui -
+ * lambda_i' f_u|T at an observed row u, u the last observed row before t, v the
+ * first after it, d1 = t - u, d2 = v - t,
+ *   only u (ragged edge, forecast rows):  e = rho^d1 ehat_u
+ *   only v (late starter):                e = rho^d2 ehat_v
+ *   both (the AR(1) bridge):  e = [rho^d1 (1 - rho^(2 d2)) ehat_u
+ *                                  + rho^d2 (1 - rho^(2 d1)) ehat_v] / (1 - rho^(2 (d1 + d2)))
+ *   neither: e = 0
+ * and the fill is lambda_i' f_t|T + e.
+ *
+ * Two-step estimate of rho, after step 2 of dfm_ss_fit: eps_ti = Z_ti - f_t'
+ * lambda_i over the observed entries, P_i the pair rows of series i,
+ *   rho_i = sum_P eps_t eps_{t-1} / sum_P eps_{t-1}^2, clamped to +-0.99
+ *   sigma^2_i = sum_P (eps_t - rho_i eps_{t-1})^2 / |P_i|
+ * with |P_i| < 3 or a zero denominator: rho_i = 0 and sigma^2_i stays step 2's;
+ * a non-positive variance after this is -10. */
+
+/* dfm_ss_smooth with AR(1) idiosyncratic terms: rho has N entries, params->A
+ * is r x rp, params->a0 (s) and params->P0 (s x s) are those of the padded
+ * state, s = r max(p, 2).  An all-zero rho runs this path too. */
+int dfm_ss_smooth_ar(dfm_ctx *ctx, const double *X, int64_t M, int64_t T, int64_t N, int64_t ldx, int64_t stride,
+                     const dfm_ss_params *params, const double *rho, const dfm_ss_spec *spec, double *filtered,
+                     double *smoothed, double *smoothed_cov, double *loglik, int64_t *n_observed);
+
+/* dfm_ss_estimate with the two-step estimate of rho: rho_out (N), sigma_out the
+ * innovation variances, P0_out (s x s) of the padded form, s = r max(p, 2). */
+int dfm_ss_estimate_ar(dfm_ctx *ctx, const double *Zm, int64_t T, int64_t N, int64_t ldx, const double *F,
+                       const double *L, int r, int p, double *sigma_out, double *A_out, double *Q_out, double *P0_out,
+                       double *rho_out);
+
+/* The fill rule.  X: T x N column-major (ldx >= T), NaN = missing; L: N x r
+ * column-major; smoothed: (T + horizon) x r row-major, as dfm_ss_smooth_ar
+ * returns it; completed: (T + horizon) x N column-major (ld T + horizon),
+ * observed entries copied.  Pure host arithmetic; no context. */
+int dfm_ss_ar_fill(const double *X, int64_t T, int64_t N, int64_t ldx, const double *L, int r, const double *rho,
+                   const double *smoothed, int64_t horizon, double *completed);
+
+/* dfm_ss_fit with AR(1) idiosyncratic terms: dfm_em, dfm_ss_estimate_ar,
+ * dfm_ss_smooth_ar on Zm, then the fill rule on the standardised panel:
+ * x_smoothed is the fill's first T rows, x_completed = m ? X : fill sd + mu
+ * (observed entries bit-equal to X), forecast the fill's last h rows in the
+ * panel's units.  out->P0 is s x s at s = r max(p, 2); rho_out: N (may be NULL). */
+int dfm_ss_fit_ar(dfm_ctx *ctx, const double *X, int64_t T, int64_t N, int64_t ldx, const dfm_em_spec *em_spec, int p,
+                  int horizon, dfm_em_info *info, const dfm_ss_fit_out *out, double *rho_out);
+
 /* Quasi-maximum likelihood by EM (Doz, Giannone & Reichlin 2012; Banbura &
  * Modugno 2014 for arbitrary missing patterns), dfm_ss_em: M panels of one
  * shape, each with its own parameters and its own stopping time; the whole
